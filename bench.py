@@ -5,11 +5,14 @@ One step = reset the node table from a pristine on-device copy (fgi_restore, ~0.
 + one invalidation wave from the workload's root batch, with the roots already resident in HBM.
 Both are inside the timed region. Rank 0 prints one JSON line (the driver's contract).
 
-  python bench.py [--gpus N --steps K --warmup W] [--config rmat24] [--no-cpu]
+  python bench.py [--gpus N --steps K --warmup W] [--config rmat24] [--dump-outputs DIR] [--full [--no-cpu]]
 
-N=1 runs BASELINE.json configs[1] (R-MAT scale 24, 4,096 roots, one MI355X). The CPU baseline leg
-times the C++ restatement of the reference cascade (oracle/, parallelised over roots) on a bounded
-sample of the same workload family on this host's cores.
+N=1 runs BASELINE.json configs[1] (R-MAT scale 24, 4,096 roots, one MI355X). A plain run builds the
+graph, warms up, times the K steps and prints the line. --dump-outputs DIR also writes what the last
+timed step computed (dump_outputs). --full adds every other leg to the same line: the instrumented
+pass behind `roofline`, the pipelined and end-to-end legs, the secondary workloads and the CPU
+baseline, which times the C++ restatement of the reference cascade (oracle/, parallelised over
+roots) on this host's cores.
 """
 import argparse
 import glob
@@ -150,6 +153,38 @@ def profiled_traffic(kname, config_scale, live_avg_ms):
 
 
 
+DUMP_SAMPLE = 1 << 21   # handles in the seeded sample that stands for a larger output
+DUMP_SEED = 0x5EEDD0
+
+
+def dump_outputs(path, ids, n_total, counts, flags=None, suffix=""):
+    """--dump-outputs: what the last timed step handed its caller, as float .npy files under `path`
+    (42 MB at the most). `ids`: the wave's invalidated handles; `n_total`: the handles of the whole
+    graph; `flags`: the node table's state flags after the step (single device). A graph of more than
+    DUMP_SAMPLE handles is cut down to a fixed sample of them (DUMP_SEED), the same from run to run:
+      invalidated_ids.npy  float64  the invalidated handles among the sampled ones, ascending
+      state_flags.npy      float32  the sampled handles' state flags
+      sample_handles.npy   float64  the sampled handles, ascending (every handle of a small graph)
+      counts.npy           float64  the step's invalidated count, then V_inv, E_trav and levels per step (E_match
+                                    is left out: it counts the edges the wave's kernels examined, which
+                                    differs from one wave to the next on the same graph and roots)
+    `suffix` tells the ranks of a partitioned run apart (each writes the slots it owns)."""
+    os.makedirs(path, exist_ok=True)
+    ids = np.sort(np.asarray(ids, np.uint32))
+    if n_total > DUMP_SAMPLE:
+        sample = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n_total, DUMP_SAMPLE, dtype=np.int64))
+        member = np.zeros(n_total, bool)
+        member[sample] = True
+        ids = ids[member[ids]]
+    else:
+        sample = np.arange(n_total, dtype=np.int64)
+    np.save(os.path.join(path, f"invalidated_ids{suffix}.npy"), ids.astype(np.float64))
+    np.save(os.path.join(path, f"sample_handles{suffix}.npy"), sample.astype(np.float64))
+    np.save(os.path.join(path, f"counts{suffix}.npy"), np.asarray(counts, np.float64))
+    if flags is not None:
+        np.save(os.path.join(path, f"state_flags{suffix}.npy"), np.asarray(flags)[sample].astype(np.float32))
+
+
 def dump_maps():
     """FGI_MAPS_OUT=<file>: this process's /proc/self/maps (every library mapped by now), so the PCs of
     a crash at exit (e.g. under rocprofv3) can be mapped to libraries and symbols."""
@@ -231,6 +266,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="rmat24")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (instrumented pass and roofline, "
+                         "pipelined, end-to-end, secondary workloads, CPU baseline); the --no-* options trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--cpu-scale", type=int, default=0,
                     help="R-MAT scale of the CPU baseline (default: the workload's own, i.e. the identical graph)")
@@ -345,9 +385,10 @@ def main():
             f"{len(roots)} roots in {build_s:.1f}s, partitioned={partitioned}, comm={comm or 'none'}")
         return g, cfg, n, roots, n_edges, build_s
 
-    def measure(g, roots):
-        """W untimed warm-up steps, then K timed steps between barriers (max over ranks), then the
-        same K steps again with per-level HIP events (the roofline figures)."""
+    def measure(g, roots, n, dump_dir=""):
+        """W untimed warm-up steps, then K timed steps between barriers (max over ranks); dump_dir: the
+        last step's outputs go there (dump_outputs). --full: then the same K steps again with per-level
+        HIP events (the roofline figures), and the pipelined leg."""
         if os.environ.get("FGI_BENCH_DROP_RANK") == str(rank):
             # tests only: this rank leaves before its first wave, as a rank that died would; its peers'
             # first collective must then fail within the bounded waits, naming itself
@@ -378,22 +419,32 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t_start = time.perf_counter()
+        n_last = 0
         for _ in range(args.steps):
-            step(st)
+            n_last = step(st)
         torch.cuda.synchronize()
         if dist:
             dist.barrier()
         elapsed = time.perf_counter() - t_start
+        if dump_dir:
+            K = max(1, args.steps)
+            counts = [n_last, st.v_inv / K, st.e_trav / K, st.levels / K]
+            if partitioned:
+                dump_outputs(dump_dir, g.part_export_ids(), n, counts, suffix=f"_rank{rank}" if world > 1 else "")
+            else:
+                dump_outputs(dump_dir, g.last_wave_ids(), n, counts, g.dump_states()[1])
         g.set_option(pkg.fgi.OPT_LEVEL_TIMING, 1)
-        st_k = pkg.WaveStats()
-        t_k = time.perf_counter()
-        for _ in range(args.steps):
-            step(st_k)
-        torch.cuda.synchronize()
-        instrumented_ms = (time.perf_counter() - t_k) / args.steps * 1e3
+        st_k, instrumented_ms = None, None
+        if args.full:
+            st_k = pkg.WaveStats()
+            t_k = time.perf_counter()
+            for _ in range(args.steps):
+                step(st_k)
+            torch.cuda.synchronize()
+            instrumented_ms = (time.perf_counter() - t_k) / args.steps * 1e3
         v_inv, e_trav, e_match = st.v_inv, st.e_trav, st.e_match
         pipe = None
-        if not partitioned and not args.no_pipelined:
+        if args.full and not partitioned and not args.no_pipelined:
             # pipelined leg (fgi_invalidate_async / fgi_wave_wait, ComputedExt.WhenInvalidated): the next
             # wave is queued before the previous one is waited for, so the host's wait, the published
             # counters' read and the next wave's launches overlap the device's work
@@ -485,7 +536,7 @@ def main():
                          f"({'weak-scaling point: configs[1] generator, 16.8M slots per GPU' if partitioned else 'size sweep'})")
 
     g, cfg, n, roots, n_edges, build_s = build(sel["headline"])
-    m = measure(g, roots)
+    m = measure(g, roots, n, args.dump_outputs)
     st, st_k = m["st"], m["st_k"]
     elapsed = m["elapsed"]
 
@@ -493,7 +544,7 @@ def main():
     # with the roots in host memory and the invalidated ids copied into a pinned host buffer
     e2e = None
     ids_host = None
-    if not partitioned and not args.no_e2e:
+    if args.full and not partitioned and not args.no_e2e:
         out_host = torch.empty(g.n_handles, dtype=torch.int32).pin_memory()
         g.set_option(pkg.fgi.OPT_LEVEL_TIMING, 0)
         for _ in range(max(1, args.warmup)):
@@ -542,35 +593,29 @@ def main():
                        "`value` (the bench contract: inputs resident in HBM)",
                "ids_output": ids_leg}
 
-    if e2e is None and not partitioned:
+    if args.full and e2e is None and not partitioned:
         g.restore()
         ids_host = np.asarray(g.invalidate(roots), np.uint32)
     v_inv, e_trav, e_match_all = m["v_inv"], m["e_trav"], m["e_match"]
-    try:
-        rv, rpath = pkg.fgi.rccl_info()
-        # libfgi resolves RCCL from /opt/rocm's librccl.so.1 at run time (RTLD_LOCAL, part.hip rccl()),
-        # so torch's bundled librccl, loaded first in this process, does not take its place
-        linked = "/opt/rocm"
-        differs = not os.path.realpath(rpath).startswith(os.path.realpath(linked))
-        rccl = {"version": rv, "path": rpath, "linked": linked + "/lib/librccl.so.1",
-                "differs_from_linked": differs, "torch_loaded_first": True}
-        log(f"[rank {rank}] libfgi RCCL: ncclGetVersion {rv} from {rpath}")
-        if differs:
-            log(f"[rank {rank}] WARNING: libfgi is bound to {rpath}, not {linked}/lib/librccl.so.1")
-    except Exception as e:  # informational only
-        rccl = {"error": repr(e)}
+    rccl = None
+    if args.full:
+        try:
+            rv, rpath = pkg.fgi.rccl_info()
+            # libfgi resolves RCCL from /opt/rocm's librccl.so.1 at run time (RTLD_LOCAL, part.hip rccl()),
+            # so torch's bundled librccl, loaded first in this process, does not take its place
+            linked = "/opt/rocm"
+            differs = not os.path.realpath(rpath).startswith(os.path.realpath(linked))
+            rccl = {"version": rv, "path": rpath, "linked": linked + "/lib/librccl.so.1",
+                    "differs_from_linked": differs, "torch_loaded_first": True}
+            log(f"[rank {rank}] libfgi RCCL: ncclGetVersion {rv} from {rpath}")
+            if differs:
+                log(f"[rank {rank}] WARNING: libfgi is bound to {rpath}, not {linked}/lib/librccl.so.1")
+        except Exception as e:  # informational only
+            rccl = {"error": repr(e)}
     g.close()
 
     value = v_inv / elapsed
     gteps = e_trav / elapsed / 1e9
-    # roofline of the dominant kernel: k_level (push and pull levels are one kernel; the split is
-    # reported beside it)
-    kname = "k_level"
-    k_ms = st_k.pull_ms + st_k.expand_ms
-    k_bytes = st_k.pull_bytes + st_k.expand_bytes
-    k_launches = st_k.pull_launches + st_k.expand_launches
-    k_gbs = (k_bytes / (k_ms * 1e-3) / 1e9) if k_ms > 0 else 0.0
-    traffic, traffic_src = profiled_traffic(kname, cfg.get("scale"), k_ms / max(1, k_launches))
     wave_gbs = (st.alg_bytes / (st.kernel_ms * 1e-3) / 1e9) if st.kernel_ms > 0 else 0.0
     result = line_head(world, args.steps, args.warmup, args.config, elapsed, v_inv, workload_name(cfg), n, n_edges,
                        len(roots), parallelism(), cfg)
@@ -589,28 +634,20 @@ def main():
         "remote_msgs_per_step": st.remote_msgs / args.steps,
         "first_wave_s": m["first_wave_s"],
         "build_s": build_s,
-        "roofline": {
-            "bound": "hbm",
-            "kernel": kname,
-            "achieved": k_gbs,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": k_gbs / HBM_PEAK_GBS,
-            "traffic": traffic,
-            "traffic_source": traffic_src,
-            "launches_per_step": k_launches / args.steps,
-            "avg_launch_ms": k_ms / max(1, k_launches),
-            "alg_bytes_per_launch": k_bytes / max(1, k_launches),
-            "timing_pass_ms_per_step": m["instrumented_ms"],
-            "push_levels": {"ms_per_step": st_k.expand_ms / args.steps,
-                            "launches_per_step": st_k.expand_launches / args.steps,
-                            "gbs": (st_k.expand_bytes / (st_k.expand_ms * 1e-3) / 1e9) if st_k.expand_ms > 0 else 0.0},
-            "pull_levels": {"ms_per_step": st_k.pull_ms / args.steps,
-                            "launches_per_step": st_k.pull_launches / args.steps,
-                            "gbs": (st_k.pull_bytes / (st_k.pull_ms * 1e-3) / 1e9) if st_k.pull_ms > 0 else 0.0},
-        },
-        "rccl": rccl,
     })
+    if args.full:
+        # roofline of the dominant kernel: k_level (push and pull levels are one kernel; the split is
+        # reported beside it)
+        K = args.steps
+        push_gbs = (st_k.expand_bytes / (st_k.expand_ms * 1e-3) / 1e9) if st_k.expand_ms > 0 else 0.0
+        pull_gbs = (st_k.pull_bytes / (st_k.pull_ms * 1e-3) / 1e9) if st_k.pull_ms > 0 else 0.0
+        result["roofline"] = dict(
+            kernel_roofline(st_k, K, cfg), timing_pass_ms_per_step=m["instrumented_ms"],
+            push_levels={"ms_per_step": st_k.expand_ms / K, "launches_per_step": st_k.expand_launches / K,
+                         "gbs": push_gbs},
+            pull_levels={"ms_per_step": st_k.pull_ms / K, "launches_per_step": st_k.pull_launches / K,
+                         "gbs": pull_gbs})
+        result["rccl"] = rccl
     # SURVEY.md §8(d)'s layout-A formula B = 28 V_exp + 24 E_trav + 4 E_match + 4 R counts every
     # edge of every expanded node, as a push-only traversal would read them. Pull levels read
     # dependency-list heads instead of those edges, so B / t is a push-equivalent rate that can exceed
@@ -632,14 +669,14 @@ def main():
         result["e2e"] = e2e
 
     # secondary workloads: configs[2] on this one GPU (N = 1), the weak-scaling point (N > 1)
-    for key, name, scale in ([] if args.no_secondary else sel["secondary"]):
+    for key, name, scale in (sel["secondary"] if args.full and not args.no_secondary else []):
         g2, cfg2, n2, roots2, e2, b2 = build(name, scale)
-        m2 = measure(g2, roots2)
+        m2 = measure(g2, roots2, n2)
         g2.close()
         result[key] = brief(m2, cfg2, n2, roots2, e2, b2)
         log(f"[rank {rank}] {key}: {result[key]['ms_per_step']:.4f} ms/step, {result[key]['value'] / 1e9:.2f} G nodes/s")
 
-    if rank == 0 and world == 1 and not args.no_cpu and cfg["kind"] == "rmat":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and cfg["kind"] == "rmat":
         result["cpu_baseline"] = cpu_legs(args, cfg, roots, ids_host, st, value, result.get("configs2_single_gpu"))
     if rank == 0:
         json_out.write(json.dumps(result) + "\n")

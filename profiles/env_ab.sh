@@ -11,7 +11,7 @@ for r in $(seq 1 "$rounds"); do
   for setting in "$@"; do
     i=$((i + 1))
     envs=(); [ "$setting" != "-" ] && read -r -a envs <<< "$setting"
-    env "${envs[@]}" timeout -k 10 240 python bench.py --no-cpu --no-e2e --steps 50 --warmup 5 "${extra[@]}" \
+    env "${envs[@]}" timeout -k 10 240 python bench.py --full --no-cpu --no-e2e --steps 50 --warmup 5 "${extra[@]}" \
       > "$out/s${i}_$r.json" 2> "$out/s${i}_$r.err"
     rc=$?
     if [ $rc -ne 0 ]; then echo "$setting rc=$rc"; exit $rc; fi

@@ -16,7 +16,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
     echo "smoke ok"
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-    timeout -k 10 500 python bench.py $BENCH_ARGS > "$O/bench.json" 2> "$O/bench.err" || exit 22
+    timeout -k 10 500 python bench.py --full $BENCH_ARGS > "$O/bench.json" 2> "$O/bench.err" || exit 22
     cat "$O/bench.json"
 fi
 [ "${SKIP_PROFILE:-1}" = 1 ] && exit 0

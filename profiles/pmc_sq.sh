@@ -2,7 +2,7 @@
 # Instruction-mix PMC pass (SQ counters, one pass) over a short bench run: per-dispatch instruction
 # and cycle counts, used to find latency-bound launches. Usage: profiles/pmc_sq.sh <tag> [bench args]
 TAG=${1:-sq}; shift
-ARGS=${@:-"--steps 3 --warmup 1 --no-cpu"}
+ARGS=${@:-"--full --steps 3 --warmup 1 --no-cpu"}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/sq_$TAG
 mkdir -p "$OUT"

@@ -7,7 +7,7 @@
 set -o pipefail
 TAG=${1:-r01}
 shift
-ARGS=${@:-"--steps 5 --warmup 1 --no-cpu"}
+ARGS=${@:-"--full --steps 5 --warmup 1 --no-cpu"}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p "$OUT"

@@ -2,7 +2,7 @@
 # Kernel trace of a short bench run (no PMC): per-dispatch timeline for gap analysis.
 # Usage: profiles/trace_only.sh <tag> [bench args]
 TAG=${1:-t}; shift
-ARGS=${@:-"--steps 5 --warmup 1 --no-cpu"}
+ARGS=${@:-"--full --steps 5 --warmup 1 --no-cpu"}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/trace_$TAG
 mkdir -p "$OUT"
