@@ -2919,6 +2919,132 @@ void launch_roots(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, con
                        g->vis_bm, o, g->ctr, g->done, publish, rm, imm_dev ? 0 : stamp);
 }
 
+// ---- what the wave drivers share --------------------------------------------------------------------
+// A wave's start: k_wave_init clears the counters, the per-block statistics and the invalidated bitmap,
+// and the visit bitmap too if it is stale. launch = false: the state is known to be clean already (a
+// clean start; a cooperative wave left it so; the fused head clears it itself). clear_vis = false: the
+// cooperative wave, which folds its own visits and never clears the bitmap.
+void wave_start(fgi_graph* g, bool launch, bool clear_vis) {
+    g->wave_clean = false;   // every path dirties the wave state; the ones that leave it clean say so at their end
+    if (launch)
+        hipLaunchKernelGGL(k_wave_init, dim3(kInitBlocks), dim3(kBlock), 0, g->stream, g->ctr, g->blk_stats, g->inv_bm,
+                           clear_vis && g->vis_stale ? g->vis_bm : nullptr, (uint64_t)g->bm_words);
+    if (clear_vis) g->vis_stale = false;
+    g->coop_clean = false;
+}
+
+hipError_t ensure_events(fgi_graph* g, size_t n) {
+    while (g->ev.size() < n) {
+        hipEvent_t e;
+        const hipError_t r = hipEventCreateWithFlags(&e, event_flags());
+        if (r != hipSuccess) return r;
+        g->ev.push_back(e);
+    }
+    return hipSuccess;
+}
+
+// One wave's tally on the host: what fill_wave_stats needs besides the device's counters.
+struct WaveTally {
+    uint64_t levels = 0, e_trav = 0, f_total = 0, pull_levels = 0;
+    uint64_t level_edges = 0, level_f = 0;   // push work run by k_level launches
+    uint64_t fused_edges = 0, fused_f = 0;   // push work run by a persistent launch (the tail, the fused grid)
+    uint64_t remote_msgs = 0;
+    double pull_ms = 0, expand_ms = 0, fused_ms = 0;
+    uint64_t pull_launches = 0, expand_launches = 0, fused_launches = 0;
+    uint64_t syncs = 0;
+    bool totals_only = false;   // wave_wait: no byte split, launch counts or level times; pull_pushed instead
+};
+
+// the wave's totals as the device counted them (tail_account): paths whose levels the host did not all see
+void device_totals(WaveTally* t, const WaveCtr& c) {
+    t->levels = c.n_levels;
+    t->e_trav = c.e_trav;
+    t->f_total = c.f_total;
+    t->pull_levels = c.n_pull;
+}
+
+// A finished level into the tally. ran: the level counts as one of the wave's levels (each driver's own
+// rule); ev: the event pair around its k_level launch, or nullptr if the level was not timed. A timed
+// launch counts whether the level had work or not, so the average launch duration is the one rocprofv3
+// reports for k_level.
+fgi_status tally_level(fgi_graph* g, WaveTally* t, const LevelCtr& lc, bool ran, const hipEvent_t* ev, float* ms_out = nullptr) {
+    const uint64_t F = lvl_F(lc), T = lvl_T(lc);
+    if (ran) {
+        ++t->levels;
+        if (lc.pull) ++t->pull_levels;
+    }
+    if (F) {
+        t->e_trav += T;
+        t->f_total += F;
+        if (!lc.pull) {
+            t->level_edges += T;
+            t->level_f += F;
+        }
+    }
+    if (ev) {
+        float ms = 0;
+        FGI_HIP(g, hipEventElapsedTime(&ms, ev[0], ev[1]));
+        (lc.pull ? t->pull_ms : t->expand_ms) += ms;
+        ++(lc.pull ? t->pull_launches : t->expand_launches);
+        if (ms_out) *ms_out = ms;
+    }
+    return FGI_OK;
+}
+
+// a synchronous wave's span: its event pair, or the device wall clock from WaveCtr::t0 to the last publish
+float wave_span_ms(fgi_graph* g, const WaveCtr& c, bool events) {
+    if (!events) return wall_ms(g, c.t0, g->last_pub_t);
+    float ms = 0;
+    return hipEventElapsedTime(&ms, g->ev_w0, g->ev_w1) == hipSuccess ? ms : 0.f;
+}
+
+// The one fill of fgi_wave_stats, and the one copy of the algorithmic-bytes model. Push
+// level, per traversed edge: col 4 + tag 8 + node-word gather 8; per frontier entry: fr_off 4 + escan 8
+// read, fr_off 4 + fr_len 4 + escan 8 written by the producer, its row length and offset 12 gathered.
+// Pull levels: pull_level_bytes. Final collect: 4 B per invalidated node. Per root 5. Per forwarded
+// target of a partition 8 (written + received).
+void fill_wave_stats(fgi_wave_stats* stats, const WaveCtr& c, uint64_t n_roots, const WaveTally& t, float wave_ms,
+                     std::chrono::steady_clock::time_point t0) {
+    const uint64_t level_b = 20 * t.level_edges + 40 * t.level_f;
+    const uint64_t fused_b = 20 * t.fused_edges + 40 * t.fused_f;
+    const uint64_t pull_b = pull_level_bytes(c);
+    stats->roots += n_roots;
+    stats->levels += t.levels;
+    stats->v_inv += c.inv;
+    stats->e_trav += t.e_trav;
+    stats->e_match += c.e_match;
+    stats->n_flagged += c.n_flagged;
+    stats->f_total += t.f_total;
+    stats->pull_levels += t.pull_levels;
+    stats->pull_edges += c.pull_edges;
+    stats->remote_msgs += t.remote_msgs;
+    stats->alg_bytes += level_b + fused_b + pull_b + 4 * c.inv + 8 * t.remote_msgs + 5 * n_roots;
+    stats->kernel_ms += wave_ms;
+    stats->host_syncs += t.syncs;
+    if (t.totals_only) {
+        stats->pull_pushed += c.pull_pushed;
+    } else {
+        stats->expand_bytes += level_b;
+        stats->fused_push_bytes += fused_b;
+        stats->pull_bytes += pull_b;
+        stats->expand_ms += t.expand_ms;
+        stats->pull_ms += t.pull_ms;
+        stats->fused_ms += t.fused_ms;
+        stats->expand_launches += t.expand_launches;
+        stats->pull_launches += t.pull_launches;
+        stats->fused_launches += t.fused_launches;
+    }
+    stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// Beamer's direction rule on the host (the partitioned drivers; the single engine's k_collect decides on
+// the device): pull a level with T frontier edges once they pass the alpha threshold, stay pulling while
+// the frontier keeps more than the beta share of the nodes
+bool beamer_pull(bool allow_pull, int direction, uint64_t F, uint64_t T, bool last_pull, const WaveParams& wp) {
+    return allow_pull && T != 0 &&
+           (direction == 2 || (direction == 0 && (T > wp.pull_threshold || (last_pull && F > wp.stay_pull_f))));
+}
+
 }  // namespace
 
 #if FGI_PROBE
@@ -2994,10 +3120,7 @@ fgi_status run_wave_coop(fgi_graph* g, uint32_t n_max, const uint32_t* roots_dev
         return set_err(g, FGI_ENOTSUP, "cooperative wave: %u blocks cannot be resident", G);
     FGI_TRY(fold(g));   // visits of a level-launched wave
     if (coop) FGI_TRY(coop_warm(g));
-    g->wave_clean = false;   // this path dirties the wave state (run_wave re-inits)
-    if (!g->coop_clean)
-        hipLaunchKernelGGL(k_wave_init, dim3(kInitBlocks), dim3(kBlock), 0, s, g->ctr, g->blk_stats, g->inv_bm,
-                           (uint32_t*)nullptr, (uint64_t)g->bm_words);
+    wave_start(g, !g->coop_clean, false);   // the previous cooperative wave cleared what it used
     CoopArgs a{};
     a.roots = roots_dev;
     a.imm = imm_dev;
@@ -3102,10 +3225,8 @@ void print_probe(fgi_graph* g, int L0, int L1) {
 }
 #endif
 
-namespace {
-
 #if FGI_VARIANTS
-// FGI_FUSED_BLOCKS: the fused kernels' grid (default one block per CU; measurement)
+namespace {
 
 bool fused_init_in_head() {
     static const bool h = [] {
@@ -3115,6 +3236,7 @@ bool fused_init_in_head() {
     return h;
 }
 
+// FGI_FUSED_BLOCKS: the fused kernels' grid (default one block per CU; measurement)
 uint32_t fused_grid(const fgi_graph* g) {
     static const uint32_t env = [] {
         const char* e = getenv("FGI_FUSED_BLOCKS");
@@ -3123,21 +3245,8 @@ uint32_t fused_grid(const fgi_graph* g) {
     return std::max<uint32_t>((uint32_t)kStats, env ? env : (uint32_t)std::max(g->n_cu, 1));
 }
 
-#endif  // FGI_VARIANTS
-
-hipError_t ensure_events(fgi_graph* g, size_t n) {
-    while (g->ev.size() < n) {
-        hipEvent_t e;
-        const hipError_t r = hipEventCreateWithFlags(&e, event_flags());
-        if (r != hipSuccess) return r;
-        g->ev.push_back(e);
-    }
-    return hipSuccess;
-}
-
 }  // namespace
 
-#if FGI_VARIANTS
 // A wave as fused launches (k_wave_fused head, k_collect + k_level mid pairs, k_wave_fused tail; see
 // above): one host synchronisation when the predicted number of mid pairs suffices. Returns
 // FGI_ENOTSUP (nothing launched) if the fused grid cannot be resident on this device.
@@ -3191,18 +3300,15 @@ static fgi_status run_wave_fused(fgi_graph* g, uint32_t n_roots, const uint32_t*
     a.fin_G = (uint32_t)std::min<uint64_t>(kFinalBlocks, std::max<uint64_t>(kStats, (words + kFinalWpb - 1) / kFinalWpb));
     a.fin_wpb = (words + a.fin_G - 1) / a.fin_G;
     a.status = g->bsum + 6ull * kStatBlocks;
-    g->vis_stale = false;
-    g->coop_clean = false;
     if (n_roots) g->v_dirty = true;
     const auto* node = reinterpret_cast<const unsigned long long*>(g->node);
     FGI_HIP(g, ensure_events(g, 2 * (size_t)kMidMax + 4));
     hipEvent_t* ev = g->ev.data();
     const size_t eh = 2 * (size_t)kMidMax;   // the head's / tail's event pair
     if (timing || stats) FGI_HIP(g, hipEventRecord(g->ev_w0, s));
-    g->wave_clean = false;   // this path dirties the wave state (run_wave re-inits)
-    if (!a.do_init)   // the wave state cleared by its own launch: the head's first barrier has no dirty 4 MB
-        hipLaunchKernelGGL(k_wave_init, dim3(kInitBlocks), dim3(kBlock), 0, s, g->ctr, g->blk_stats, g->inv_bm,
-                           a.clear_vis ? g->vis_bm : nullptr, (uint64_t)g->bm_words);
+    // the wave state cleared by its own launch (the head's first barrier has no dirty 4 MB) unless the
+    // head clears it (do_init, with the visit bitmap: a.clear_vis)
+    wave_start(g, !a.do_init, true);
     if (timing) FGI_HIP(g, hipEventRecord(ev[eh], s));
     hipLaunchKernelGGL(k_wave_fused<false>, dim3(G), dim3(kBlock), 0, s, a);
     if (timing) FGI_HIP(g, hipEventRecord(ev[eh + 1], s));
@@ -3212,13 +3318,14 @@ static fgi_status run_wave_fused(fgi_graph* g, uint32_t n_roots, const uint32_t*
     const PullArgs pa = pull_args(g, g->n_slots, g->inv_bm);
     const CollectArgs c0 = collect_args(g, g->n_slots, wp, 0), c1 = collect_args(g, g->n_slots, wp, 1);
     int P = (g->opt_fused & kFusedNoPredict) ? 0 : std::min(kMidMax, std::max(0, g->last_mid));
-    double pull_ms = 0, expand_ms = 0, fused_ms = 0;
-    uint64_t pull_launches = 0, expand_launches = 0, fused_launches = 1, syncs = 0;
+    WaveTally t;
+    t.fused_launches = 1;
     float ms = 0;
     for (int round = 0;; ++round) {
         if (round > 0) FGI_HIP(g, hipMemsetAsync(g->ctr->mid_kind, 0, sizeof(g->ctr->mid_kind), s));
         for (int i = 0; i < P; ++i) {
-            // the level (mid_base + i) is known on the device only: its parity picks the buffers there
+            // the level (mid_base + i) is known on the device only: its parity picks the buffers there, so
+            // the pair passes both buffers and big_push and does not fit launch_levels (one known level)
             hipLaunchKernelGGL(k_collect, dim3(collect_grid(g, wp)), dim3(kCollectThreads), 0, s, -1 - i, g->ctr, wp,
                                c0, c1, a.big_push);
             if (timing) FGI_HIP(g, hipEventRecord(ev[2 * i], s));
@@ -3229,7 +3336,7 @@ static fgi_status run_wave_fused(fgi_graph* g, uint32_t n_roots, const uint32_t*
         if (timing) FGI_HIP(g, hipEventRecord(ev[eh + 2], s));
         hipLaunchKernelGGL(k_wave_fused<true>, dim3(G), dim3(kBlock), 0, s, a);
         if (timing) FGI_HIP(g, hipEventRecord(ev[eh + 3], s));
-        ++fused_launches;
+        ++t.fused_launches;
         if (g->want_ids) {
             const auto* inv64 = reinterpret_cast<const unsigned long long*>(g->inv_bm);
             hipLaunchKernelGGL(k_final_write, dim3(a.fin_G), dim3(kBlock), 0, s, inv64, words, a.fin_wpb,
@@ -3239,26 +3346,26 @@ static fgi_status run_wave_fused(fgi_graph* g, uint32_t n_roots, const uint32_t*
         FGI_HIP(g, hipMemcpyAsync(g->ctr_host, g->ctr, sizeof(WaveCtr), hipMemcpyDeviceToHost, s));
         if (timing || stats) FGI_HIP(g, hipEventRecord(g->ev_w1, s));   // the round's end (re-recorded if it goes on)
         FGI_HIP(g, hipStreamSynchronize(s));
-        ++syncs;
+        ++t.syncs;
         const WaveCtr& c = *g->ctr_host;
         if (timing) {
-            if (round == 0 && hipEventElapsedTime(&ms, ev[eh], ev[eh + 1]) == hipSuccess) fused_ms += ms;
-            if (hipEventElapsedTime(&ms, ev[eh + 2], ev[eh + 3]) == hipSuccess) fused_ms += ms;
+            if (round == 0 && hipEventElapsedTime(&ms, ev[eh], ev[eh + 1]) == hipSuccess) t.fused_ms += ms;
+            if (hipEventElapsedTime(&ms, ev[eh + 2], ev[eh + 3]) == hipSuccess) t.fused_ms += ms;
             for (int i = 0; i < P; ++i) {
                 const unsigned long long kind = c.mid_kind[i];
                 if (!kind || hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]) != hipSuccess) continue;
                 if (kind == 2) {
-                    pull_ms += ms;
-                    ++pull_launches;
+                    t.pull_ms += ms;
+                    ++t.pull_launches;
                 } else {
-                    expand_ms += ms;
-                    ++expand_launches;
+                    t.expand_ms += ms;
+                    ++t.expand_launches;
                 }
             }
         } else {
             for (int i = 0; i < P; ++i) {
-                pull_launches += c.mid_kind[i] == 2;
-                expand_launches += c.mid_kind[i] == 1;
+                t.pull_launches += c.mid_kind[i] == 2;
+                t.expand_launches += c.mid_kind[i] == 1;
             }
         }
         if (c.broken) {
@@ -3285,36 +3392,14 @@ static fgi_status run_wave_fused(fgi_graph* g, uint32_t n_roots, const uint32_t*
                 "in the fused grid: %llu entries / %llu edges; %llu host syncs; head+tail %.3f ms, pull %.3f ms\n",
                 (unsigned long long)c.inv, (unsigned long long)c.n_levels, (unsigned long long)c.n_pull,
                 (unsigned long long)c.n_mid, (unsigned long long)c.e_trav, (unsigned long long)c.push_f,
-                (unsigned long long)c.push_edges, (unsigned long long)syncs, fused_ms, pull_ms);
-    if (stats) {
-        const uint64_t v = c.inv;
-        stats->roots += n_roots;
-        stats->levels += c.n_levels;
-        stats->v_inv += v;
-        stats->e_trav += c.e_trav;
-        stats->e_match += c.e_match;
-        stats->n_flagged += c.n_flagged;
-        stats->pull_levels += c.n_pull;
-        stats->pull_edges += c.pull_edges;
-        const uint64_t pull_b = pull_level_bytes(c);
-        const uint64_t mid_push_b = 20 * c.mid_push_edges + 40 * c.mid_push_f;
-        const uint64_t fused_push_b = 20 * c.push_edges + 40 * c.push_f;
-        stats->alg_bytes += mid_push_b + fused_push_b + pull_b + 4 * v + 5ull * n_roots;
-        float wave_ms = 0;
-        hipEventElapsedTime(&wave_ms, g->ev_w0, g->ev_w1);
-        stats->kernel_ms += wave_ms;
-        stats->expand_ms += expand_ms;
-        stats->pull_ms += pull_ms;
-        stats->expand_launches += expand_launches;
-        stats->expand_bytes += mid_push_b;
-        stats->pull_bytes += pull_b;
-        stats->pull_launches += pull_launches;
-        stats->f_total += c.f_total;
-        stats->fused_launches += fused_launches;
-        stats->fused_ms += fused_ms;
-        stats->fused_push_bytes += fused_push_b;
-        stats->host_syncs += syncs;
-        stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+                (unsigned long long)c.push_edges, (unsigned long long)t.syncs, t.fused_ms, t.pull_ms);
+    if (stats) {   // the device's totals (tail_account): the mid pairs' push work by k_level, the rest in the fused grid
+        device_totals(&t, c);
+        t.level_edges = c.mid_push_edges;
+        t.level_f = c.mid_push_f;
+        t.fused_edges = c.push_edges;
+        t.fused_f = c.push_f;
+        fill_wave_stats(stats, c, n_roots, t, wave_span_ms(g, c, true), t0);
     }
     return FGI_OK;
 }
@@ -3476,6 +3561,73 @@ static void plan_collects(const fgi_graph* g, const WaveParams& wp, int L0, int 
     }
 }
 
+// Queues the single engine's levels [L0, L0 + group): per level the collect (unless plan_collects
+// leaves it out) and k_level, with the level's event pair g->ev[2 L], g->ev[2 L + 1] around k_level
+// when timing.
+static fgi_status launch_levels(fgi_graph* g, const WaveParams& wp, int L0, int group, int prev_pull, bool timing) {
+    hipStream_t s = g->stream;
+    const auto* node = reinterpret_cast<const unsigned long long*>(g->node);
+    uint32_t skip = 0, pin = 0;   // left-out collects, levels pinned to push
+    plan_collects(g, wp, L0, group, prev_pull, &skip, &pin);
+    for (int k = 0; k < group; ++k) {
+        const int L = L0 + k, buf = L & 1;
+        WaveParams wl = wp;
+        if (k < 32 && ((pin >> k) & 1u)) wl.direction = 1;
+        if (!(k < 32 && ((skip >> k) & 1u)))
+            hipLaunchKernelGGL(k_collect, dim3(collect_grid_at(g, wl, L)), dim3(kCollectThreads), 0, s, L, g->ctr, wl,
+                               collect_args(g, g->n_slots, wl, buf), collect_args(g, g->n_slots, wl, buf), ~0ull);
+        if (timing) {
+            FGI_HIP(g, ensure_events(g, 2 * (size_t)(L + 1) + 2));
+            FGI_HIP(g, hipEventRecord(g->ev[2 * L], s));
+        }
+        hipLaunchKernelGGL(k_level<false>, dim3(wl.grid), dim3(kBlock), 0, s, L, wl, expand_args(g, buf),
+                           expand_args(g, buf), pull_args(g, g->n_slots, g->inv_bm), node, g->vis_bm,
+                           out_for(g, buf ^ 1, nullptr), out_for(g, buf ^ 1, nullptr), g->ctr, g->blk_stats,
+                           g->done, RemoteArgs{}, ~0ull);
+        if (timing) FGI_HIP(g, hipEventRecord(g->ev[2 * L + 1], s));
+    }
+    return FGI_OK;
+}
+
+// the persistent tail behind a group that ended before level L, with the event pair of slot L when timing
+static fgi_status launch_tail(fgi_graph* g, const TailArgs& ta, int L, bool timing) {
+    hipStream_t s = g->stream;
+    if (timing) {
+        FGI_HIP(g, ensure_events(g, 2 * (size_t)(L + 1) + 4));
+        FGI_HIP(g, hipEventRecord(g->ev[2 * L], s));
+    }
+    hipLaunchKernelGGL(k_wave_tail, dim3(tail_blocks(g)), dim3(kBlock), 0, s, ta);
+    if (timing) FGI_HIP(g, hipEventRecord(g->ev[2 * L + 1], s));
+    return FGI_OK;
+}
+
+// From the ring entries of a group's levels [L0, L1): what the automatic choice wanted per level
+// (dirs[l]: the next wave's launch plan, plan_collects) and the wave's head, the levels up to the last one
+// the tail cannot run (a pull level, or a push level of more than tail_edges edges).
+static void head_and_dirs(const WaveCtr& c, int L0, int L1, uint64_t tail_edges, int* head, uint8_t* dirs) {
+    for (int l = L0; l < L1; ++l) {
+        const LevelCtr& lc = c.lvl[l % kRing];
+        dirs[l] = lc.want ? 1 : 0;
+        if (lvl_F(lc) && (lc.pull || lvl_T(lc) > tail_edges)) *head = l + (lc.pull ? tail_head_after_pull() : 1);
+    }
+}
+
+// The bookkeeping after a single-engine wave: its count and id list, the stale-entry estimate
+// (fgi_prune_step's trigger: the invalidated nodes' rows and the matched entries pointing at them) and,
+// if it had roots, what sizes the next wave's level group. dirs = nullptr: the ring rolled over, no plan.
+static void wave_finished(fgi_graph* g, const WaveCtr& c, bool ids_valid, uint32_t* ids, bool had_roots,
+                          const WaveTally& t, int head, std::vector<uint8_t>* dirs) {
+    g->last_wave_n = c.inv;
+    g->ids_valid = ids_valid;
+    g->inv_cur = ids;
+    g->stale_est += t.e_trav + c.e_match;
+    if (!had_roots) return;
+    g->last_levels = (int)std::max<uint64_t>(t.levels, 1);
+    g->last_head = head;
+    if (dirs) g->last_dirs.swap(*dirs);
+    else g->last_dirs.clear();
+}
+
 fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, const uint8_t* imm_dev,
                     fgi_wave_stats* stats, bool ext_roots) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -3508,12 +3660,7 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
     // the previous wave left the counters, statistics and invalidated bitmap zeroed (WaveEnd) and the visit
     // bitmap is clean (fgi_restore swapped in the spare): no init kernel, the roots kernel stamps t0
     const bool clean_start = g->wave_clean && !g->vis_stale && n_roots != 0;
-    g->wave_clean = false;
-    if (!clean_start)
-        hipLaunchKernelGGL(k_wave_init, dim3(kInitBlocks), dim3(kBlock), 0, s, g->ctr, g->blk_stats, g->inv_bm,
-                           g->vis_stale ? g->vis_bm : nullptr, (uint64_t)g->bm_words);
-    g->vis_stale = false;
-    g->coop_clean = false;
+    wave_start(g, !clean_start, true);
 #if FGI_PROBE
     {
         void* pp = nullptr;
@@ -3527,7 +3674,6 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
         g->v_dirty = true;
         launch_roots(g, n_roots, roots_dev, imm_dev, 0u, g->n_handles, 0, ext_roots, clean_start ? 1 : 0);
     }
-    const auto* node = reinterpret_cast<const unsigned long long*>(g->node);
     // the list kernel and the publish of a group leave the state clean once the wave is over (WaveEnd):
     // only when the list kernel runs (ids wanted, not the measurement-only merged publish)
     static const bool list_pub = getenv("FGI_LIST_PUBLISH") && getenv("FGI_LIST_PUBLISH")[0] == '1';
@@ -3553,52 +3699,17 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
     int L = 0, head = 1;
     std::vector<uint8_t> dirs;   // this wave's directions (the next wave's collect grids)
     bool dirs_ok = true;
-    uint64_t levels = 0, e_trav = 0, f_total = 0, pull_levels = 0;
-    double expand_ms = 0, pull_ms = 0, tail_ms = 0;
-    uint64_t expand_launches = 0, expand_edges = 0, expand_f = 0, pull_launches = 0, syncs = 0;
-    uint64_t tail_launches = 0, tail_edges_run = 0, tail_f = 0;
+    WaveTally t;
     bool done = (n_roots == 0);
     bool final_done = false;
     while (!done) {
         const int L0 = L;
         WaveParams wp = wp0;
         if (!allow_pull) wp.direction = 1;
-        uint32_t skip = 0, pin = 0;   // left-out collects, levels pinned to push (plan_collects)
-        plan_collects(g, wp, L0, group, L0 > 0 ? (g->ctr_host->lvl[(L0 - 1) % kRing].pull ? 1 : 0) : -1, &skip, &pin);
-        for (int k = 0; k < group; ++k, ++L) {
-            const int buf = L & 1;
-            WaveParams wl = wp;
-            if (k < 32 && ((pin >> k) & 1u)) wl.direction = 1;
-            if (!(k < 32 && ((skip >> k) & 1u)))
-                hipLaunchKernelGGL(k_collect, dim3(collect_grid_at(g, wl, L)), dim3(kCollectThreads), 0, s, L, g->ctr, wl,
-                                   collect_args(g, g->n_slots, wl, buf), collect_args(g, g->n_slots, wl, buf), ~0ull);
-            if (timing) {
-                while (g->ev.size() < 2 * (size_t)(L + 1) + 2) {
-                    hipEvent_t e;
-                    FGI_HIP(g, hipEventCreateWithFlags(&e, event_flags()));
-                    g->ev.push_back(e);
-                }
-                FGI_HIP(g, hipEventRecord(g->ev[2 * L], s));
-            }
-            hipLaunchKernelGGL(k_level<false>, dim3(wl.grid), dim3(kBlock), 0, s, L, wl, expand_args(g, buf),
-                               expand_args(g, buf), pull_args(g, g->n_slots, g->inv_bm), node, g->vis_bm,
-                               out_for(g, buf ^ 1, nullptr), out_for(g, buf ^ 1, nullptr), g->ctr, g->blk_stats,
-                               g->done, RemoteArgs{}, ~0ull);
-            if (timing) FGI_HIP(g, hipEventRecord(g->ev[2 * L + 1], s));
-        }
-        if (use_tail) {   // the wave's small push levels after the group: one persistent launch
-            const TailArgs ta = tail_args(g, L0, L, wp, tail_edges);
-            if (timing) {
-                while (g->ev.size() < 2 * (size_t)(L + 1) + 4) {
-                    hipEvent_t e;
-                    FGI_HIP(g, hipEventCreateWithFlags(&e, event_flags()));
-                    g->ev.push_back(e);
-                }
-                FGI_HIP(g, hipEventRecord(g->ev[2 * L], s));
-            }
-            hipLaunchKernelGGL(k_wave_tail, dim3(tail_blocks(g)), dim3(kBlock), 0, s, ta);
-            if (timing) FGI_HIP(g, hipEventRecord(g->ev[2 * L + 1], s));
-        }
+        FGI_TRY(launch_levels(g, wp, L0, group, L0 > 0 ? (g->ctr_host->lvl[(L0 - 1) % kRing].pull ? 1 : 0) : -1, timing));
+        L += group;
+        // the wave's small push levels after the group: one persistent launch
+        if (use_tail) FGI_TRY(launch_tail(g, tail_args(g, L0, L, wp, tail_edges), L, timing));
         // the list kernel may publish the counters itself (one launch fewer), but its last block's
         // system-scope release then writes back the whole list first: 11.6 -> 33.7 us for configs[1]'s
         // k_final_write, 0.231 -> 0.262 ms/step (profiles/r12c); measurement only (FGI_LIST_PUBLISH=1)
@@ -3617,7 +3728,7 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
         // recording it after the wait would cost the call a further device round trip
         if (merged) FGI_TRY(counters_published(g, s, events, lp.seq));
         else FGI_TRY(counters_to_host(g, s, events, we));
-        ++syncs;
+        ++t.syncs;
         if (use_tail && g->ctr_host->broken) {   // half a wave is applied: poisoned until fgi_restore (fgi.h)
             FGI_HIP(g, hipMemsetAsync(g->gbar + kGbarTail, 0, sizeof(unsigned long long), s));
             FGI_HIP(g, hipStreamSynchronize(s));
@@ -3631,8 +3742,8 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
         const bool ring_ok = stop - L0 < kRing - 4;
         if (use_tail) {
             float ms = 0;
-            if (timing && hipEventElapsedTime(&ms, g->ev[2 * L], g->ev[2 * L + 1]) == hipSuccess) tail_ms += ms;
-            ++tail_launches;
+            if (timing && hipEventElapsedTime(&ms, g->ev[2 * L], g->ev[2 * L + 1]) == hipSuccess) t.fused_ms += ms;
+            ++t.fused_launches;
             for (int l = std::max(L, stop - (kRing - 4)); trace && l < stop; ++l) {
                 const LevelCtr& lc = g->ctr_host->lvl[l % kRing];
                 fprintf(stderr, "[fgi] level %d push (tail): frontier %llu edges %llu chunk x%llu\n", l,
@@ -3641,41 +3752,18 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
         }
         if (ring_ok) {
             dirs.resize(std::max<size_t>(dirs.size(), (size_t)stop), 0);
-            for (int l = L0; l < L; ++l) dirs[l] = g->ctr_host->lvl[l % kRing].want ? 1 : 0;
+            head_and_dirs(*g->ctr_host, L0, L, tail_edges, &head, dirs.data());
         } else {
             dirs_ok = false;
         }
         for (int l = L0; l < L && ring_ok; ++l) {
             const LevelCtr& lc = g->ctr_host->lvl[l % kRing];
-            if (lvl_F(lc) && (lc.pull || lvl_T(lc) > tail_edges)) head = l + (lc.pull ? tail_head_after_pull() : 1);
             float ms = 0;
-            if (timing) {
-                // every k_level launch counts (empty levels too), so the average launch duration
-                // is the one rocprofv3 reports for k_level
-                FGI_HIP(g, hipEventElapsedTime(&ms, g->ev[2 * l], g->ev[2 * l + 1]));
-                if (lc.pull) {
-                    pull_ms += ms;
-                    ++pull_launches;
-                } else {
-                    expand_ms += ms;
-                    ++expand_launches;
-                }
-            }
-            const uint64_t lF = lvl_F(lc), lT = lvl_T(lc);
-            if (lF && !use_tail) {
-                ++levels;
-                e_trav += lT;
-                f_total += lF;
-                if (lc.pull) {
-                    ++pull_levels;
-                } else {
-                    expand_edges += lT;
-                    expand_f += lF;
-                }
-            }
+            // a level with a frontier counts; with the tail the device's totals replace the work figures below
+            FGI_TRY(tally_level(g, &t, lc, lvl_F(lc) != 0, timing ? &g->ev[2 * l] : nullptr, &ms));
             if (trace)
                 fprintf(stderr, "[fgi] level %d %s: frontier %llu edges %llu chunk x%llu k_level %.3f ms\n", l,
-                        lc.pull ? "pull" : "push", (unsigned long long)lF, (unsigned long long)lT,
+                        lc.pull ? "pull" : "push", (unsigned long long)lvl_F(lc), (unsigned long long)lvl_T(lc),
                         (unsigned long long)lc.mult, ms);
         }
 #if FGI_PROBE
@@ -3703,33 +3791,18 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
         FGI_HIP(g, hipGetLastError());
         FGI_TRY(counters_to_host(g, s, events));
     }
-    if (use_tail && final_done) {   // the device's totals (tail_account)
-        const WaveCtr& c = *g->ctr_host;
-        levels = c.n_levels;
-        e_trav = c.e_trav;
-        f_total = c.f_total;
-        pull_levels = c.n_pull;
-        tail_edges_run = c.mid_push_edges;
-        tail_f = c.mid_push_f;
-        expand_edges = c.push_edges - c.mid_push_edges;
-        expand_f = c.push_f - c.mid_push_f;
+    const WaveCtr& c = *g->ctr_host;
+    if (use_tail && final_done) {   // the device's totals (tail_account): the tail's share of the push work apart
+        device_totals(&t, c);
+        t.fused_edges = c.mid_push_edges;
+        t.fused_f = c.mid_push_f;
+        t.level_edges = c.push_edges - c.mid_push_edges;
+        t.level_f = c.push_f - c.mid_push_f;
     }
     if (imm_dev && n_roots) note_words(g);   // immediate roots changed node words
     // the last group's list kernel and publish saw the wave over (the host's loop ends on the same test)
     g->wave_clean = leave_clean && final_done;
-    g->last_wave_n = g->ctr_host->inv;
-    g->ids_valid = g->want_ids;
-    g->inv_cur = g->inv;
-    // entries this wave made stale: the invalidated nodes' rows and the matched entries pointing at
-    // them (fgi_prune_step's trigger)
-    g->stale_est += e_trav + g->ctr_host->e_match;
-    if (n_roots) {
-        g->last_levels = (int)std::max<uint64_t>(levels, 1);
-        g->last_head = head;
-        if (dirs_ok) g->last_dirs.swap(dirs);
-        else g->last_dirs.clear();
-    }
-    const WaveCtr& c = *g->ctr_host;
+    wave_finished(g, c, g->want_ids, g->inv, n_roots != 0, t, head, dirs_ok ? &dirs : nullptr);
     if (trace)
         fprintf(stderr,
                 "[fgi] wave: %llu invalidated; pull: live %llu, survivors %llu, queued %llu, dependencies "
@@ -3737,41 +3810,8 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
                 (unsigned long long)c.inv, (unsigned long long)c.pull_live, (unsigned long long)c.pull_surv,
                 (unsigned long long)c.pull_tail, (unsigned long long)c.pull_edges, (unsigned long long)c.pull_win);
     if (stats) {
-        const uint64_t v = c.inv;
-        stats->roots += n_roots;
-        stats->levels += levels;
-        stats->v_inv += v;
-        stats->e_trav += e_trav;
-        stats->e_match += c.e_match;
-        stats->n_flagged += c.n_flagged;
-        stats->pull_levels += pull_levels;
-        stats->pull_edges += c.pull_edges;
-        // Algorithmic bytes. Push level, per traversed edge: col 4 + tag 8 +
-        // node-word gather 8; per frontier entry: fr_off 4 + escan 8 read, fr_off 4 + fr_len 4 +
-        // escan 8 written by the producer, its row length and offset 12 gathered. Final collect:
-        // 4 B per invalidated node. Per root 5.
-        const uint64_t push_b = 20 * (expand_edges + tail_edges_run) + 40 * (expand_f + tail_f);
-        const uint64_t pull_b = pull_level_bytes(c);
-        stats->alg_bytes += push_b + pull_b + 4 * v + 5ull * n_roots;
-        float wave_ms = 0;
-        if (events) {
-            hipEventElapsedTime(&wave_ms, g->ev_w0, g->ev_w1);
-        } else {
-            wave_ms = wall_ms(g, c.t0, g->last_pub_t);
-        }
-        stats->kernel_ms += wave_ms;
-        stats->expand_ms += expand_ms;
-        stats->pull_ms += pull_ms;
-        stats->expand_launches += expand_launches;
-        stats->expand_bytes += 20 * expand_edges + 40 * expand_f;
-        stats->fused_launches += tail_launches;
-        stats->fused_ms += tail_ms;
-        stats->fused_push_bytes += 20 * tail_edges_run + 40 * tail_f;
-        stats->pull_bytes += pull_b;
-        stats->pull_launches += pull_launches;
-        stats->f_total += f_total;
-        stats->host_syncs += syncs + (final_done ? 0 : 1);
-        stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (!final_done) ++t.syncs;   // no roots: the final collect's
+        fill_wave_stats(stats, c, n_roots, t, wave_span_ms(g, c, events), t0);
     }
     return FGI_OK;
 }
@@ -3809,35 +3849,16 @@ fgi_status run_wave_async(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_
     if (!(wp0.direction != 1 && pull_ready(g, wp0))) wp.direction = 1;
     // as run_wave: no init kernel after a wave that left the state clean (the queue is stream-ordered)
     const bool clean_start = g->wave_clean && !g->vis_stale && n_roots != 0;
-    g->wave_clean = false;
-    if (!clean_start)
-        hipLaunchKernelGGL(k_wave_init, dim3(kInitBlocks), dim3(kBlock), 0, s, g->ctr, g->blk_stats, g->inv_bm,
-                           g->vis_stale ? g->vis_bm : nullptr, (uint64_t)g->bm_words);
-    g->vis_stale = false;
-    g->coop_clean = false;
-    const auto* node = reinterpret_cast<const unsigned long long*>(g->node);
+    wave_start(g, !clean_start, true);
     // the previous wave's levels in the group (up to 8), its head at least; the tail runs the rest
     int group = std::min(8, std::max(std::max(1, g->last_head), g->last_levels));
     if (n_roots) {
         g->v_dirty = true;
         launch_roots(g, n_roots, roots_dev, imm_dev, 0u, g->n_handles, 0, true, clean_start ? 1 : 0);
-        uint32_t skip = 0, pin = 0;
-        plan_collects(g, wp, 0, group, -1, &skip, &pin);
-        for (int L = 0; L < group; ++L) {
-            const int buf = L & 1;
-            WaveParams wl = wp;
-            if (L < 32 && ((pin >> L) & 1u)) wl.direction = 1;
-            if (!(L < 32 && ((skip >> L) & 1u)))
-                hipLaunchKernelGGL(k_collect, dim3(collect_grid_at(g, wl, L)), dim3(kCollectThreads), 0, s, L, g->ctr, wl,
-                                   collect_args(g, g->n_slots, wl, buf), collect_args(g, g->n_slots, wl, buf), ~0ull);
-            hipLaunchKernelGGL(k_level<false>, dim3(wl.grid), dim3(kBlock), 0, s, L, wl, expand_args(g, buf),
-                               expand_args(g, buf), pull_args(g, g->n_slots, g->inv_bm), node, g->vis_bm,
-                               out_for(g, buf ^ 1, nullptr), out_for(g, buf ^ 1, nullptr), g->ctr, g->blk_stats,
-                               g->done, RemoteArgs{}, ~0ull);
-        }
+        FGI_TRY(launch_levels(g, wp, 0, group, -1, false));
         TailArgs ta = tail_args(g, 0, group, wp, ~0ull);
         ta.all = 1;
-        hipLaunchKernelGGL(k_wave_tail, dim3(tail_blocks(g)), dim3(kBlock), 0, s, ta);
+        FGI_TRY(launch_tail(g, ta, group, false));
     } else {
         group = 0;
     }
@@ -3939,51 +3960,28 @@ fgi_status wave_wait(fgi_graph* g, uint64_t ticket, uint64_t* out_n, const uint3
     }
     // the wave's totals from the device (tail_account); the group's levels from the ring while it has not
     // rolled over (the next wave's group size)
-    const uint64_t levels = c.n_levels, e_trav = c.e_trav, f_total = c.f_total, pull_levels = c.n_pull;
-    const uint64_t push_e = c.push_edges, push_f = c.push_f;
-    uint64_t head = (uint64_t)std::max(1, g->last_head);
+    WaveTally t;
+    device_totals(&t, c);
+    t.fused_edges = c.push_edges;   // every push level, the group's too: totals_only fills no split
+    t.fused_f = c.push_f;
+    t.syncs = 1;
+    t.totals_only = true;
+    int head = std::max(1, g->last_head);
     const uint64_t stop = a.group ? std::max<uint64_t>((uint64_t)a.group, c.cur) : 0;
-    if (stop < (uint64_t)kRing - 4) {
+    const bool ring_ok = stop < (uint64_t)kRing - 4;
+    std::vector<uint8_t> dirs;   // the next waves' launch plans (plan_collects); the tail's levels push
+    if (ring_ok) {
         head = 1;
-        std::vector<uint8_t> dirs(stop, 0);   // the next waves' launch plans (plan_collects); the tail's levels push
-        for (uint64_t l = 0; l < (uint64_t)a.group; ++l) {
-            const LevelCtr& lc = c.lvl[l % kRing];
-            dirs[l] = lc.want ? 1 : 0;
-            if (lvl_F(lc) && (lc.pull || lvl_T(lc) > (uint64_t)tail_blocks(g) * kChunk))
-                head = l + (lc.pull ? tail_head_after_pull() : 1);
-        }
-        if (a.n_roots) g->last_dirs.swap(dirs);
-    } else if (a.n_roots) {
-        g->last_dirs.clear();
+        dirs.assign(stop, 0);
+        // the tail's grid sets the threshold here (run_wave: FGI_TAIL_EDGES)
+        head_and_dirs(c, 0, a.group, (uint64_t)tail_blocks(g) * kChunk, &head, dirs.data());
     }
     a.n_inv = c.inv;
-    g->last_wave_n = c.inv;
-    g->inv_cur = (ticket & 1) ? g->inv_alt : g->inv;
-    g->ids_valid = true;
-    g->stale_est += e_trav + c.e_match;
-    if (a.n_roots) {
-        g->last_levels = (int)std::max<uint64_t>(levels, 1);
-        g->last_head = (int)head;
-        if (c.t_max > g->pool_top / (uint64_t)std::max(1, g->opt_pull_alpha)) g->lists_wanted = true;
-    }
+    wave_finished(g, c, true, (ticket & 1) ? g->inv_alt : g->inv, a.n_roots != 0, t, head, ring_ok ? &dirs : nullptr);
+    if (a.n_roots && c.t_max > g->pool_top / (uint64_t)std::max(1, g->opt_pull_alpha)) g->lists_wanted = true;
     if (out_n) *out_n = c.inv;
     if (ids_dev) *ids_dev = g->inv_cur;
-    if (stats) {
-        stats->roots += a.n_roots;
-        stats->levels += levels;
-        stats->v_inv += c.inv;
-        stats->e_trav += e_trav;
-        stats->e_match += c.e_match;
-        stats->n_flagged += c.n_flagged;
-        stats->pull_levels += pull_levels;
-        stats->pull_edges += c.pull_edges;
-        stats->alg_bytes += 20 * push_e + 40 * push_f + pull_level_bytes(c) + 4 * c.inv + 5ull * a.n_roots;
-        stats->kernel_ms += wall_ms(g, c.t0, pub[kPubWords + 1]);
-        stats->f_total += f_total;
-        stats->host_syncs += 1;
-        stats->pull_pushed += c.pull_pushed;
-        stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a.t0).count();
-    }
+    if (stats) fill_wave_stats(stats, c, a.n_roots, t, wall_ms(g, c.t0, pub[kPubWords + 1]), a.t0);
     return FGI_OK;
 }
 
@@ -4040,18 +4038,62 @@ uint64_t part_plan_key(const fgi_graph* g) {
 // spin wait); otherwise by the device wall clock between WaveCtr::t0 and the wave's last publish
 static inline bool part_events(const fgi_graph* g) { return g->opt_level_timing != 0 || !FGI_SPIN_WAIT; }
 
+// What a partitioned wave's level launches share, built once per wave. front: the invalidated bitmap
+// over all slots that the pull levels probe (hot heads are global ids), front_global as gathered before
+// a pull level. alias: one rank without collectives probes its own invalidated bitmap instead (no copy
+// into front_global per pull level) when its hot snapshot sits where the partition's would (the same
+// word count: no detached handles).
+struct PartLevels {
+    bool coll, alias;
+    const uint32_t* front;
+    uint32_t* hot_base;
+    RemoteArgs ra;
+};
+
+static PartLevels part_levels(const fgi_graph* g, const PartView& pv, bool coll) {
+    const bool alias = !coll && g->hot_w0 == g->bm_words;
+    return PartLevels{coll, alias, alias ? g->inv_bm : pv.front_global, alias ? g->inv_bm : pv.front_global,
+                      RemoteArgs{pv.base, pv.n_local, pv.block, pv.world, pv.ver_all, pv.sent_bm, pv.send_buf, pv.send_cnt}};
+}
+
+// Before a pull level's launches: the level's direction for its kernels (the flag's high word is zero:
+// the ring slot was cleared two levels ago or at wave start, so a 32-bit device-side set is the whole
+// store) and, without collectives, this rank's own words as the global bitmap. With collectives the
+// caller gathers it.
+static fgi_status part_pull_begin(fgi_graph* g, const PartView& pv, const PartLevels& pl, int L) {
+    hipStream_t s = g->stream;
+    FGI_HIP(g, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&g->ctr->lvl[L % kRing].pull), 1, 1, s));
+    if (!pl.coll && !pl.alias)
+        FGI_HIP(g, hipMemcpyAsync(pv.front_global, g->inv_bm, (size_t)pv.block / 32 * 4, hipMemcpyDeviceToDevice, s));
+    return FGI_OK;
+}
+
+// a partition's level L: the collect and k_level, with the event pair ev around k_level (nullptr: not timed)
+static fgi_status launch_part_level(fgi_graph* g, const PartView& pv, const PartLevels& pl, const WaveParams& wp, int L,
+                                    const hipEvent_t* ev) {
+    hipStream_t s = g->stream;
+    const int buf = L & 1;
+    CollectArgs ca = collect_args(g, pv.n_local, wp, buf);
+    ca.inv = pl.front;
+    ca.hot_bm = pl.hot_base + g->hot_w0;
+    ca.sum_bm = reinterpret_cast<unsigned long long*>(g->sum_bm);   // over front_global (part init)
+    ca.n64 = pv.front_words_global / 2;
+    hipLaunchKernelGGL(k_collect, dim3(collect_grid(g, wp)), dim3(kCollectThreads), 0, s, L, g->ctr, wp, ca, ca, ~0ull);
+    if (ev) FGI_HIP(g, hipEventRecord(ev[0], s));
+    hipLaunchKernelGGL(k_level<true>, dim3(wp.grid), dim3(kBlock), 0, s, L, wp, expand_args(g, buf), expand_args(g, buf),
+                       pull_args(g, g->n_slots, pl.front), reinterpret_cast<const unsigned long long*>(g->node), g->vis_bm,
+                       out_for(g, buf ^ 1, nullptr), out_for(g, buf ^ 1, nullptr), g->ctr, g->blk_stats, g->done, pl.ra,
+                       ~0ull);
+    if (ev) FGI_HIP(g, hipEventRecord(ev[1], s));
+    return FGI_OK;   // the caller checks the launches with its own that follow
+}
+
 static fgi_status run_part_planned(fgi_graph* g, const PartView& pv, const WaveParams& wp, const PartBuckets& pb,
                                    uint32_t n_roots, fgi_wave_stats* stats, std::chrono::steady_clock::time_point t0) {
     hipStream_t s = g->stream;
     const bool coll = pv.world > 1 || g->opt_part_coll;
     const auto* node = reinterpret_cast<const unsigned long long*>(g->node);
-    const RemoteArgs ra{pv.base, pv.n_local, pv.block, pv.world, pv.ver_all, pv.sent_bm, pv.send_buf, pv.send_cnt};
-    // one rank without collectives: the pull levels probe the invalidated bitmap itself (no copy into
-    // front_global per pull level) when its hot snapshot sits where the partition's would (the same
-    // word count: no detached handles)
-    const bool alias = !coll && g->hot_w0 == g->bm_words;
-    const uint32_t* front = alias ? g->inv_bm : pv.front_global;
-    uint32_t* const hot_base = alias ? g->inv_bm : pv.front_global;
+    const PartLevels pl = part_levels(g, pv, coll);
     if (coll) {
         FGI_HIP(g, hipMemsetAsync(pv.send_cnt, 0, (size_t)pv.world * 8, s));
         FGI_HIP(g, hipMemsetAsync(pb.cur, 0, (size_t)pv.world * 8, s));
@@ -4059,37 +4101,20 @@ static fgi_status run_part_planned(fgi_graph* g, const PartView& pv, const WaveP
     std::vector<uint8_t> plan = g->part_plan;
     const bool timing = g->opt_level_timing != 0;
     FGI_HIP(g, ensure_events(g, 2 * (size_t)kPlanMax + 2));
-    uint64_t syncs = 0, rounds = 0;
+    uint64_t rounds = 0;
     int L = 0;
     std::vector<uint64_t> glob, plan_ft;
-    double pull_ms = 0, expand_ms = 0;
-    uint64_t pull_launches = 0, expand_launches = 0;
-    uint64_t levels = 0, e_trav = 0, f_total = 0, push_edges = 0, push_f = 0, pull_levels = 0;
+    WaveTally t;
     while (true) {
         const int L0 = L;
         for (size_t k = 0; k < plan.size(); ++k, ++L) {
             const bool pull = plan[k] != 0;
             const int buf = L & 1;
-            const int e = 2 * (L - L0);
             if (pull) {
-                FGI_HIP(g, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&g->ctr->lvl[L % kRing].pull), 1, 1, s));
+                FGI_TRY(part_pull_begin(g, pv, pl, L));
                 if (coll) FGI_TRY(part_allgather_front_async(g));
-                else if (!alias)
-                    FGI_HIP(g, hipMemcpyAsync(pv.front_global, g->inv_bm, (size_t)pv.block / 32 * 4, hipMemcpyDeviceToDevice, s));
             }
-            CollectArgs ca = collect_args(g, pv.n_local, wp, buf);
-            ca.inv = front;   // hot heads are global ids
-            ca.hot_bm = hot_base + g->hot_w0;
-            ca.sum_bm = reinterpret_cast<unsigned long long*>(g->sum_bm);   // over front_global (part init)
-            ca.n64 = pv.front_words_global / 2;
-            hipLaunchKernelGGL(k_collect, dim3(collect_grid(g, wp)), dim3(kCollectThreads), 0, s, L, g->ctr, wp, ca, ca,
-                               ~0ull);
-            if (timing) FGI_HIP(g, hipEventRecord(g->ev[e], s));
-            hipLaunchKernelGGL(k_level<true>, dim3(wp.grid), dim3(kBlock), 0, s, L, wp, expand_args(g, buf),
-                               expand_args(g, buf), pull_args(g, g->n_slots, front), node, g->vis_bm,
-                               out_for(g, buf ^ 1, nullptr), out_for(g, buf ^ 1, nullptr), g->ctr, g->blk_stats, g->done,
-                               ra, ~0ull);
-            if (timing) FGI_HIP(g, hipEventRecord(g->ev[e + 1], s));
+            FGI_TRY(launch_part_level(g, pv, pl, wp, L, timing ? &g->ev[2 * (L - L0)] : nullptr));
             if (!pull && coll) {
                 hipLaunchKernelGGL(k_a2a_pack, dim3(pv.world), dim3(kBlock), 0, s, pv.rank, pb.C, pv.send_buf, pv.block,
                                    pv.send_cnt, pb.cur, pb.send);
@@ -4122,33 +4147,14 @@ static fgi_status run_part_planned(fgi_graph* g, const PartView& pv, const WaveP
 #endif
         if (timing) FGI_HIP(g, hipEventSynchronize(g->ev_w1));       // complete already: the level events too
         if (rounds == 0) plan_ft.assign(glob.begin() + 2, glob.end());
-        ++syncs;
+        ++t.syncs;
         ++rounds;
         for (int l = L0; l < L; ++l) {   // the round's levels (a round has at most kPlanMax < kRing)
             const LevelCtr& lc = g->ctr_host->lvl[l % kRing];
-            const uint64_t F = lvl_F(lc), T = lvl_T(lc);
             // a level counts as the host-driven loop counts it: if any rank had a frontier (round 0: the
             // all-reduced F; later rounds, push levels: this rank's); a plan's surplus levels do not
-            const bool ran = rounds == 1 ? plan_ft[2 * (l - L0)] != 0 : F != 0;
-            if (lc.pull && ran) ++pull_levels;
-            if (ran) ++levels;
-            if (F) {
-                e_trav += T;
-                f_total += F;
-                if (!lc.pull) {
-                    push_edges += T;
-                    push_f += F;
-                }
-            }
-            float ms = 0;
-            if (!timing || hipEventElapsedTime(&ms, g->ev[2 * (l - L0)], g->ev[2 * (l - L0) + 1]) != hipSuccess) continue;
-            if (lc.pull) {
-                pull_ms += ms;
-                ++pull_launches;
-            } else {
-                expand_ms += ms;
-                ++expand_launches;
-            }
+            const bool ran = rounds == 1 ? plan_ft[2 * (l - L0)] != 0 : lvl_F(lc) != 0;
+            FGI_TRY(tally_level(g, &t, lc, ran, timing ? &g->ev[2 * (l - L0)] : nullptr));
         }
         if (glob[0] == 0 && glob[1] == 0) break;
         // work left (a longer wave than the plan, or ids waiting in send_buf): push levels; each moves
@@ -4165,9 +4171,7 @@ static fgi_status run_part_planned(fgi_graph* g, const PartView& pv, const WaveP
         for (size_t l = 0; 2 * l + 1 < plan_ft.size() && next.size() < kPlanMax; ++l) {
             const uint64_t F = plan_ft[2 * l], T = plan_ft[2 * l + 1];
             if (F == 0) break;
-            const bool pull = allow_pull && T != 0 &&
-                              (wp.direction == 2 ||
-                               (wp.direction == 0 && (T > wp.pull_threshold || (last_pull && F > wp.stay_pull_f))));
+            const bool pull = beamer_pull(allow_pull, wp.direction, F, T, last_pull, wp);
             next.push_back(pull ? 1 : 0);
             last_pull = pull;
         }
@@ -4177,37 +4181,13 @@ static fgi_status run_part_planned(fgi_graph* g, const PartView& pv, const WaveP
     g->last_wave_n = c.inv;
     g->ids_valid = true;
     if (stats) {
-        uint64_t sent_total = 0;
         if (coll) {
             std::vector<unsigned long long> sc(pv.world, 0);
             FGI_HIP(g, hipMemcpy(sc.data(), pv.send_cnt, (size_t)pv.world * 8, hipMemcpyDeviceToHost));
-            for (uint32_t q = 0; q < pv.world; ++q) sent_total += sc[q];
+            for (uint32_t q = 0; q < pv.world; ++q) t.remote_msgs += sc[q];
+            ++t.syncs;   // the start all-reduce
         }
-        const uint64_t v = c.inv;
-        stats->roots += n_roots;
-        stats->levels += levels;
-        stats->v_inv += v;
-        stats->e_trav += e_trav;
-        stats->e_match += c.e_match;
-        stats->n_flagged += c.n_flagged;
-        stats->remote_msgs += sent_total;
-        const uint64_t pull_b = pull_level_bytes(c);
-        stats->alg_bytes += 20 * push_edges + 40 * push_f + pull_b + 4 * v + 8 * sent_total + 5ull * n_roots;
-        stats->pull_levels += pull_levels;
-        stats->pull_edges += c.pull_edges;
-        stats->pull_ms += pull_ms;
-        stats->pull_bytes += pull_b;
-        stats->pull_launches += pull_launches;
-        float wave_ms = 0;
-        if (part_events(g)) hipEventElapsedTime(&wave_ms, g->ev_w0, g->ev_w1);
-        else wave_ms = wall_ms(g, c.t0, g->last_pub_t);
-        stats->kernel_ms += wave_ms;
-        stats->expand_ms += expand_ms;
-        stats->expand_launches += expand_launches;
-        stats->expand_bytes += 20 * push_edges + 40 * push_f;
-        stats->f_total += f_total;
-        stats->host_syncs += syncs + (coll ? 1 : 0);   // + the start all-reduce
-        stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        fill_wave_stats(stats, c, n_roots, t, wave_span_ms(g, c, part_events(g)), t0);
     }
     return FGI_OK;
 }
@@ -4224,17 +4204,9 @@ fgi_status run_part_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_d
     // one rank: nothing is remote, the collectives are identities (skipped unless FGI_OPT_PART_COLLECTIVES)
     const bool coll = pv.world > 1 || g->opt_part_coll;
     if (coll) FGI_HIP(g, hipMemsetAsync(pv.sent_bm, 0, pv.sent_words * 4, s));
-    g->wave_clean = false;   // this path dirties the wave state (run_wave re-inits)
     if (coll) FGI_TRY(part_front_reset(g));
-    hipLaunchKernelGGL(k_wave_init, dim3(kInitBlocks), dim3(kBlock), 0, s, g->ctr, g->blk_stats, g->inv_bm,
-                       g->vis_stale ? g->vis_bm : nullptr, (uint64_t)g->bm_words);
-    g->vis_stale = false;
-    g->coop_clean = false;
-    while (g->ev.size() < 2) {
-        hipEvent_t e;
-        FGI_HIP(g, hipEventCreateWithFlags(&e, event_flags()));
-        g->ev.push_back(e);
-    }
+    wave_start(g, true, true);
+    FGI_HIP(g, ensure_events(g, 2));
     // the wave's span: stream events with per-level timing, else the device wall clock (spin waits:
     // WaveCtr::t0 from k_wave_init, the end from the last publish)
     if (part_events(g)) FGI_HIP(g, hipEventRecord(g->ev_w0, s));
@@ -4280,60 +4252,33 @@ fgi_status run_part_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_d
     g->part_plan.clear();      // learnt again by this wave's levels
     g->part_plan_key = key;
     g->part_plan_pull = sums[3] == 0;   // every rank's pull lists were ready (the same on all ranks)
-    const uint64_t stay_pull_f = wp.stay_pull_f;
     const bool allow_pull = sums[3] == 0;
-    const int direction = wp.direction;
-    const RemoteArgs ra{pv.base, pv.n_local, pv.block, pv.world, pv.ver_all, pv.sent_bm, pv.send_buf, pv.send_cnt};
-    // the invalidated bitmap over all slots: all-gathered before pull levels (one rank without
-    // collectives: its own words copied in, so the hot snapshot past its end is where the candidates
-    // expect it)
-    // one rank without collectives: the pull levels probe the invalidated bitmap itself (no copy into
-    // front_global per pull level) when its hot snapshot sits where the partition's would (the same
-    // word count: no detached handles)
-    const bool alias = !coll && g->hot_w0 == g->bm_words;
-    const uint32_t* front = alias ? g->inv_bm : pv.front_global;
-    uint32_t* const hot_base = alias ? g->inv_bm : pv.front_global;
+    // the invalidated bitmap over all slots is all-gathered before pull levels (one rank without
+    // collectives: part_pull_begin)
+    const PartLevels pl = part_levels(g, pv, coll);
+    const hipEvent_t* const lev = g->opt_level_timing ? g->ev.data() : nullptr;   // every level's event pair
     uint64_t f_global = sums[1], t_global = sums[2];
     const double avg_deg = (double)sums[0] / std::max<uint64_t>(1, pv.n_global);
-    uint64_t levels = 0, e_trav = 0, f_total = 0, sent_total = 0, push_edges = 0, push_f = 0;
-    uint64_t pull_levels = 0, pull_launches = 0, expand_launches = 0;
-    uint64_t syncs = 1;   // the start's all-reduce
-    double expand_ms = 0, pull_ms = 0;
+    WaveTally t;
+    t.syncs = 1;   // the start's all-reduce
     int L = 0;
     bool last_pull = false;
     for (; f_global != 0; ++L) {
-        const bool pull = allow_pull && t_global != 0 &&
-                          (direction == 2 || (direction == 0 && (t_global > wp.pull_threshold ||
-                                                                 (last_pull && f_global > stay_pull_f))));
+        const bool pull = beamer_pull(allow_pull, wp.direction, f_global, t_global, last_pull, wp);
         if (g->part_plan.size() < kPlanMax) g->part_plan.push_back(pull ? 1 : 0);
         const int buf = L & 1;
         if (coll) FGI_HIP(g, hipMemsetAsync(pv.send_cnt, 0, (size_t)pv.world * 8, s));
-        // the level's direction for its kernels: the flag's high word is zero (the ring slot was
-        // cleared two levels ago or at wave start), so a 32-bit device-side set is the whole store
         if (pull) {
-            FGI_HIP(g, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&g->ctr->lvl[L % kRing].pull), 1, 1, s));
+            FGI_TRY(part_pull_begin(g, pv, pl, L));
             if (coll) {
                 uint64_t f0 = 0, d0 = 0, d1 = 0, b = 0;
                 FGI_TRY(part_front_stats(g, &f0, &d0, &b));
                 FGI_TRY(part_allgather_front(g));
                 FGI_TRY(part_front_stats(g, &f0, &d1, &b));
-                syncs += g->opt_front_exchange != 1 ? 1 : 0;   // the delta count's read-back (auto or delta)
-            } else if (!alias) {
-                FGI_HIP(g, hipMemcpyAsync(pv.front_global, g->inv_bm, (size_t)pv.block / 32 * 4, hipMemcpyDeviceToDevice, s));
+                t.syncs += g->opt_front_exchange != 1 ? 1 : 0;   // the delta count's read-back (auto or delta)
             }
         }
-        CollectArgs ca = collect_args(g, pv.n_local, wp, buf);
-        ca.inv = front;   // hot heads are global ids
-        ca.hot_bm = hot_base + g->hot_w0;
-        ca.sum_bm = reinterpret_cast<unsigned long long*>(g->sum_bm);   // over front_global (part init)
-        ca.n64 = pv.front_words_global / 2;
-        hipLaunchKernelGGL(k_collect, dim3(collect_grid(g, wp)), dim3(kCollectThreads), 0, s, L, g->ctr, wp, ca, ca, ~0ull);
-        if (g->opt_level_timing) FGI_HIP(g, hipEventRecord(g->ev[0], s));
-        hipLaunchKernelGGL(k_level<true>, dim3(wp.grid), dim3(kBlock), 0, s, L, wp, expand_args(g, buf),
-                           expand_args(g, buf), pull_args(g, g->n_slots, front), node, g->vis_bm,
-                           out_for(g, buf ^ 1, nullptr), out_for(g, buf ^ 1, nullptr), g->ctr, g->blk_stats, g->done,
-                           ra, ~0ull);
-        if (g->opt_level_timing) FGI_HIP(g, hipEventRecord(g->ev[1], s));
+        FGI_TRY(launch_part_level(g, pv, pl, wp, L, lev));
         FGI_HIP(g, hipGetLastError());
         uint64_t n_recv = 0, n_sent = 0, glob[3] = {0, 0, 0};
         const bool exch = !pull && coll;
@@ -4349,8 +4294,8 @@ fgi_status run_part_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_d
                                dim3(kBlock), 0, s, L, n_recv, pv.recv_buf, pv.base, node, g->vis_bm,
                                out_for(g, buf ^ 1, nullptr), g->ctr, g->blk_stats, g->done, 0u);
         FGI_HIP(g, hipGetLastError());
-        sent_total += n_sent;
-        ++syncs;   // the level's count all-gather or all-reduce
+        t.remote_msgs += n_sent;
+        ++t.syncs;   // the level's count all-gather or all-reduce
         // every winner remote (the wave's tail): whether the received targets add any is known only
         // after they are applied, so the exact all-reduce decides termination (no empty level)
         if (exch && (glob[0] != 0 || glob[2] == 0)) {
@@ -4366,58 +4311,20 @@ fgi_status run_part_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_d
             f_global = ft[0];
             t_global = ft[1];
         }
-        const LevelCtr& lc = g->ctr_host->lvl[L % kRing];
-        ++levels;
-        e_trav += lc.T;
-        f_total += lc.F;
-        float ms = 0;
-        if (g->opt_level_timing) FGI_HIP(g, hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
-        if (pull) {
-            ++pull_levels;
-            ++pull_launches;
-            pull_ms += ms;
-        } else {
-            push_edges += lc.T;
-            push_f += lc.F;
-            ++expand_launches;
-            expand_ms += ms;
-        }
+        // every level of the loop counts (some rank had a frontier), whether this rank had one or not
+        FGI_TRY(tally_level(g, &t, g->ctr_host->lvl[L % kRing], true, lev));
+        // this driver counts its launches without level timing too (the others count timed launches only)
+        if (!lev) ++(pull ? t.pull_launches : t.expand_launches);
         last_pull = pull;
     }
     FGI_HIP(g, launch_final(g, pv.n_local));
     FGI_HIP(g, hipGetLastError());
     FGI_TRY(counters_to_host(g, s, part_events(g)));
-    g->last_wave_n = g->ctr_host->inv;
+    ++t.syncs;   // the final collect's
+    const WaveCtr& c = *g->ctr_host;
+    g->last_wave_n = c.inv;
     g->ids_valid = true;
-    if (stats) {
-        const WaveCtr& c = *g->ctr_host;
-        const uint64_t v = c.inv;
-        stats->roots += n_roots;
-        stats->levels += levels;
-        stats->v_inv += v;
-        stats->e_trav += e_trav;
-        stats->e_match += c.e_match;
-        stats->n_flagged += c.n_flagged;
-        stats->remote_msgs += sent_total;
-        stats->host_syncs += syncs + 1;   // + the final collect's
-        // as run_wave, plus 8 B per forwarded target (written + received)
-        const uint64_t pull_b = pull_level_bytes(c);
-        stats->alg_bytes += 20 * push_edges + 40 * push_f + pull_b + 4 * v + 8 * sent_total + 5ull * n_roots;
-        stats->pull_levels += pull_levels;
-        stats->pull_edges += c.pull_edges;
-        stats->pull_ms += pull_ms;
-        stats->pull_bytes += pull_b;
-        stats->pull_launches += pull_launches;
-        float wave_ms = 0;
-        if (part_events(g)) hipEventElapsedTime(&wave_ms, g->ev_w0, g->ev_w1);
-        else wave_ms = wall_ms(g, c.t0, g->last_pub_t);
-        stats->kernel_ms += wave_ms;
-        stats->expand_ms += expand_ms;
-        stats->expand_launches += expand_launches;
-        stats->expand_bytes += 20 * push_edges + 40 * push_f;
-        stats->f_total += f_total;
-        stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
+    if (stats) fill_wave_stats(stats, c, n_roots, t, wave_span_ms(g, c, part_events(g)), t0);
     return FGI_OK;
 }
 
