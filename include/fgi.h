@@ -257,6 +257,29 @@ fgi_status fgi_wave_ids_dev(fgi_graph* g, const uint32_t** ids_dev, uint64_t* n)
 /* Host copy of the last wave's invalidated handles — e.g. the displacement cascade of
  * fgi_begin_compute, whose Invalidated handlers the host must still run. */
 fgi_status fgi_last_wave_ids(fgi_graph* g, uint32_t* out_ids, uint64_t cap, uint64_t* out_n);
+/* The two branches of Computed.Invalidate() that do not invalidate (Computed.cs:173-178: a Computing node
+ * only gets InvalidateOnSetOutput, and InvalidationDelayStarted from an `immediately` root; Computed.cs:186-197:
+ * a Consistent node with an InvalidationDelay only gets InvalidationDelayStarted and schedules its own
+ * timer, ComputedExt.Invalidate(TimeSpan), ComputedExt.cs:10-37, which later calls Invalidate(true)).
+ * The flagged set of a call: every handle whose canonical state_flags gained
+ * FGI_F_INVALIDATE_ON_SET_OUTPUT and / or FGI_F_INVALIDATION_DELAY_STARTED during the call and that the call
+ * did not invalidate — the difference of two state dumps, whatever the order of the visits
+ * (fgi_wave_stats.n_flagged stays a visit count). The host starts its timers from it.
+ * fgi_last_wave_flagged: the flagged set of the last cascade of the last call (fgi_invalidate, _dev, _bits,
+ * fgi_invalidate_all, fgi_begin_compute's displacement cascade, fgi_set_output's cascade; empty if the call
+ * ran no cascade): boundary handles (detached ones included), ascending; out_flags[i] (nullable) = the
+ * node's canonical state_flags after the call. A slot fgi_begin_compute displaced is not listed (its
+ * handle names the new node when the call returns; the displaced node is out_detached[i]). FGI_ECAPACITY
+ * with *out_n set if cap is short; out_ids NULL = count only. Valid until the next call that runs a wave.
+ * After fgi_run_batch or any fgi_part_* call: FGI_ENOTSUP (their cascades report no flagged sets).
+ * A graph that never held a Computing node or one with hasDelay reports empty sets at no cost: its waves
+ * launch nothing for them. */
+fgi_status fgi_last_wave_flagged(fgi_graph* g, uint32_t* out_ids, uint32_t* out_flags, uint64_t cap, uint64_t* out_n);
+/* The same for an asynchronous ticket (waits like fgi_wave_wait; same validity window as the ticket's ids:
+ * until the wave two tickets later is queued or a synchronous wave runs); out_flags[i] = the node's
+ * canonical state_flags after the ticket's wave. */
+fgi_status fgi_wave_wait_flagged(fgi_graph* g, uint64_t ticket, uint32_t* out_ids, uint32_t* out_flags,
+                                 uint64_t cap, uint64_t* out_n);
 /* ComputedRegistry.InvalidateEverything (ComputedRegistry.cs:142-147). */
 fgi_status fgi_invalidate_all(fgi_graph* g, uint32_t* out_ids, uint64_t cap, uint64_t* out_n,
                               fgi_wave_stats* stats);

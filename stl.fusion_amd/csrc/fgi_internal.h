@@ -407,6 +407,7 @@ struct fgi_graph {
         uint64_t n_inv = 0;            // V_inv, once waited for
         uint32_t n_roots = 0;
         bool busy = false, imm = false, timing = false;
+        bool flg = false;              // the wave queued the flagged-set post-pass (flag_gate was on)
         int group = 0;
         std::chrono::steady_clock::time_point t0;
     };
@@ -450,6 +451,22 @@ struct fgi_graph {
     uint32_t* cls_bm = nullptr;
     bool cls_valid = false;
     bool words_dirty = true;           // node words changed since the snapshot
+    // Flagged sets (fgi_last_wave_flagged / fgi_wave_wait_flagged). flag_gate: the graph may
+    // hold a Computing node or one with hasDelay, the only nodes a visit can flag without invalidating
+    // (set by fgi_register_nodes / fgi_begin_compute / a batch's begin_compute steps, restored with the
+    // snapshot). While it is off no wave launches anything for the flagged set and every set is empty.
+    // flg_bm is the flaggable-class bitmap beside cls_bm: bit h set = a non-immediate first visit of h
+    // would only set a flag (first_visit == 2 on h's canonical word, its visit bit folded in). A wave's
+    // flagged set is vis_bm & flg_bm & ~inv_bm; the post-pass (k_flag_list) lists it and clears the bits
+    // it found, so a node is reported once although vis_bm keeps its bit until the next fold.
+    bool flag_gate = false, snap_flag_gate = false;
+    uint32_t* flg_bm = nullptr;        // [bm_words], allocated when the gate first opens
+    bool flg_valid = false;            // flg_bm matches the node words and visit bits (cleared with cls_valid)
+    unsigned long long* flg_out[2] = {nullptr, nullptr};   // [n_handles] per ticket parity (synchronous waves: 0):
+                                       // boundary handle << 32 | canonical state_flags, unordered
+    unsigned long long* flg_cnt = nullptr;   // [2] entries in flg_out[k]
+    int flg_last = -1;                 // the last call's set: -1 empty, 0 / 1 flg_out[k], -2 not reported (batch)
+    std::vector<uint32_t> flg_drop;    // boundary slots the last call replaced (fgi_begin_compute): not in its set
     // Invalidated bitmap: bit h set = node h was invalidated by this wave. It is the frontier of a
     // pull level: every node invalidated before the previous level already had all its dependants
     // visited, so "an invalidated parent" and "a parent in the previous level's frontier" select
@@ -669,6 +686,7 @@ inline void touch(fgi_graph* g) { g->mut_epoch = ++g->epoch_counter; }
 // Record a change of node words (class bitmap rebuilt before the next wave; restore copies words).
 inline void note_words(fgi_graph* g) {
     g->cls_valid = false;
+    g->flg_valid = false;
     g->words_dirty = true;
     g->nodes_written = true;
 }
@@ -698,8 +716,12 @@ fgi_status wave_wait(fgi_graph* g, uint64_t ticket, uint64_t* out_n, const uint3
 // the same wave from roots in host memory: staged through the ticket parity's pinned buffer
 fgi_status run_wave_async_host(fgi_graph* g, uint32_t n_roots, const uint32_t* roots, const uint8_t* imm, uint64_t* ticket);
 fgi_status drain_async(fgi_graph* g);
-// Rebuild the expandable-class bitmap if node words changed (wave.hip).
+// Rebuild the expandable-class bitmap if node words changed (wave.hip); with flag_gate, the flaggable one too.
 fgi_status ensure_cls(fgi_graph* g);
+// The flagged set of ticket parity k's last wave (k < 0: empty), sorted by handle, without `drop` (sorted
+// boundary slots): packed handle << 32 | state_flags. Waits for the graph's stream unless `blocking_copy`
+// (an asynchronous ticket already waited for: a copy on the null stream lets later waves run on).
+fgi_status read_flagged(fgi_graph* g, int k, bool blocking_copy, std::vector<uint64_t>* out);
 // Pull tiles of a level over n slots with `grid` blocks.
 __host__ __device__ inline uint64_t pull_iters(uint64_t n, uint32_t grid) { return (n + (uint64_t)grid * kPullTile - 1) / ((uint64_t)grid * kPullTile); }
 // ---- multi-GPU partition (part.hip) ----

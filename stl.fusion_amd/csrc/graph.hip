@@ -1835,7 +1835,7 @@ extern "C" {
 
 fgi_status fgi_version(uint32_t* major, uint32_t* minor) {
     if (major) *major = 0;
-    if (minor) *minor = 1;
+    if (minor) *minor = 2;   // 0.2: fgi_last_wave_flagged, fgi_wave_wait_flagged
     return FGI_OK;
 }
 
@@ -1964,6 +1964,10 @@ fgi_status fgi_destroy(fgi_graph* g) {
     }
     dfree(g->vis_bm);
     dfree(g->vis_spare);
+    if (g->flg_bm) (void)hipFree(g->flg_bm);
+    if (g->flg_cnt) (void)hipFree(g->flg_cnt);
+    for (int k = 0; k < 2; ++k)
+        if (g->flg_out[k]) (void)hipFree(g->flg_out[k]);
     dfree(g->cls_bm);
     dfree(g->uin_more);
     dfree(g->sum_bm);
@@ -2022,6 +2026,10 @@ fgi_status fgi_register_nodes(fgi_graph* g, uint32_t n, const uint32_t* slot, co
         if (state_flags && (state_flags[i] & 3u) == 3u) return set_err(g, FGI_EINVAL, "bad state for slot %u", slot[i]);
     }
     if (n == 0) return FGI_OK;
+    // a Computing node, or one with an invalidation delay, can be flagged by a visit (flagged sets)
+    for (uint32_t i = 0; i < n && state_flags && !g->flag_gate; ++i)
+        if (version[i] && ((state_flags[i] & FGI_STATE_MASK) == FGI_COMPUTING || (state_flags[i] & FGI_F_HAS_DELAY)))
+            g->flag_gate = true;
     hipSetDevice(g->device);
     Tmp ts, tv, tf;
     uint32_t *ds, *df = nullptr;
@@ -2311,6 +2319,7 @@ fgi_status fgi_snapshot(fgi_graph* g) {
     FGI_HIP(g, hipStreamSynchronize(s));
     g->snap_epoch = g->pool_epoch;
     g->snap_mut_epoch = g->mut_epoch;
+    g->snap_flag_gate = g->flag_gate;
     g->words_dirty = false;
     return FGI_OK;
 }
@@ -2342,6 +2351,7 @@ fgi_status fgi_restore(fgi_graph* g) {
         g->wave_clean = false;
         g->words_dirty = false;
         g->cls_valid = false;
+        g->flg_valid = false;
         g->v_dirty = false;
         g->vis_stale = false;
         g->coop_clean = false;   // the next cascade re-initialises the wave counters
@@ -2353,6 +2363,12 @@ fgi_status fgi_restore(fgi_graph* g) {
         g->words_dirty = false;
         g->cls_valid = false;
     }
+    // the flaggable bitmap follows the words and the visit bits, and the visit bits go: rebuilt by the next
+    // wave (only graphs that can flag have one); the gate is the snapshot's again
+    g->flg_valid = false;
+    g->flag_gate = g->snap_flag_gate;
+    g->flg_last = -1;
+    g->flg_drop.clear();
     // the visit bits are forgotten: the clean spare bitmap takes the visit bitmap's place, and the next
     // wave's list kernel clears the old one; without a clean spare, the next wave's init kernel clears it
     // (or flush_vis before any other use)
@@ -2613,6 +2629,53 @@ fgi_status fgi_last_wave_ids(fgi_graph* g, uint32_t* out_ids, uint64_t cap, uint
     return copy_ids(g, out_ids, cap, out_n);
 }
 
+// a sorted flagged set (handle << 32 | state_flags) into the caller's arrays
+static fgi_status copy_flagged(fgi_graph* g, const std::vector<uint64_t>& set, const std::vector<uint32_t>& drop,
+                               uint32_t* out_ids, uint32_t* out_flags, uint64_t cap, uint64_t* out_n) {
+    uint64_t n = 0;
+    for (const uint64_t e : set) n += std::binary_search(drop.begin(), drop.end(), (uint32_t)(e >> 32)) ? 0 : 1;
+    if (out_n) *out_n = n;
+    if (!out_ids) return FGI_OK;
+    if (n > cap) return set_err(g, FGI_ECAPACITY, "the flagged set holds %llu handles, the buffer %llu",
+                                (unsigned long long)n, (unsigned long long)cap);
+    uint64_t k = 0;
+    for (const uint64_t e : set) {
+        if (std::binary_search(drop.begin(), drop.end(), (uint32_t)(e >> 32))) continue;
+        out_ids[k] = (uint32_t)(e >> 32);
+        if (out_flags) out_flags[k] = (uint32_t)e;
+        ++k;
+    }
+    return FGI_OK;
+}
+
+fgi_status fgi_last_wave_flagged(fgi_graph* g, uint32_t* out_ids, uint32_t* out_flags, uint64_t cap, uint64_t* out_n) {
+    if (!g) return FGI_EINVAL;
+    FGI_TRY(usable(g));
+    if (g->part || g->flg_last == -2)
+        return set_err(g, FGI_ENOTSUP, "fgi_last_wave_flagged: the cascades of fgi_run_batch and of the fgi_part_* calls "
+                                       "report no flagged sets");
+    hipSetDevice(g->device);
+    std::vector<uint64_t> set;
+    FGI_TRY(read_flagged(g, g->flg_last, false, &set));
+    return copy_flagged(g, set, g->flg_drop, out_ids, out_flags, cap, out_n);
+}
+
+fgi_status fgi_wave_wait_flagged(fgi_graph* g, uint64_t ticket, uint32_t* out_ids, uint32_t* out_flags, uint64_t cap,
+                                 uint64_t* out_n) {
+    if (!g) return FGI_EINVAL;
+    FGI_TRY(usable_now(g));
+    if (g->part || g->flg_last == -2)
+        return set_err(g, FGI_ENOTSUP, "fgi_wave_wait_flagged: the cascades of fgi_run_batch and of the fgi_part_* calls "
+                                       "report no flagged sets");
+    hipSetDevice(g->device);
+    FGI_TRY(wave_wait(g, ticket, nullptr, nullptr, nullptr));
+    // the ticket's buffer is its own until the wave two tickets later is queued (as its ids); a blocking
+    // copy on the null stream, so a wave queued after the ticket's keeps running (fgi_wave_wait_ids)
+    std::vector<uint64_t> set;
+    FGI_TRY(read_flagged(g, g->aw[ticket & 1].flg ? (int)(ticket & 1) : -1, true, &set));
+    return copy_flagged(g, set, std::vector<uint32_t>{}, out_ids, out_flags, cap, out_n);
+}
+
 fgi_status fgi_invalidate_all(fgi_graph* g, uint32_t* out_ids, uint64_t cap, uint64_t* out_n, fgi_wave_stats* stats) {
     if (!g) return FGI_EINVAL;
     FGI_TRY(single_only(g, "fgi_invalidate_all"));
@@ -2651,6 +2714,9 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
         if (why) return set_err(g, FGI_EINVAL, "%s (%u)", why, bad);
     }
     FGI_TRY(single_only(g, "fgi_begin_compute"));
+    g->flag_gate = true;   // Computing nodes from here on (flagged sets)
+    g->flg_last = -1;
+    g->flg_drop.clear();
     hipSetDevice(g->device);
     hipStream_t st = g->stream;
     Tmp ts, tv, td, tc, tr, tf, to;
@@ -2681,6 +2747,10 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
     // displacement cascade first (ComputedRegistry.cs:91-94), then detach + install
     g->last_wave_n = 0;
     if (cnt[0]) FGI_TRY(run_wave(g, (uint32_t)cnt[0], droots, nullptr, stats));
+    // the call's slots hold new nodes when it returns: a displaced node the cascade flagged is not in the
+    // call's flagged set under its slot (it lives on as out_detached[i])
+    g->flg_drop.assign(slot, slot + n);
+    std::sort(g->flg_drop.begin(), g->flg_drop.end());
     std::vector<uint32_t> take(g->free_detached.end() - (ptrdiff_t)cnt[1], g->free_detached.end());
     FGI_TRY(tmalloc(g, tf, &dfree_h, take.size() + 1));
     FGI_TRY(h2d(g, dfree_h, take.data(), take.size()));
@@ -2770,6 +2840,8 @@ fgi_status fgi_set_output(fgi_graph* g, uint32_t n, const uint32_t* handle, uint
     if (out_n) *out_n = 0;
     if (n == 0) return FGI_OK;
     FGI_TRY(single_only(g, "fgi_set_output"));
+    g->flg_last = -1;
+    g->flg_drop.clear();
     hipSetDevice(g->device);
     hipStream_t st = g->stream;
     Tmp th, ts, tr;
@@ -2939,6 +3011,9 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
         }
     }
     FGI_TRY(single_only(g, "fgi_run_batch"));
+    g->flg_last = -2;   // a batch's cascades report no flagged sets
+    g->flg_drop.clear();
+    if (n_begin) g->flag_gate = true;
     const auto t_check = std::chrono::steady_clock::now();
     hipSetDevice(g->device);
     hipStream_t st = g->stream;

@@ -589,7 +589,8 @@ __device__ __forceinline__ uint32_t root_label(const RootMap& m, uint32_t x) {
 template <int IMM>
 __device__ __forceinline__ void root_step(uint32_t i, const uint32_t* __restrict__ roots, const uint8_t* __restrict__ imm,
                                           uint32_t n, uint32_t base, uint32_t n_range, unsigned long long* node,
-                                          uint32_t* vis, const Out& o, WaveCtr* ctr, const RootMap& rm = RootMap{}) {
+                                          uint32_t* vis, const Out& o, WaveCtr* ctr, const RootMap& rm = RootMap{},
+                                          uint32_t* flg = nullptr) {
     uint32_t win = 0, flagged = 0, h = 0;
     if (i < n) {
         h = rm.on ? root_label(rm, roots[i]) : roots[i] - base;
@@ -612,6 +613,14 @@ __device__ __forceinline__ void root_step(uint32_t i, const uint32_t* __restrict
                         w = prev;
                     }
                     if (r == 1) atomicOr(vis + (h >> 5), 1u << (h & 31));
+                    // a flag-only immediate root (a Computing node gained InvalidateOnSetOutput and / or
+                    // DelayStarted, Computed.cs:173-178) joins the wave's flagged set: its visit and flaggable
+                    // bits are set for the post-pass (k_flag_list), which clears the latter. The visit bit
+                    // changes nothing else: the word already holds what a visit would set.
+                    if (r == 2 && flg) {
+                        atomicOr(vis + (h >> 5), 1u << (h & 31));
+                        atomicOr(flg + (h >> 5), 1u << (h & 31));
+                    }
                 } else {
                     r = visit_bit(vis, h, w);
                 }
@@ -634,9 +643,9 @@ template <int IMM>
 __global__ __launch_bounds__(kBlock) void k_roots(const uint32_t* __restrict__ roots, const uint8_t* __restrict__ imm,
                                                   uint32_t n, uint32_t base, uint32_t n_range, unsigned long long* node,
                                                   uint32_t* vis, Out o, WaveCtr* ctr, unsigned long long* done,
-                                                  int publish, RootMap rm, int stamp) {
+                                                  int publish, RootMap rm, int stamp, uint32_t* flg) {
     if (stamp && blockIdx.x == 0 && threadIdx.x == 0) ctr->t0 = wall_clock64();
-    root_step<IMM>(blockIdx.x * blockDim.x + threadIdx.x, roots, imm, n, base, n_range, node, vis, o, ctr, rm);
+    root_step<IMM>(blockIdx.x * blockDim.x + threadIdx.x, roots, imm, n, base, n_range, node, vis, o, ctr, rm, flg);
     if (publish) publish_ft(o.ln, done, gridDim.x);
 }
 
@@ -2651,6 +2660,89 @@ __global__ __launch_bounds__(kBlock) void k_build_cls(uint32_t n, const unsigned
     }
 }
 
+// k_build_cls with the flaggable class beside it (flag_gate): bit h of flg64 set = a non-immediate first
+// visit of h would only set a flag. vis (nullable: known clear) holds visits not yet folded into the
+// words: a visited node's canonical word is visited_word(w), which no second visit changes.
+__global__ __launch_bounds__(kBlock) void k_build_cls_flg(uint32_t n, const unsigned long long* __restrict__ node,
+                                                          const uint32_t* __restrict__ vis, unsigned long long* cls64,
+                                                          unsigned long long* flg64) {
+    const uint64_t nthr = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t lim = ((uint64_t)n + 63) / 64 * 64;
+    for (uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; h < lim; h += nthr) {
+        bool c = false, f = false;
+        if (h < n) {
+            const unsigned long long w = node[h];
+            c = (w & kVMask) != 0 && word_state(w) == FGI_CONSISTENT && !(w & kW_HasDelay);
+            f = (w & kVMask) != 0 && first_visit(w) == 2 && !(vis && bit_of(vis, (uint32_t)h));
+        }
+        const unsigned long long m = __ballot(c), mf = __ballot(f);
+        if (lane_id() == 0) {
+            cls64[h >> 6] = m;
+            flg64[h >> 6] = mf;
+        }
+    }
+}
+
+// ---- the flagged set of a wave (fgi_last_wave_flagged) ------------------------------
+// Runs stream-ordered after a wave's final collect, only on graphs that can flag (flag_gate). The set is
+// vis & flaggable & ~inv over labels: visited by a wave since the last fold, still flaggable (so not
+// reported by an earlier wave) and not invalidated by this wave's immediate roots. Every hit's flaggable
+// bit is cleared, invalidated or not. Three coalesced bitmap streams; a wave takes 64 words, one per
+// lane, then lists the words that have hits one at a time, a lane per handle: a ballot and mbcnt rank the
+// hits, so the node words (for the reported flags) and the output are touched in runs. One atomic per
+// wave and 64 words reserves the output space; the list is unordered (the host sorts what it reads).
+struct FlagArgs {
+    unsigned long long* flg64;
+    const unsigned long long* vis64;
+    const unsigned long long* inv64;
+    uint64_t words;                    // 64-bit words of the bitmaps
+    const unsigned long long* node;
+    const uint32_t* l2s;               // hot label -> slot (labels below K)
+    uint32_t K;
+    unsigned long long* out;           // handle << 32 | canonical state_flags
+    unsigned long long* cnt;
+    uint64_t cap;                      // entries of out (n_handles: the set cannot hold more)
+};
+
+__global__ __launch_bounds__(kBlock) void k_flag_list(FlagArgs a) {
+    const uint32_t lane = lane_id();
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t w0 = wave * 64; w0 < a.words; w0 += nwaves * 64) {   // wave-uniform
+        const uint64_t x = w0 + lane;
+        unsigned long long e = 0;
+        if (x < a.words) {
+            const unsigned long long f = a.flg64[x];
+            const unsigned long long hit = f ? (f & a.vis64[x]) : 0ull;
+            if (hit) {
+                e = hit & ~a.inv64[x];
+                a.flg64[x] = f & ~hit;
+            }
+        }
+        uint32_t total = (uint32_t)__popcll(e);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) total += __shfl_xor(total, d, 64);
+        if (!total) continue;
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(a.cnt, (unsigned long long)total);
+        base = __shfl(base, 0, 64);
+        for (unsigned long long todo = __ballot(e != 0); todo; todo &= todo - 1) {   // wave-uniform
+            const int src = __ffsll((long long)todo) - 1;
+            const unsigned long long ew = __shfl(e, src, 64);
+            const bool p = (ew >> lane) & 1ull;
+            const unsigned long long b = __ballot(p);
+            if (p) {
+                const uint32_t l = (uint32_t)((w0 + (uint64_t)src) * 64 + lane);
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+                const unsigned long long o = base + rank;
+                const uint32_t id = l < a.K ? a.l2s[l] : l - a.K;
+                if (o < a.cap) a.out[o] = ((unsigned long long)id << 32) | word_to_flags(visited_word(a.node[l]));
+            }
+            base += (unsigned long long)__popcll(b);
+        }
+    }
+}
+
 }  // namespace
 
 fgi_status flush_vis(fgi_graph* g) {
@@ -2674,8 +2766,23 @@ fgi_status fold(fgi_graph* g) {
 }
 
 fgi_status ensure_cls(fgi_graph* g) {
-    if (g->cls_valid) return FGI_OK;
+    if (g->cls_valid && (!g->flag_gate || g->flg_valid)) return FGI_OK;
     const uint32_t H = g->n_handles;
+    if (g->flag_gate) {
+        if (!g->flg_bm) {
+            FGI_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->flg_bm), g->bm_words * 4));
+            FGI_HIP(g, hipMemsetAsync(g->flg_bm, 0, g->bm_words * 4, g->stream));
+        }
+        // the visit bitmap counts only while it holds this graph's visits (not after fgi_restore left its
+        // clearing to the next wave's init kernel, which runs after this)
+        hipLaunchKernelGGL(k_build_cls_flg, dim3(std::min<uint32_t>((H + kBlock - 1) / kBlock + 1, 8192)), dim3(kBlock), 0,
+                           g->stream, H, reinterpret_cast<const unsigned long long*>(g->node),
+                           g->v_dirty && !g->vis_stale ? (const uint32_t*)g->vis_bm : (const uint32_t*)nullptr,
+                           reinterpret_cast<unsigned long long*>(g->cls_bm), reinterpret_cast<unsigned long long*>(g->flg_bm));
+        FGI_HIP(g, hipGetLastError());
+        g->cls_valid = g->flg_valid = true;
+        return FGI_OK;
+    }
     hipLaunchKernelGGL(k_build_cls, dim3(std::min<uint32_t>((H + kBlock - 1) / kBlock + 1, 8192)), dim3(kBlock), 0,
                        g->stream, H, reinterpret_cast<const unsigned long long*>(g->node),
                        reinterpret_cast<unsigned long long*>(g->cls_bm));
@@ -2914,9 +3021,10 @@ void launch_roots(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, con
     // the immediate roots' launch never publishes: the second launch adds to the same counter
     if (imm_dev)
         hipLaunchKernelGGL(k_roots<1>, dim3(nb), dim3(kRootBlock), 0, g->stream, roots_dev, imm_dev, n_roots, base, n_range,
-                           node, g->vis_bm, o, g->ctr, g->done, 0, rm, stamp);
+                           node, g->vis_bm, o, g->ctr, g->done, 0, rm, stamp,
+                           g->flag_gate && g->flg_valid ? g->flg_bm : nullptr);
     hipLaunchKernelGGL(k_roots<0>, dim3(nb), dim3(kRootBlock), 0, g->stream, roots_dev, imm_dev, n_roots, base, n_range, node,
-                       g->vis_bm, o, g->ctr, g->done, publish, rm, imm_dev ? 0 : stamp);
+                       g->vis_bm, o, g->ctr, g->done, publish, rm, imm_dev ? 0 : stamp, (uint32_t*)nullptr);
 }
 
 // ---- what the wave drivers share --------------------------------------------------------------------
@@ -3628,9 +3736,61 @@ static void wave_finished(fgi_graph* g, const WaveCtr& c, bool ids_valid, uint32
     else g->last_dirs.clear();
 }
 
+// Queues the flagged-set post-pass behind the wave just queued (flag_gate), into ticket parity k's buffer
+// (synchronous waves: 0). The wave's invalidated bitmap must still be intact: such waves do not leave the
+// state clean (no WaveEnd).
+static fgi_status launch_flagged(fgi_graph* g, int k) {
+    hipStream_t s = g->stream;
+    if (!g->flg_cnt) FGI_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->flg_cnt), 2 * sizeof(unsigned long long)));
+    if (!g->flg_out[k])
+        FGI_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->flg_out[k]), (size_t)g->n_handles * sizeof(unsigned long long)));
+    FGI_HIP(g, hipMemsetAsync(g->flg_cnt + k, 0, sizeof(unsigned long long), s));
+    const uint64_t words = ((uint64_t)g->n_handles + 63) / 64;
+    const FlagArgs a{reinterpret_cast<unsigned long long*>(g->flg_bm),
+                     reinterpret_cast<const unsigned long long*>(g->vis_bm),
+                     reinterpret_cast<const unsigned long long*>(g->inv_bm),
+                     words,
+                     reinterpret_cast<const unsigned long long*>(g->node),
+                     g->l2s,
+                     g->lbl_K,
+                     g->flg_out[k],
+                     g->flg_cnt + k,
+                     (uint64_t)g->n_handles};
+    // a block's four waves take 64 words each
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, (words + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(k_flag_list, dim3(grid), dim3(kBlock), 0, s, a);
+    FGI_HIP(g, hipGetLastError());
+    return FGI_OK;
+}
+
+fgi_status read_flagged(fgi_graph* g, int k, bool blocking_copy, std::vector<uint64_t>* out) {
+    out->clear();
+    if (k < 0 || !g->flg_cnt || !g->flg_out[k]) return FGI_OK;
+    unsigned long long n = 0;
+    if (blocking_copy) {
+        FGI_HIP(g, hipMemcpy(&n, g->flg_cnt + k, sizeof(n), hipMemcpyDeviceToHost));
+    } else {
+        FGI_HIP(g, hipMemcpyAsync(&n, g->flg_cnt + k, sizeof(n), hipMemcpyDeviceToHost, g->stream));
+        FGI_HIP(g, hipStreamSynchronize(g->stream));
+    }
+    n = std::min<unsigned long long>(n, g->n_handles);
+    if (!n) return FGI_OK;
+    out->resize(n);
+    if (blocking_copy) {
+        FGI_HIP(g, hipMemcpy(out->data(), g->flg_out[k], (size_t)n * 8, hipMemcpyDeviceToHost));
+    } else {
+        FGI_HIP(g, hipMemcpyAsync(out->data(), g->flg_out[k], (size_t)n * 8, hipMemcpyDeviceToHost, g->stream));
+        FGI_HIP(g, hipStreamSynchronize(g->stream));
+    }
+    std::sort(out->begin(), out->end());   // by handle: the high half
+    return FGI_OK;
+}
+
 fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, const uint8_t* imm_dev,
                     fgi_wave_stats* stats, bool ext_roots) {
     const auto t0 = std::chrono::steady_clock::now();
+    g->flg_last = -1;
+    g->flg_drop.clear();
     forget_async_results(g, g->inv);   // the list goes to g->inv (now, or on demand: ensure_ids)
     hipStream_t s = g->stream;
     static const bool trace = getenv("FGI_TRACE") != nullptr;
@@ -3650,7 +3810,7 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
     // fused launches when the wave's directions are settled (lists ready, or push only); a wave that
     // may still have to build the dependency lists part-way runs as level groups below
 #if FGI_VARIANTS
-    if ((g->opt_fused & kFusedOn) && !g->lbl_K && (allow_pull || wp0.direction == 1)) {   // labels: level groups
+    if ((g->opt_fused & kFusedOn) && !g->lbl_K && !g->flag_gate && (allow_pull || wp0.direction == 1)) {   // labels, flagged sets: level groups
         WaveParams wp = wp0;
         if (!allow_pull) wp.direction = 1;
         const fgi_status r = run_wave_fused(g, n_roots, roots_dev, imm_dev, stats, wp, timing, t0);
@@ -3678,7 +3838,8 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
     // only when the list kernel runs (ids wanted, not the measurement-only merged publish)
     static const bool list_pub = getenv("FGI_LIST_PUBLISH") && getenv("FGI_LIST_PUBLISH")[0] == '1';
     const bool merged = FGI_SPIN_WAIT && g->want_ids && list_pub;
-    const bool leave_clean = g->want_ids && !merged && FGI_SPIN_WAIT;
+    // (a graph that can flag keeps the invalidated bitmap for the flagged-set post-pass: launch_flagged)
+    const bool leave_clean = g->want_ids && !merged && FGI_SPIN_WAIT && !g->flag_gate;
     // Levels run in groups between host synchronisations (one ~30 us round trip each); the first
     // group is sized by the previous wave's depth, so a repeated workload syncs once per wave and an
     // overshoot costs only empty levels (two ~2 us launches each). Every group ends with the final
@@ -3799,6 +3960,10 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
         t.level_edges = c.push_edges - c.mid_push_edges;
         t.level_f = c.push_f - c.mid_push_f;
     }
+    if (g->flag_gate && final_done) {
+        FGI_TRY(launch_flagged(g, 0));
+        g->flg_last = 0;
+    }
     if (imm_dev && n_roots) note_words(g);   // immediate roots changed node words
     // the last group's list kernel and publish saw the wave over (the host's loop ends on the same test)
     g->wave_clean = leave_clean && final_done;
@@ -3830,6 +3995,8 @@ fgi_status run_wave_async(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_
     const uint64_t t = g->next_ticket;
     fgi_graph::AsyncWave& a = g->aw[t & 1];
     if (a.busy) FGI_TRY(wave_wait(g, a.ticket, nullptr, nullptr, nullptr));   // at most two in flight
+    g->flg_last = -1;
+    g->flg_drop.clear();
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t s = g->stream;
     if (!g->apub[0]) {
@@ -3865,20 +4032,28 @@ fgi_status run_wave_async(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_
     uint32_t* out = (t & 1) ? g->inv_alt : g->inv;
     // the queue runs every level (the tail's `all`), so the wave is over after it: its list kernel and
     // publish leave the state clean for the next wave (WaveEnd)
-    const WaveEnd we{g->ctr, group, 1, g->blk_stats, g->inv_bm, ((uint64_t)g->n_handles + 63) / 64,
+    // (not on a graph that can flag: the flagged-set post-pass reads the invalidated bitmap after the list)
+    WaveEnd we{};
+    if (!g->flag_gate) {
+        we = WaveEnd{g->ctr, group, 1, g->blk_stats, g->inv_bm, ((uint64_t)g->n_handles + 63) / 64,
                      g->spare_dirty ? g->vis_spare : nullptr};
-    g->spare_dirty = false;
+        g->spare_dirty = false;
+    }
     FGI_HIP(g, launch_final(g, g->n_handles, true, out, ListPub{}, we));
+    const bool flg = g->flag_gate && n_roots != 0;
+    if (flg) FGI_TRY(launch_flagged(g, (int)(t & 1)));
     const unsigned long long seq = ++g->apub_seq;
     hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, s, reinterpret_cast<const unsigned long long*>(g->ctr),
                        (uint32_t)kPubWords, g->apub[t & 1], seq, we);
     FGI_HIP(g, hipGetLastError());
-    g->wave_clean = true;   // once the queue has run (every later launch is stream-ordered after it)
+    g->wave_clean = we.ctr != nullptr;   // once the queue has run (every later launch is stream-ordered after it)
+    g->flg_last = flg ? (int)(t & 1) : -1;
     if (imm_dev && n_roots) note_words(g);   // immediate roots change node words (fgi_restore copies them back)
     a.ticket = t;
     a.seq = seq;
     a.n_roots = n_roots;
     a.imm = imm_dev != nullptr;
+    a.flg = flg;
     a.group = group;
     a.t0 = t0;
     a.busy = true;

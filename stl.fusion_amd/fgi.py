@@ -120,6 +120,8 @@ SIGNATURES = {
     "fgi_free_pinned": [C.c_void_p],
     "fgi_wave_ids_dev": [_G, C.POINTER(C.c_void_p), _u64p],
     "fgi_last_wave_ids": [_G, _u32p, C.c_uint64, _u64p],
+    "fgi_last_wave_flagged": [_G, _u32p, _u32p, C.c_uint64, _u64p],
+    "fgi_wave_wait_flagged": [_G, C.c_uint64, _u32p, _u32p, C.c_uint64, _u64p],
     "fgi_invalidate_all": [_G, _u32p, C.c_uint64, _u64p, C.POINTER(WaveStats)],
     "fgi_prune": [_G, C.POINTER(PruneStats)],
     "fgi_prune_range": [_G, C.c_uint32, C.c_uint32, C.POINTER(PruneStats)],
@@ -490,6 +492,25 @@ class Graph:
         self._check(self.lib.fgi_last_wave_ids(self.h, _ptr(ids, C.c_uint32), len(ids), C.byref(n)),
                     "last_wave_ids")
         return ids
+
+    def last_wave_flagged(self) -> Tuple[np.ndarray, np.ndarray]:
+        """fgi_last_wave_flagged: (handles, state_flags) of the nodes the last call's cascade flagged
+        (InvalidateOnSetOutput / InvalidationDelayStarted newly set) without invalidating them, ascending."""
+        n = C.c_uint64()
+        self._check(self.lib.fgi_last_wave_flagged(self.h, None, None, 0, C.byref(n)), "last_wave_flagged")
+        ids, flags = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
+        self._check(self.lib.fgi_last_wave_flagged(self.h, _ptr(ids, C.c_uint32), _ptr(flags, C.c_uint32), len(ids),
+                                                   C.byref(n)), "last_wave_flagged")
+        return ids, flags
+
+    def wave_wait_flagged(self, ticket: int) -> Tuple[np.ndarray, np.ndarray]:
+        """fgi_wave_wait_flagged: wait for the ticket's wave; its flagged (handles, state_flags), ascending."""
+        n = C.c_uint64()
+        self._check(self.lib.fgi_wave_wait_flagged(self.h, ticket, None, None, 0, C.byref(n)), "wave_wait_flagged")
+        ids, flags = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
+        self._check(self.lib.fgi_wave_wait_flagged(self.h, ticket, _ptr(ids, C.c_uint32), _ptr(flags, C.c_uint32),
+                                                   len(ids), C.byref(n)), "wave_wait_flagged")
+        return ids, flags
 
     def invalidate_all(self, stats: Optional[WaveStats] = None) -> np.ndarray:
         ids = np.zeros(self.n_handles, np.uint32)

@@ -101,7 +101,7 @@ uint32_t* ComputedRegistry::IdsBuffer(uint64_t need) {
 }
 
 std::shared_ptr<Computed> ComputedRegistry::Get(const std::string& input) {
-    CompletePending();
+    Sync();
     const uint32_t s = SlotOf(input, false);
     if (s == FGI_NONE || !current_[s]) return nullptr;
     const ConsistencyState st = current_[s]->State();
@@ -117,7 +117,7 @@ void ComputedRegistry::MoveSubs(uint32_t from, uint32_t to) {
 }
 
 std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& input, bool has_delay) {
-    CompletePending();
+    Sync();
     const uint32_t s = SlotOf(input, true);
     auto c = std::make_shared<Computed>();
     c->reg_ = this;
@@ -129,12 +129,27 @@ std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& inpu
     uint32_t detached = FGI_NONE;
     fgi_wave_stats ws{};
     Check(fgi_begin_compute(g_, 1, &s, &c->version_, &hd, &detached, &ws), "fgi_begin_compute");
+    StartTimers(0);   // the delayed nodes the displacement cascade reached
     auto old = current_[s];
     if (detached != FGI_NONE) {   // displaced but alive (Computing / delayed): its handle moves
         if (old) {
             old->handle_ = detached;
             detached_[detached] = old;
             has_obj_[detached] = 1;
+            // a delayed node displaced while Consistent is flagged under its new handle (the call's flagged
+            // set does not list its slot, which names the new node now): its timer starts here, or follows
+            // it if it was already running
+            auto it = timers_.find(s);
+            if (it != timers_.end() && it->second.version == old->version_) {
+                timers_[detached] = it->second;
+                timers_.erase(s);
+            } else {
+                uint64_t v = 0;
+                uint32_t f = 0;
+                Check(fgi_get_state(g_, 1, &detached, &v, &f), "fgi_get_state");
+                if ((f & FGI_STATE_MASK) == FGI_CONSISTENT && (f & FGI_F_INVALIDATION_DELAY_STARTED))
+                    StartTimer(detached, old->version_, old->delay_);
+            }
         }
         MoveSubs(s, detached);   // the replicas follow the old node
     }
@@ -152,8 +167,14 @@ std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& inpu
     return c;
 }
 
+std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& input, std::chrono::nanoseconds delay) {
+    auto c = BeginCompute(input, delay != std::chrono::nanoseconds::zero());
+    c->delay_ = delay;
+    return c;
+}
+
 uint32_t ComputedRegistry::AddUsed(Computed& dependant, Computed& used) {
-    CompletePending();
+    Sync();
     uint32_t out = 0;
     const uint32_t d = dependant.handle_, u = used.handle_;
     Check(fgi_add_used(g_, 1, &d, &u, &out), "fgi_add_used");
@@ -161,7 +182,7 @@ uint32_t ComputedRegistry::AddUsed(Computed& dependant, Computed& used) {
 }
 
 bool ComputedRegistry::SetOutput(Computed& c) {
-    CompletePending();
+    Sync();
     uint8_t set = 0;
     const uint32_t h = c.handle_;
     uint64_t n = 0;
@@ -172,12 +193,13 @@ bool ComputedRegistry::SetOutput(Computed& c) {
         s = fgi_last_wave_ids(g_, ids, n, &n);
     }
     Check(s, "fgi_set_output");
+    StartTimers(0);
     Dispatch(ids, n);
     return set != 0;
 }
 
 void ComputedRegistry::RunWave(const uint32_t* roots, size_t n_roots, const uint8_t* imm) {
-    CompletePending();
+    Sync();
     uint64_t n = 0;
     last_ = fgi_wave_stats{};
     // the bitmap (n_handles / 8 bytes) costs less to bring back than the id list (4 B per node) once a
@@ -189,6 +211,7 @@ void ComputedRegistry::RunWave(const uint32_t* roots, size_t n_roots, const uint
         uint64_t* bits = bits_.get();
         Check(fgi_invalidate_bits(g_, (uint32_t)n_roots, roots, imm, bits, words, &n, &last_), "fgi_invalidate_bits");
         pred_v_ = n;
+        StartTimers(0);
         DispatchBits(bits, words, n);
         return;
     }
@@ -200,6 +223,7 @@ void ComputedRegistry::RunWave(const uint32_t* roots, size_t n_roots, const uint
     }
     Check(s, "fgi_invalidate");
     pred_v_ = n;
+    StartTimers(0);
     Dispatch(ids, n);
 }
 
@@ -222,6 +246,7 @@ void ComputedRegistry::DispatchBits(const uint64_t* bits, uint64_t words, uint64
 
 void ComputedRegistry::DispatchImpl(const uint32_t* ids, const uint64_t* bits, uint64_t words, uint64_t n) {
     const auto t0 = std::chrono::steady_clock::now();
+    DropTimers(ids, bits, words, n);
     std::unique_ptr<uint32_t[]> own;
     uint64_t own_cap = 0;
     if (ids_ && ids && ids == ids_.get()) {
@@ -470,12 +495,111 @@ void ComputedRegistry::Complete(uint64_t ticket) {
         Check(s, "fgi_wave_wait_ids");
         last_ = ws;
         pred_v_ = n;
+        StartTimers(t);
         Dispatch(ids, n);
     }
 }
 
 void ComputedRegistry::CompletePending() {
     if (!pending_.empty()) Complete(pending_.back());
+}
+
+// ---- delayed invalidation (Computed.cs:186-197, ComputedExt.cs:10-45) -----------------------------------
+// The reference's delayed node starts a timer of its own when Invalidate() only sets InvalidationDelayStarted;
+// the timer calls Invalidate(true), and the node's Invalidated handler disposes it. Here the engine reports
+// the nodes a wave flagged, the registry keeps one entry per such node, and the host drives the clock.
+void ComputedRegistry::Sync() {
+    CompletePending();
+    RunDueTimers();
+}
+
+void ComputedRegistry::StartTimer(uint32_t handle, LTag version, std::chrono::nanoseconds delay) {
+    using ns = std::chrono::nanoseconds;
+    if (delay == ns::zero()) delay = DefaultInvalidationDelay;
+    if (delay <= ns::zero() || delay == ns::max()) return;   // none, or never (TimeSpan.MaxValue, ComputedExt.cs:12)
+    auto it = timers_.find(handle);
+    if (it != timers_.end() && it->second.version == version) return;   // already running
+    const TimePoint now = Clock();
+    const TimePoint due = delay > TimePoint::max() - now ? TimePoint::max() : now + delay;
+    timers_[handle] = Timer{due, version};
+}
+
+void ComputedRegistry::StartTimers(uint64_t ticket) {
+    auto read = [&](uint32_t* ids, uint32_t* flags, uint64_t cap, uint64_t* n) {
+        return ticket ? fgi_wave_wait_flagged(g_, ticket, ids, flags, cap, n) : fgi_last_wave_flagged(g_, ids, flags, cap, n);
+    };
+    uint64_t n = 0;
+    Check(read(nullptr, nullptr, 0, &n), "fgi_last_wave_flagged");
+    if (!n) return;
+    std::vector<uint32_t> ids(n), flags(n);
+    Check(read(ids.data(), flags.data(), n, &n), "fgi_last_wave_flagged");
+    std::vector<uint32_t> bare;   // flagged nodes without a host object (bulk-registered)
+    for (uint64_t i = 0; i < n; ++i) {
+        // Computing nodes in the set need no host action: TrySetOutput invalidates them (Computed.cs:153-156)
+        if ((flags[i] & FGI_STATE_MASK) != FGI_CONSISTENT || !(flags[i] & FGI_F_INVALIDATION_DELAY_STARTED)) continue;
+        const uint32_t h = ids[i];
+        std::shared_ptr<Computed> c;
+        if (h < n_slots_) {
+            c = current_[h];
+        } else {
+            auto it = detached_.find(h);
+            if (it != detached_.end()) c = it->second;
+        }
+        if (c) StartTimer(h, c->version_, c->delay_);
+        else bare.push_back(h);
+    }
+    if (bare.empty() || DefaultInvalidationDelay <= std::chrono::nanoseconds::zero()) return;
+    std::vector<uint64_t> ver(bare.size());
+    std::vector<uint32_t> fl(bare.size());
+    Check(fgi_get_state(g_, (uint32_t)bare.size(), bare.data(), ver.data(), fl.data()), "fgi_get_state");
+    for (size_t i = 0; i < bare.size(); ++i) StartTimer(bare[i], ver[i], std::chrono::nanoseconds::zero());
+}
+
+void ComputedRegistry::DropTimers(const uint32_t* ids, const uint64_t* bits, uint64_t words, uint64_t n) {
+    if (timers_.empty() || n == 0) return;
+    for (auto it = timers_.begin(); it != timers_.end();) {
+        const uint32_t h = it->first;
+        const bool hit = bits ? ((uint64_t)(h >> 6) < words && ((bits[h >> 6] >> (h & 63)) & 1ull))
+                              : (ids && std::binary_search(ids, ids + n, h));   // ids come in ascending order
+        it = hit ? timers_.erase(it) : std::next(it);
+    }
+}
+
+size_t ComputedRegistry::RunDueTimers() {
+    if (in_timers_ || timers_.empty()) return 0;
+    CompletePending();   // a wave in flight may have invalidated a due node: its fan-out removes the entry
+    const TimePoint now = Clock();
+    std::vector<std::pair<uint32_t, LTag>> entries;   // (handle, version)
+    for (auto it = timers_.begin(); it != timers_.end();) {
+        if (it->second.due <= now) {
+            entries.emplace_back(it->first, it->second.version);
+            it = timers_.erase(it);
+        } else {
+            ++it;
+        }
+    }
+    if (entries.empty()) return 0;
+    std::sort(entries.begin(), entries.end());
+    std::vector<uint32_t> due;
+    for (const auto& e : entries) due.push_back(e.first);
+    // the entry fires only for the node it was started for, still waiting (Consistent, DelayStarted)
+    std::vector<uint64_t> ver(due.size());
+    std::vector<uint32_t> fl(due.size());
+    Check(fgi_get_state(g_, (uint32_t)due.size(), due.data(), ver.data(), fl.data()), "fgi_get_state");
+    std::vector<uint32_t> roots;
+    for (size_t i = 0; i < due.size(); ++i)
+        if (ver[i] == entries[i].second && (fl[i] & FGI_STATE_MASK) == FGI_CONSISTENT &&
+            (fl[i] & FGI_F_INVALIDATION_DELAY_STARTED))
+            roots.push_back(due[i]);
+    if (roots.empty()) return 0;
+    const std::vector<uint8_t> imm(roots.size(), 1);
+    struct Guard {
+        bool& b;
+        ~Guard() { b = false; }
+    } guard{in_timers_};
+    in_timers_ = true;
+    RunWave(roots.data(), roots.size(), imm.data());   // Invalidate(true), one wave for the batch
+    return roots.size();
 }
 
 // ---- access reports (ComputedRegistry.ReportAccess, Computed.RenewTimeouts) -----------------------
@@ -494,7 +618,7 @@ std::shared_ptr<Computed> ComputedRegistry::TryUseExisting(const std::string& in
 }
 
 std::shared_ptr<Computed> ComputedRegistry::GetExisting(const std::string& input) {
-    CompletePending();
+    Sync();
     const uint32_t s = SlotOf(input, false);
     if (s == FGI_NONE || !current_[s]) return nullptr;
     ReportAccess(*current_[s], false);
@@ -507,7 +631,7 @@ void ComputedRegistry::UseNew(Computed& computed, Computed* usedBy) {
 }
 
 void ComputedRegistry::InvalidateEverything() {
-    CompletePending();
+    Sync();
     uint64_t n = 0;
     last_ = fgi_wave_stats{};
     uint32_t* ids = IdsBuffer(1024);
@@ -517,11 +641,12 @@ void ComputedRegistry::InvalidateEverything() {
         s = fgi_last_wave_ids(g_, ids, n, &n);
     }
     Check(s, "fgi_invalidate_all");
+    StartTimers(0);
     Dispatch(ids, n);
 }
 
 std::pair<uint64_t, uint64_t> ComputedRegistry::Prune() {
-    CompletePending();
+    Sync();
     fgi_prune_stats ps{};
     Check(fgi_prune(g_, &ps), "fgi_prune");
     return {ps.old_edges, ps.new_edges};

@@ -15,6 +15,12 @@
 //   ComputeMethodFunctionBase.Compute -> new Computing node (ComputeMethodFunctionBase.cs:19-27)
 //   IComputedImpl.AddUsed, TrySetOutput, UsedBy      (Computed.cs:141-160, 327-385)
 //   ComputedGraphPruner pass                         (Internal/ComputedGraphPruner.cs:79-94)
+//   Delayed invalidation: a Consistent node with an InvalidationDelay that a cascade reaches only gets
+//   InvalidationDelayStarted and schedules its own timer, which later calls Invalidate(true)
+//                                                   (Computed.cs:186-197, ComputedExt.cs:10-45) — here
+//   a timer entry per node the engine reports as flagged (fgi_last_wave_flagged /
+//   fgi_wave_wait_flagged), on a registry clock tests can drive: no threads, no sleeping; RunDueTimers
+//   invalidates what is due.
 //   RPC replica invalidation: an inbound compute call waits for its computed's invalidation and
 //   then sends `$sys-c.Invalidate(callId)` to its peer (Client/Internal/RpcInboundComputeCall.cs:
 //   53-62, 102-106) — here a subscription (handle -> peer, call id), delivered per peer in batches
@@ -33,6 +39,7 @@
 //   4. per host object: OnUnregister, then its InvalidatedHandlerSet, each handler exactly once.
 #pragma once
 
+#include <chrono>
 #include <cstdint>
 #include <deque>
 #include <functional>
@@ -119,6 +126,7 @@ class Computed {
     LTag version_ = 0;
     bool fired_ = false;
     InvalidatedHandlerSet handlers_;
+    std::chrono::nanoseconds delay_{0};          // ComputedOptions.InvalidationDelay (0: none, max(): never)
     std::shared_ptr<std::promise<void>> when_;   // WhenInvalidated's promise, once asked for
     std::shared_future<void> when_f_;
 };
@@ -148,7 +156,12 @@ class ComputedRegistry {
     std::shared_ptr<Computed> Get(const std::string& input);
     // ComputeMethodFunctionBase.Compute: a new Computing node of `input` replaces (and, per
     // Register, invalidates) the current one
+    // has_delay without a duration: the node is flagged like a delayed one (InvalidationDelayStarted), and
+    // gets a timer only if the registry has a DefaultInvalidationDelay
     std::shared_ptr<Computed> BeginCompute(const std::string& input, bool has_delay = false);
+    // ComputedOptions.InvalidationDelay: 0 = none, nanoseconds::max() = never (TimeSpan.MaxValue,
+    // ComputedExt.cs:12: the node is flagged, no timer starts)
+    std::shared_ptr<Computed> BeginCompute(const std::string& input, std::chrono::nanoseconds delay);
     // dependant.AddUsed(used); returns the FGI_USED_* outcome (FGI_USED_ESTATE = the reference throws)
     uint32_t AddUsed(Computed& dependant, Computed& used);
     // TrySetOutput: true if the node was Computing; an InvalidateOnSetOutput node cascades at once
@@ -188,7 +201,7 @@ class ComputedRegistry {
     // when the registry completes the wave — Complete(ticket), CompletePending(), or any other registry
     // call, which completes the waves in flight first. LastTicket() names the last queued wave.
     InvalidationScope InvalidateAsync() {
-        async_scope_ = true;
+        if (scope_depth_ == 0) async_scope_ = true;   // only the outermost scope decides how the batch is flushed
         return InvalidationScope(this);
     }
     uint64_t LastTicket() const { return last_ticket_; }
@@ -198,6 +211,20 @@ class ComputedRegistry {
     void Complete(uint64_t ticket);
     void CompletePending();
     size_t PendingWaves() const { return pending_.size(); }
+    // ---- delayed invalidation (Computed.cs:186-197 -> ComputedExt.Invalidate(TimeSpan), ComputedExt.cs:10-45) --
+    // After every wave the registry runs (RunWave in both output forms, Complete, BeginCompute's displacement
+    // cascade, SetOutput's cascade, InvalidateEverything) it reads the wave's flagged set; each handle reported
+    // Consistent with InvalidationDelayStarted gets a timer entry (due time, handle, version) — its node's
+    // delay, or DefaultInvalidationDelay for a node without one (has_delay only, bulk-registered). Computing
+    // nodes in the set need no host action: fgi_set_output cascades them. RunDueTimers invalidates every due
+    // entry with immediately = true in one wave; an entry whose node was invalidated meanwhile is removed
+    // when that wave is fanned out (ComputedExt.cs:38-45), never fired. It also runs at the start of every
+    // registry call that completes the pending waves. Returns the entries fired.
+    using TimePoint = std::chrono::steady_clock::time_point;
+    std::function<TimePoint()> Clock = [] { return std::chrono::steady_clock::now(); };
+    std::chrono::nanoseconds DefaultInvalidationDelay{0};
+    size_t RunDueTimers();
+    size_t PendingTimers() const { return timers_.size(); }
     // `_ = svc.Get(input)` inside a scope: TryUseExisting's Invalidate branch (ComputedExt.cs:29-35)
     void InvalidateInput(const std::string& input);
     // Slot-level roots (inputs already resolved by the host, e.g. bulk-registered nodes)
@@ -244,6 +271,13 @@ class ComputedRegistry {
     void DispatchBits(const uint64_t* bits, uint64_t words, uint64_t n);
     void DispatchImpl(const uint32_t* ids, const uint64_t* bits, uint64_t words, uint64_t n);
     void FlushScope();
+    // CompletePending, then RunDueTimers: the start of every registry call that needs the registry current
+    void Sync();
+    // the flagged set of the last synchronous call (ticket 0) or of an asynchronous ticket -> timer entries
+    void StartTimers(uint64_t ticket);
+    void StartTimer(uint32_t handle, LTag version, std::chrono::nanoseconds delay);
+    // the timers of the nodes a wave invalidated are removed before its handlers run
+    void DropTimers(const uint32_t* ids, const uint64_t* bits, uint64_t words, uint64_t n);
     void ReportAccess(Computed& c, bool is_new);
     LTag NextVersion(LTag current);
     void MoveSubs(uint32_t from, uint32_t to);
@@ -258,6 +292,12 @@ class ComputedRegistry {
     std::vector<uint8_t> scope_imm_;
     int scope_depth_ = 0;
     bool async_scope_ = false;               // the outermost open scope flushes asynchronously
+    struct Timer {
+        TimePoint due;
+        LTag version;
+    };
+    std::unordered_map<uint32_t, Timer> timers_;   // handle -> its pending delayed invalidation
+    bool in_timers_ = false;                 // RunDueTimers is running (its own wave does not re-enter it)
     std::deque<uint64_t> pending_;           // asynchronous waves queued, not yet completed (ticket order)
     uint64_t last_ticket_ = 0;
     LTag ltag_ = 0x100000;
