@@ -271,7 +271,8 @@ fgi_status fgi_last_wave_ids(fgi_graph* g, uint32_t* out_ids, uint64_t cap, uint
  * node's canonical state_flags after the call. A slot fgi_begin_compute displaced is not listed (its
  * handle names the new node when the call returns; the displaced node is out_detached[i]). FGI_ECAPACITY
  * with *out_n set if cap is short; out_ids NULL = count only. Valid until the next call that runs a wave.
- * After fgi_run_batch or any fgi_part_* call: FGI_ENOTSUP (their cascades report no flagged sets).
+ * After fgi_run_batch: FGI_ENOTSUP (a batch's cascades report through fgi_last_batch_flagged); after any
+ * fgi_part_* call: FGI_ENOTSUP (their cascades report no flagged sets).
  * A graph that never held a Computing node or one with hasDelay reports empty sets at no cost: its waves
  * launch nothing for them. */
 fgi_status fgi_last_wave_flagged(fgi_graph* g, uint32_t* out_ids, uint32_t* out_flags, uint64_t cap, uint64_t* out_n);
@@ -336,6 +337,30 @@ typedef struct fgi_batch_stats {
  * reported once and nothing later runs on an undefined registry. */
 fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, uint32_t* out_ids, uint64_t cap,
                          uint64_t* out_n, fgi_batch_stats* stats);
+/* The flagged sets of the last fgi_run_batch, cascade after cascade (steps of kind INVALIDATE,
+ * BEGIN_COMPUTE, SET_OUTPUT, in step order): out_step[i] = index of the step whose cascade flagged
+ * out_ids[i]; within a step ascending boundary handles (detached ones included); out_flags[i] = the
+ * node's canonical state_flags right after that cascade.
+ * The flagged set of a cascade is fgi_last_wave_flagged's, per cascade: every handle whose canonical
+ * state_flags gained FGI_F_INVALIDATE_ON_SET_OUTPUT and / or FGI_F_INVALIDATION_DELAY_STARTED during that
+ * cascade and that the cascade did not invalidate, whatever the visit order. A handle may appear under
+ * more than one step (a Computing node a cascade reaches in step 0 gains InvalidateOnSetOutput; an
+ * `immediately` root on it in step 2 adds InvalidationDelayStarted). A begin_compute step's own slots are
+ * not listed under that step (fgi_last_wave_flagged's rule: the displaced node that survives is the
+ * step's out[i]).
+ * Slot reuse: a record names the node that lived at the handle when its cascade ended. If a later step of
+ * the same batch begins a computation on that slot, that node lives on at that step's out[i] detached
+ * handle, or is gone if out[i] is FGI_NONE; the host that starts timers from the records follows it there.
+ * out_step and out_flags are nullable; out_ids NULL = count only; FGI_ECAPACITY with *out_n set if cap is
+ * short. The batch itself copies nothing for this: the records stay on the device and the first call after
+ * the batch copies them (one device-to-host copy, one wait). Valid until the next call that runs a wave or
+ * a batch, or fgi_restore. After a batch that failed with FGI_ECAPACITY at step k (out of detached
+ * handles): the cascades of the steps before k. FGI_ENOTSUP if the last call that ran cascades was not
+ * fgi_run_batch, and after any fgi_part_* call; FGI_ESTATE on a poisoned graph. A graph that never held a
+ * Computing node or one with hasDelay reports empty sets at no cost: its batches allocate and launch
+ * nothing for them (the records take 16 bytes of device memory per handle otherwise). */
+fgi_status fgi_last_batch_flagged(fgi_graph* g, uint32_t* out_step, uint32_t* out_ids, uint32_t* out_flags,
+                                  uint64_t cap, uint64_t* out_n);
 
 /* ---- graph maintenance ---------------------------------------------------------------------- */
 /* One ComputedGraphPruner pass (Internal/ComputedGraphPruner.cs:79-94): PruneUsedBy on every

@@ -181,6 +181,29 @@ constexpr int kAccBarrierIdx = 7;       // acc[7]: a cascade's grid barrier time
 // word 0 k_wave_coop's (streaming cascades), word kGbarFused k_wave_fused's (their grids differ)
 constexpr int kGbarWords = 32, kGbarFused = 16;
 
+// Record sink of a batch's cascades (fgi_last_batch_flagged). A cascade of k_wave_coop
+// appends one record per node it only flags: boundary handle << 32 | canonical state_flags (k_flag_list's
+// format). rec == nullptr: no sink (the graph cannot flag, or the wave is no batch's). The cursor counts
+// every record of the batch, also those past cap, which are not written. A batch's cascades run one after
+// the other on one stream, so a cascade's records are the run [cursor at its start, cursor at its end).
+// A cascade records in two places: its `immediately` roots before its first grid barrier, its fold behind
+// its last one; nothing in between. So one thread publishes the boundary for free while the levels run:
+// mark: the step's word, set after the first barrier to 1 + the cursor (then: this cascade's start + its
+//   immediate roots' records); it stays 0 if the launch finds no roots or the batch aborted, which
+//   records nothing;
+// imm_n: the step's count of immediate roots' records.
+// The cascade's run starts at mark - 1 - imm_n and ends where the next cascade that ran starts (the last
+// one: at the cursor the batch's results bring back).
+struct RecSink {
+    unsigned long long* rec = nullptr;   // [cap]
+    unsigned long long* cur = nullptr;
+    uint64_t cap = 0;
+    const uint32_t* l2s = nullptr;       // hot label -> slot (labels below K); a cold label l is handle l - K
+    uint32_t K = 0;
+    unsigned long long* mark = nullptr;
+    unsigned long long* imm_n = nullptr;
+};
+
 // Per-level counters. The producers of level L's frontier (roots, push emits, received targets)
 // reserve list space with ONE packed 64-bit atomic on `ft` (frontier entries << 32 | edges): the
 // returned value is both the entry index and the exclusive edge offset (escan) of the reserving
@@ -465,7 +488,7 @@ struct fgi_graph {
     unsigned long long* flg_out[2] = {nullptr, nullptr};   // [n_handles] per ticket parity (synchronous waves: 0):
                                        // boundary handle << 32 | canonical state_flags, unordered
     unsigned long long* flg_cnt = nullptr;   // [2] entries in flg_out[k]
-    int flg_last = -1;                 // the last call's set: -1 empty, 0 / 1 flg_out[k], -2 not reported (batch)
+    int flg_last = -1;                 // the last call's set: -1 empty, 0 / 1 flg_out[k], -2 a batch's (bflg_runs)
     std::vector<uint32_t> flg_drop;    // boundary slots the last call replaced (fgi_begin_compute): not in its set
     // Invalidated bitmap: bit h set = node h was invalidated by this wave. It is the frontier of a
     // pull level: every node invalidated before the previous level already had all its dependants
@@ -574,6 +597,22 @@ struct fgi_graph {
     uint32_t* bout = nullptr;
     uint64_t bout_cap = 0;
     uint64_t batch_ids_hint = 0;       // the previous batch's id count (sizes the copy made with the results)
+    // The flagged sets of the last batch's cascades (fgi_last_batch_flagged), valid while
+    // flg_last == -2. brec: the records the cascades wrote (16 B per handle, allocated by the first batch on
+    // a graph that can flag). bflg_runs: per cascade that ran to its end, in step order, its record run and
+    // where the staging (bst_h) keeps a begin_compute step's slots (dropped from its run). bflg_step /
+    // bflg_set: the accessor's result, made on its first call after the batch (one copy, sorted per run).
+    unsigned long long* brec = nullptr;
+    uint64_t brec_cap = 0;
+    struct BatchRun {
+        uint32_t step = 0, n_drop = 0;
+        size_t drop_off = 0;           // the step's slots in bst_h (n_drop of them; begin_compute only)
+        uint64_t lo = 0, hi = 0;       // records [lo, hi) of brec
+    };
+    std::vector<BatchRun> bflg_runs;
+    std::vector<uint32_t> bflg_step;   // the accessor's cache: step, then handle << 32 | state_flags
+    std::vector<uint64_t> bflg_set;
+    bool bflg_read = false;
     std::vector<hipEvent_t> batch_ev;  // fgi_run_batch per-cascade timing events (pairs)
     hipEvent_t ev_w0 = nullptr, ev_w1 = nullptr;
 
@@ -703,10 +742,11 @@ void print_coop_probe();
 // device-resident roots (n_max, or *n_dev of them), ids appended at out[*out_n ..), totals added to
 // acc[0..6] (waves, levels, invalidated, E_trav, E_match, flagged, frontier entries; acc[7] set if a
 // grid barrier timed out); nothing
-// happens if *abort (nullable) is set when the wave starts.
+// happens if *abort (nullable) is set when the wave starts. sink (nullable): the nodes the wave only flags
+// are appended there (RecSink).
 fgi_status run_wave_coop(fgi_graph* g, uint32_t n_max, const uint32_t* roots_dev, const uint8_t* imm_dev,
                          const unsigned long long* n_dev, uint32_t* out, unsigned long long* out_n,
-                         unsigned long long* acc, unsigned long long* abort);
+                         unsigned long long* acc, unsigned long long* abort, const RecSink* sink = nullptr);
 // Asynchronous waves (wave.hip): queue a wave and return (ticket), wait for one (and every earlier
 // one), wait for all in flight. Every entry point but fgi_restore, fgi_set_option and the async calls
 // themselves drains first (usable()).

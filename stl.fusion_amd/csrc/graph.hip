@@ -1835,7 +1835,7 @@ extern "C" {
 
 fgi_status fgi_version(uint32_t* major, uint32_t* minor) {
     if (major) *major = 0;
-    if (minor) *minor = 2;   // 0.2: fgi_last_wave_flagged, fgi_wave_wait_flagged
+    if (minor) *minor = 3;   // 0.2: fgi_last_wave_flagged, fgi_wave_wait_flagged; 0.3: fgi_last_batch_flagged
     return FGI_OK;
 }
 
@@ -2003,6 +2003,7 @@ fgi_status fgi_destroy(fgi_graph* g) {
     if (g->bst_h) hipHostFree(g->bst_h);
     dfree(g->bst_d);
     dfree(g->bout);
+    dfree(g->brec);
     if (g->ev_w0) hipEventDestroy(g->ev_w0);
     if (g->ev_w1) hipEventDestroy(g->ev_w1);
     if (g->stream) hipStreamDestroy(g->stream);
@@ -2652,8 +2653,8 @@ fgi_status fgi_last_wave_flagged(fgi_graph* g, uint32_t* out_ids, uint32_t* out_
     if (!g) return FGI_EINVAL;
     FGI_TRY(usable(g));
     if (g->part || g->flg_last == -2)
-        return set_err(g, FGI_ENOTSUP, "fgi_last_wave_flagged: the cascades of fgi_run_batch and of the fgi_part_* calls "
-                                       "report no flagged sets");
+        return set_err(g, FGI_ENOTSUP, "fgi_last_wave_flagged: the cascades of fgi_run_batch report through "
+                                       "fgi_last_batch_flagged, those of the fgi_part_* calls report no flagged sets");
     hipSetDevice(g->device);
     std::vector<uint64_t> set;
     FGI_TRY(read_flagged(g, g->flg_last, false, &set));
@@ -2665,8 +2666,8 @@ fgi_status fgi_wave_wait_flagged(fgi_graph* g, uint64_t ticket, uint32_t* out_id
     if (!g) return FGI_EINVAL;
     FGI_TRY(usable_now(g));
     if (g->part || g->flg_last == -2)
-        return set_err(g, FGI_ENOTSUP, "fgi_wave_wait_flagged: the cascades of fgi_run_batch and of the fgi_part_* calls "
-                                       "report no flagged sets");
+        return set_err(g, FGI_ENOTSUP, "fgi_wave_wait_flagged: the cascades of fgi_run_batch report through "
+                                       "fgi_last_batch_flagged, those of the fgi_part_* calls report no flagged sets");
     hipSetDevice(g->device);
     FGI_TRY(wave_wait(g, ticket, nullptr, nullptr, nullptr));
     // the ticket's buffer is its own until the wave two tickets later is queued (as its ids); a blocking
@@ -2896,7 +2897,8 @@ struct BatchStep {
 // Launches steps [from, n) of a batch; returns with the work queued (no synchronisation).
 static fgi_status batch_launch(fgi_graph* g, uint32_t from, uint32_t n_steps, const fgi_step* steps,
                                std::vector<BatchStep>& bs, unsigned long long* scr, const uint32_t* take,
-                               uint64_t n_take, bool timed, std::vector<std::pair<hipEvent_t, hipEvent_t>>& wave_ev) {
+                               uint64_t n_take, bool timed, std::vector<std::pair<hipEvent_t, hipEvent_t>>& wave_ev,
+                               const RecSink* sink) {
     FGI_TRY(flush_vis(g));
     hipStream_t st = g->stream;
     unsigned long long* abort = scr;
@@ -2906,7 +2908,16 @@ static fgi_status batch_launch(fgi_graph* g, uint32_t from, uint32_t n_steps, co
     auto* node = reinterpret_cast<unsigned long long*>(g->node);
     // per-cascade timing (the wave share of fgi_batch_stats) only when asked for: timestamped
     // markers between the launches cost device time of their own; the events are the graph's pool
-    auto wave = [&](uint32_t n_max, const uint32_t* roots, const uint8_t* imm, const unsigned long long* n_dev) -> fgi_status {
+    // sink (the graph can flag): the step's cascade records the nodes it only flags, its boundary in
+    // cnt[2] (records of immediate roots) and cnt[3] (RecSink::mark)
+    auto wave = [&](uint32_t n_max, const uint32_t* roots, const uint8_t* imm, const unsigned long long* n_dev,
+                    unsigned long long* cnt) -> fgi_status {
+        RecSink sk;
+        if (sink) {
+            sk = *sink;
+            sk.imm_n = cnt + 2;
+            sk.mark = cnt + 3;
+        }
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (timed) {
             const size_t i = wave_ev.size();
@@ -2920,7 +2931,7 @@ static fgi_status batch_launch(fgi_graph* g, uint32_t from, uint32_t n_steps, co
             wave_ev.emplace_back(e0, e1);
             FGI_HIP(g, hipEventRecord(e0, st));
         }
-        FGI_TRY(run_wave_coop(g, n_max, roots, imm, n_dev, g->bout, out_n, acc, abort));
+        FGI_TRY(run_wave_coop(g, n_max, roots, imm, n_dev, g->bout, out_n, acc, abort, sink ? &sk : nullptr));
         if (e1) FGI_HIP(g, hipEventRecord(e1, st));
         return fold(g);
     };
@@ -2933,13 +2944,13 @@ static fgi_status batch_launch(fgi_graph* g, uint32_t from, uint32_t n_steps, co
         switch (sp.kind) {
             case FGI_STEP_INVALIDATE:
                 FGI_TRY(fold(g));
-                FGI_TRY(wave(n, b.h, b.flags, nullptr));
+                FGI_TRY(wave(n, b.h, b.flags, nullptr, b.cnt));
                 break;
             case FGI_STEP_BEGIN_COMPUTE: {
                 FGI_TRY(fold(g));
                 hipLaunchKernelGGL(kb_bc_classify_check, dim3(nblk(n)), dim3(256), 0, st, abort, n, b.h, node, b.cls, b.roots,
                                    b.cnt, cursor, n_take, k, g->done);
-                FGI_TRY(wave(n, b.roots, nullptr, b.cnt));   // displacement cascade (ComputedRegistry.cs:91-94)
+                FGI_TRY(wave(n, b.roots, nullptr, b.cnt, b.cnt));   // displacement cascade (ComputedRegistry.cs:91-94)
                 touch(g);
                 note_words(g);
                 const InstallArgs ia{b.h,        b.ver,      b.flags,    b.cls,       take, cursor, g->n_slots, node,
@@ -2972,7 +2983,7 @@ static fgi_status batch_launch(fgi_graph* g, uint32_t from, uint32_t n_steps, co
                 note_words(g);
                 hipLaunchKernelGGL(kb_set_output, dim3(nblk(n)), dim3(256), 0, st, abort, n, b.h, g->n_handles, node,
                                    b.out8, b.roots, b.cnt);
-                FGI_TRY(wave(n, b.roots, nullptr, b.cnt));   // Invalidate() of InvalidateOnSetOutput nodes (153-156)
+                FGI_TRY(wave(n, b.roots, nullptr, b.cnt, b.cnt));   // Invalidate() of InvalidateOnSetOutput nodes (153-156)
                 break;
             default:
                 break;
@@ -3011,9 +3022,14 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
         }
     }
     FGI_TRY(single_only(g, "fgi_run_batch"));
-    g->flg_last = -2;   // a batch's cascades report no flagged sets
+    g->flg_last = -2;   // the batch's cascades report through fgi_last_batch_flagged (bflg_runs)
     g->flg_drop.clear();
+    g->bflg_runs.clear();
+    g->bflg_step.clear();
+    g->bflg_set.clear();
+    g->bflg_read = false;
     if (n_begin) g->flag_gate = true;
+    const bool rec_on = g->flag_gate;   // off: nothing is allocated, queued or launched differently
     const auto t_check = std::chrono::steady_clock::now();
     hipSetDevice(g->device);
     hipStream_t st = g->stream;
@@ -3025,6 +3041,16 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
         g->bout_cap = 0;
         FGI_TRY(dmalloc(g, &g->bout, need_out));
         g->bout_cap = need_out;
+    }
+    // the cascades' flag-only records: each of a node's two flag bits goes 0 -> 1 at most
+    // once in its life and every record reports at least one such change, so a batch writes at most two per
+    // node it ever holds: those of its handles and one more per begin_compute entry
+    const uint64_t need_rec = rec_on ? 2 * ((uint64_t)g->n_handles + n_begin) : 0;
+    if (g->brec_cap < need_rec) {
+        dfree(g->brec);
+        g->brec_cap = 0;
+        FGI_TRY(dmalloc(g, &g->brec, need_rec));
+        g->brec_cap = need_rec;
     }
     if (n_add) FGI_TRY(ensure_pool(g, g->pool_top + std::max<uint64_t>(1ull << 20, 4 * n_add)));
     FGI_TRY(ensure_cstart(g, std::max<uint64_t>(g->pool_top, g->pool_cap)));
@@ -3059,10 +3085,12 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
         if (sp.kind == FGI_STEP_BEGIN_COMPUTE || sp.kind == FGI_STEP_ADD_USED) out_bytes += stage_round(sp.n * 4);
         if (sp.kind == FGI_STEP_SET_OUTPUT) out_bytes += stage_round(sp.n);
     }
-    // scratch words: abort, ids, detached taken, accumulators, 4 counters per step, the pool top
-    const size_t scr_words = 3 + kAccCount + 4 * (size_t)n_steps + 1;
+    // scratch words: abort, ids, detached taken, accumulators, 4 counters per step (the last one of a step
+    // with a cascade: the record cursor at the cascade's end), the pool top, the record cursor
+    const size_t scr_words = 3 + kAccCount + 4 * (size_t)n_steps + 2;
     const size_t scr_bytes = stage_round(scr_words * 8);
-    const size_t ptop_word = scr_words - 1;
+    const size_t ptop_word = scr_words - 2;
+    const size_t rcur_word = scr_words - 1;
     // the ids are copied back with the results when they fit the previous batch's count (+25%)
     const uint64_t spec = out_ids ? std::min<uint64_t>(cap, g->batch_ids_hint + g->batch_ids_hint / 4 + 4096) : 0;
     const size_t res_off = in_bytes + scr_bytes;   // outputs follow the scratch words
@@ -3202,8 +3230,35 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
     const bool timed = stats && g->opt_level_timing;
     uint32_t syncs = 0, from = 0;
     g->last_wave_n = 0;
+    RecSink sink;
+    sink.rec = g->brec;
+    sink.cur = scr + rcur_word;
+    sink.cap = g->brec_cap;
+    sink.l2s = g->l2s;
+    sink.K = g->lbl_K;
+    // The cascades of steps [0, end) ran to their end: their record runs, from the words each left in its
+    // step's counters (RecSink; a resumed batch keeps the cursor and the words of the cascades that ran
+    // before). A cascade that found no roots left no word and has no records. The records stay on the
+    // device until fgi_last_batch_flagged asks for them.
+    auto note_runs = [&](uint32_t end) {
+        for (uint32_t k = 0; rec_on && k < end; ++k) {
+            const fgi_step& sp = steps[k];
+            const unsigned long long* cnt = scr_h + 3 + kAccCount + 4 * (size_t)k;
+            if (!sp.n || sp.kind == FGI_STEP_ADD_USED || cnt[3] == 0) continue;
+            fgi_graph::BatchRun r;
+            r.step = k;
+            r.lo = cnt[3] - 1 - cnt[2];
+            r.hi = scr_h[rcur_word];
+            if (!g->bflg_runs.empty()) g->bflg_runs.back().hi = r.lo;
+            if (sp.kind == FGI_STEP_BEGIN_COMPUTE) {
+                r.drop_off = in_off[4 * k];
+                r.n_drop = sp.n;
+            }
+            g->bflg_runs.push_back(r);
+        }
+    };
     while (true) {
-        fgi_status s = batch_launch(g, from, n_steps, steps, bs, scr, take, n_take, timed, wave_ev);
+        fgi_status s = batch_launch(g, from, n_steps, steps, bs, scr, take, n_take, timed, wave_ev, rec_on ? &sink : nullptr);
         if (s != FGI_OK) return s;
         // results: the counters, the pool top and every step's output in one copy, the ids (as
         // many as the previous batch had, +25%) in a second, then one wait
@@ -3251,10 +3306,12 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
             continue;
         }
         // out of detached handles at step k: steps before it are applied
+        note_runs(k);
         g->free_detached.resize(g->free_detached.size() - (size_t)scr_h[2]);
         return set_err(g, FGI_ECAPACITY, "step %u: out of detached handles (%zu free)", k, g->free_detached.size());
     }
-    // host bookkeeping: the detached handles taken, the per-step outputs
+    // host bookkeeping: the cascades' record runs, the detached handles taken, the per-step outputs
+    note_runs(n_steps);
     g->free_detached.resize(g->free_detached.size() - (size_t)scr_h[2]);
     for (uint32_t k = 0; k < n_steps; ++k) {
         const fgi_step& sp = steps[k];
@@ -3310,6 +3367,51 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
         stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     return ret;
+}
+
+// The batch left its cascades' records on the device (bflg_runs): the first call copies them once, sorts
+// each cascade's run by handle and drops a begin_compute step's own slots (fgi_begin_compute's rule,
+// flg_drop: they name the new nodes when the call returns; the staging still holds the step's slots as
+// the boundary numbers them).
+fgi_status fgi_last_batch_flagged(fgi_graph* g, uint32_t* out_step, uint32_t* out_ids, uint32_t* out_flags, uint64_t cap,
+                                  uint64_t* out_n) {
+    if (!g) return FGI_EINVAL;
+    FGI_TRY(usable(g));
+    if (g->part || g->flg_last != -2)
+        return set_err(g, FGI_ENOTSUP, "fgi_last_batch_flagged: the last call that ran cascades was not fgi_run_batch");
+    if (!g->bflg_read) {
+        hipSetDevice(g->device);
+        const uint64_t total = g->bflg_runs.empty() ? 0 : g->bflg_runs.back().hi;
+        if (total > g->brec_cap)
+            return set_err(g, FGI_EDEVICE, "the batch's cascades flagged %llu nodes, their buffer holds %llu",
+                           (unsigned long long)total, (unsigned long long)g->brec_cap);
+        std::vector<uint64_t> raw(total);
+        FGI_TRY(d2h(g, raw.data(), reinterpret_cast<const uint64_t*>(g->brec), total));
+        std::vector<uint32_t> drop;
+        for (const fgi_graph::BatchRun& r : g->bflg_runs) {
+            std::sort(raw.begin() + (ptrdiff_t)r.lo, raw.begin() + (ptrdiff_t)r.hi);
+            const uint32_t* slots = reinterpret_cast<const uint32_t*>(g->bst_h + r.drop_off);
+            drop.assign(slots, slots + r.n_drop);
+            std::sort(drop.begin(), drop.end());
+            for (uint64_t i = r.lo; i < r.hi; ++i) {
+                if (std::binary_search(drop.begin(), drop.end(), (uint32_t)(raw[i] >> 32))) continue;
+                g->bflg_step.push_back(r.step);
+                g->bflg_set.push_back(raw[i]);
+            }
+        }
+        g->bflg_read = true;
+    }
+    const uint64_t n = g->bflg_set.size();
+    if (out_n) *out_n = n;
+    if (!out_ids) return FGI_OK;
+    if (n > cap) return set_err(g, FGI_ECAPACITY, "the batch's flagged sets hold %llu handles, the buffer %llu",
+                                (unsigned long long)n, (unsigned long long)cap);
+    for (uint64_t i = 0; i < n; ++i) {
+        out_ids[i] = (uint32_t)(g->bflg_set[i] >> 32);
+        if (out_step) out_step[i] = g->bflg_step[i];
+        if (out_flags) out_flags[i] = (uint32_t)g->bflg_set[i];
+    }
+    return FGI_OK;
 }
 
 // PruneUsedBy over the rows of handles [lo, hi) in place (queued, no synchronisation): the

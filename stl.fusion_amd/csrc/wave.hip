@@ -586,11 +586,21 @@ __device__ __forceinline__ uint32_t root_label(const RootMap& m, uint32_t x) {
     return x + m.K;
 }
 
+// Record o of a batch's record sink (RecSink): label l, whose canonical word is now w, under its boundary
+// handle. A record past the buffer's capacity is counted (the cursor) and not written.
+__device__ __forceinline__ unsigned long long rec_word(const RecSink& rs, uint32_t l, unsigned long long w) {
+    const uint32_t id = l < rs.K ? rs.l2s[l] : l - rs.K;
+    return ((unsigned long long)id << 32) | word_to_flags(w);
+}
+__device__ __forceinline__ void rec_put(const RecSink& rs, unsigned long long o, uint32_t l, unsigned long long w) {
+    if (o < rs.cap) rs.rec[o] = rec_word(rs, l, w);
+}
+
 template <int IMM>
 __device__ __forceinline__ void root_step(uint32_t i, const uint32_t* __restrict__ roots, const uint8_t* __restrict__ imm,
                                           uint32_t n, uint32_t base, uint32_t n_range, unsigned long long* node,
                                           uint32_t* vis, const Out& o, WaveCtr* ctr, const RootMap& rm = RootMap{},
-                                          uint32_t* flg = nullptr) {
+                                          uint32_t* flg = nullptr, const RecSink& rs = RecSink{}) {
     uint32_t win = 0, flagged = 0, h = 0;
     if (i < n) {
         h = rm.on ? root_label(rm, roots[i]) : roots[i] - base;
@@ -620,6 +630,13 @@ __device__ __forceinline__ void root_step(uint32_t i, const uint32_t* __restrict
                     if (r == 2 && flg) {
                         atomicOr(vis + (h >> 5), 1u << (h & 31));
                         atomicOr(flg + (h >> 5), 1u << (h & 31));
+                    }
+                    // a batch's cascade (k_wave_coop) records it instead, one atomic per such root (w is the
+                    // word the CAS replaced). The word now holds InvalidateOnSetOutput, so a later visit of
+                    // this cascade changes nothing and its fold does not record the handle a second time.
+                    if (r == 2 && rs.rec) {
+                        rec_put(rs, atomicAdd(rs.cur, 1ull), h, imm_word(v ? visited_word(w) : w));
+                        atomicAdd(rs.imm_n, 1ull);
                     }
                 } else {
                     r = visit_bit(vis, h, w);
@@ -1990,6 +2007,7 @@ struct CoopArgs {
     int one_round;                     // chunk size by level_mult_one_round (FGI_COOP_CHUNKS=0: level_mult)
     FoldArgs fold;                     // hot labels: the ids come from the folded bitmap (fold_tile)
     uint64_t ext_words;                // words of the bitmap over boundary handles
+    RecSink sink;                      // rec null: none. The nodes the cascade only flags (fgi_last_batch_flagged)
 };
 
 // Grid barrier of a plain (non-cooperative) launch of k_wave_coop. A cooperative launch goes to the
@@ -2091,7 +2109,8 @@ __global__ __launch_bounds__(kBlock) void k_wave_coop(CoopArgs a) {
     const Out o0{a.row_off, a.row_len, a.inv_bm, a.fr_off[0], a.fr_len[0], a.escan[0], a.cstart[0], &ctr->lvl[0]};
     if (a.imm) {   // Invalidate(true) roots first: their CAS may change node words
         for (uint32_t i0 = blockIdx.x * blockDim.x; i0 < n; i0 += gsize)
-            root_step<1>(i0 + threadIdx.x, a.roots, a.imm, n, 0u, a.n_handles, a.node, a.vis, o0, ctr);
+            root_step<1>(i0 + threadIdx.x, a.roots, a.imm, n, 0u, a.n_handles, a.node, a.vis, o0, ctr, RootMap{}, nullptr,
+                         a.sink);
         if (!grid_sync()) return;
     }
     for (uint32_t i0 = blockIdx.x * blockDim.x; i0 < n; i0 += gsize)
@@ -2101,7 +2120,12 @@ __global__ __launch_bounds__(kBlock) void k_wave_coop(CoopArgs a) {
     for (int L = 0;; ++L) {
         if (!grid_sync()) return;   // level L's frontier (and its counter) is complete
         if (L < 4) CPROBE(2 + L);
+        // the cascade's boundary in the batch's records (RecSink): behind the first barrier the immediate
+        // roots have recorded and the fold has not begun (read beside the level's counter, not after it)
+        const bool mark = L == 0 && a.sink.rec && blockIdx.x == 0 && threadIdx.x == 0;
+        const unsigned long long cur = mark ? coh_read(a.sink.cur) : 0ull;
         if (threadIdx.x == 0) s_ft = coh_read(&ctr->lvl[L % kRing].ft);
+        if (mark) *a.sink.mark = cur + 1;
         __syncthreads();
         const uint64_t F = s_ft >> 32, T = s_ft & 0xFFFFFFFFull;
         if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -2229,6 +2253,25 @@ __global__ __launch_bounds__(kBlock) void k_wave_coop(CoopArgs a) {
     {
         const uint32_t W = blockDim.x >> 6;
         const uint64_t step = (uint64_t)gridDim.x * W * 64;
+        // The batch's record sink (RecSink): a wave stages its records in LDS (the chunk map's is free again:
+        // a 1,024-word tile per wave, as the listing above) and reserves output space with one atomic per
+        // kRecStage records or at its end. An atomic per step of the fold, its result awaited before the next
+        // step's loads, measured +9.0 against +4.6 us of cascade time a round on configs[4], where a few waves
+        // own a hub's consecutive leaves.
+        constexpr uint32_t kRecStage = kPullTile / 2;   // 8-byte records of a wave's tile: a step's most hits
+        static_assert(kRecStage == 8 * 64 && (kBlock / 64) * kPullTile <= kChunkEmitCap + 8, "a wave's record stage");
+        unsigned long long* st = reinterpret_cast<unsigned long long*>(s_x + wid * kPullTile);
+        uint32_t n_st = 0;   // wave-uniform
+        auto rec_flush = [&]() {
+            unsigned long long base = 0;
+            if (lane == 0) base = atomicAdd(a.sink.cur, (unsigned long long)n_st);
+            base = from_lane0(base);
+            __builtin_amdgcn_wave_barrier();
+            for (uint32_t i = lane; i < n_st; i += 64)
+                if (base + i < a.sink.cap) a.sink.rec[base + i] = st[i];
+            __builtin_amdgcn_wave_barrier();
+            n_st = 0;
+        };
         for (uint64_t w0 = ((uint64_t)blockIdx.x * W + wid) * 64; w0 < words; w0 += step) {   // wave-uniform
             const uint64_t w = w0 + lane;
             const unsigned long long mine = w < words ? vis64[w] : 0ull;
@@ -2249,8 +2292,32 @@ __global__ __launch_bounds__(kBlock) void k_wave_coop(CoopArgs a) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
                     if (m[j]) a.node[(w0 + idx[j]) * 64 + lane] = visited_word(nv[j]);
+                // The batch's record sink: a handle the cascade only flagged is one whose fold changes its word
+                // without invalidating it (old and new word are at hand). The hits of the eight words are
+                // balloted (the masks are scalars) and mbcnt ranks each word's hits into the wave's stage.
+                if (a.sink.rec) {   // uniform
+                    unsigned long long hb[8];
+                    uint32_t tot = 0;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const unsigned long long nw = visited_word(nv[j]);   // nv[j] is 0 where m[j] is not set
+                        hb[j] = __ballot(nw != nv[j] && word_state(nw) != FGI_INVALIDATED);
+                        tot += (uint32_t)__popcll(hb[j]);
+                    }
+                    if (tot) {   // wave-uniform; tot <= 8 * 64 = kRecStage
+                        if (n_st + tot > kRecStage) rec_flush();
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            if ((hb[j] >> lane) & 1ull)
+                                st[n_st + rank_in(hb[j])] =
+                                    rec_word(a.sink, (uint32_t)((w0 + idx[j]) * 64 + lane), visited_word(nv[j]));
+                            n_st += (uint32_t)__popcll(hb[j]);
+                        }
+                    }
+                }
             }
         }
+        if (n_st) rec_flush();   // wave-uniform; 0 without a sink
     }
     for (uint64_t w = lo + threadIdx.x; w < hi; w += blockDim.x)
         if (folded || w - lo >= kFinalStage || s_words[w - lo]) invw[w] = 0ull;
@@ -3203,7 +3270,7 @@ bool coop_launch_mode() {
 // out[*out_n ..). The wave folds its visits into the node words itself.
 fgi_status run_wave_coop(fgi_graph* g, uint32_t n_max, const uint32_t* roots_dev, const uint8_t* imm_dev,
                          const unsigned long long* n_dev, uint32_t* out, unsigned long long* out_n,
-                         unsigned long long* acc, unsigned long long* abort) {
+                         unsigned long long* acc, unsigned long long* abort, const RecSink* sink) {
     hipStream_t s = g->stream;
     FGI_TRY(ensure_cstart(g, std::max<uint64_t>(g->pool_top, g->pool_cap)));
     const bool coop = coop_launch_mode();
@@ -3279,6 +3346,7 @@ fgi_status run_wave_coop(fgi_graph* g, uint32_t n_max, const uint32_t* roots_dev
     a.one_round = one_round;
     a.fold = fold_args(g);
     a.ext_words = ((uint64_t)g->ext_handles + 63) / 64;
+    if (sink) a.sink = *sink;
     if (coop) {
 #if FGI_VARIANTS
         void* args[] = {&a};

@@ -146,6 +146,7 @@ SIGNATURES = {
     "fgi_part_local_invalidate": [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, _u32p, _u8p, C.POINTER(WaveStats)],
     "fgi_rccl_info": [C.POINTER(C.c_int), C.c_char_p, C.c_uint64],
     "fgi_run_batch": [_G, C.c_uint32, C.POINTER(Step), _u32p, C.c_uint64, _u64p, C.POINTER(BatchStats)],
+    "fgi_last_batch_flagged": [_G, _u32p, _u32p, _u32p, C.c_uint64, _u64p],
     "fgi_part_begin_compute": [_G, C.c_uint32, _u32p, _u64p, _u8p, _u32p, _u32p, C.c_uint64, _u64p,
                                C.POINTER(WaveStats)],
     "fgi_part_add_used": [_G, C.c_uint32, _u32p, _u32p, _u32p],
@@ -502,6 +503,18 @@ class Graph:
         self._check(self.lib.fgi_last_wave_flagged(self.h, _ptr(ids, C.c_uint32), _ptr(flags, C.c_uint32), len(ids),
                                                    C.byref(n)), "last_wave_flagged")
         return ids, flags
+
+    def last_batch_flagged(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """fgi_last_batch_flagged: (steps, handles, state_flags) of the nodes the last run_batch's cascades
+        flagged without invalidating them, cascade after cascade in step order, handles ascending within a
+        step. A streaming host starts its InvalidationDelay timers from the records carrying DelayStarted."""
+        n = C.c_uint64()
+        self._check(self.lib.fgi_last_batch_flagged(self.h, None, None, None, 0, C.byref(n)), "last_batch_flagged")
+        steps, ids, flags = (np.zeros(n.value, np.uint32) for _ in range(3))
+        self._check(self.lib.fgi_last_batch_flagged(self.h, _ptr(steps, C.c_uint32), _ptr(ids, C.c_uint32),
+                                                    _ptr(flags, C.c_uint32), len(ids), C.byref(n)),
+                    "last_batch_flagged")
+        return steps, ids, flags
 
     def wave_wait_flagged(self, ticket: int) -> Tuple[np.ndarray, np.ndarray]:
         """fgi_wave_wait_flagged: wait for the ticket's wave; its flagged (handles, state_flags), ascending."""
