@@ -447,7 +447,11 @@ fgi_status fgi_stream(fgi_graph* g, void** stream);
  *   FGI_OPT_FAULT_INJECT_TAIL [0] tests only: the same for the (k+1)-th wave tail (the persistent
  *                            launch that runs a wave's last small push levels, synchronous or
  *                            asynchronous waves): fgi_invalidate* / fgi_wave_wait return FGI_EDEVICE and
- *                            the graph is poisoned until fgi_restore */
+ *                            the graph is poisoned until fgi_restore
+ *   FGI_OPT_RUN_OFFSET_BITS [28] tests only: a pull candidate's record names its tail run by an offset
+ *                            below 2^bits words from its pull block's base; a candidate past that is
+ *                            found through the per-slot list offsets instead (tests pin that path on
+ *                            small graphs with 1..27; results never depend on it) */
 #define FGI_OPT_DEAD_FILTER 1
 #define FGI_OPT_DIRECTION 2
 #define FGI_OPT_PULL_ALPHA 3
@@ -462,6 +466,7 @@ fgi_status fgi_stream(fgi_graph* g, void** stream);
 #define FGI_OPT_PART_PLAN 13
 #define FGI_OPT_PART_BUCKET 14
 #define FGI_OPT_FAULT_INJECT_TAIL 16
+#define FGI_OPT_RUN_OFFSET_BITS 17
 /* 12 and 15: the measurement variants' options (include/fgi_variants.h); FGI_ENOTSUP here */
 fgi_status fgi_set_option(fgi_graph* g, int option, int64_t value);
 

@@ -132,6 +132,33 @@ constexpr int kFine = 256;              // edges per fine chunk of the chunk map
 constexpr uint32_t kStatBlocks = 8192;  // per-block statistics rows (grid limit of the hot kernels: 268M slots pull)
 constexpr int kStatCols = 8;
 constexpr int kPullTile = 1024;         // slots per pull tile (one block iteration of a pull level)
+// A pull candidate's record (16 B, fgi_graph::cand and the survivor buffers): words x and y below, then
+// the two list heads. x = slot relative to its pull block's first slot (15 bits: a block owns at most
+// 32 tiles) | tail flag (the list has more than two entries) << 15 | low 16 bits of the row length << 16;
+// y = high 4 bits of the row length | offset of the candidate's tail run from its block's base in
+// fgi_graph::trun, in words << 4. A row length of kRecLenEsc or more is stored as kRecLenEsc (read
+// row_len[slot] instead); a run at kRecNoOff words or more is stored as kRecNoOff (locate the list through
+// uin_len / uin_off instead).
+constexpr uint32_t kRecSlotBits = 15;
+constexpr uint32_t kRecLenEsc = (1u << 20) - 1;
+constexpr uint32_t kRecOffBits = 28;                      // FGI_OPT_RUN_OFFSET_BITS lowers the limit (tests)
+constexpr uint32_t kRecNoOff = (1u << kRecOffBits) - 1;
+__host__ __device__ inline void rec_encode(uint32_t rel, bool tail, uint32_t row_len, uint64_t run_off, uint64_t off_limit,
+                                           uint32_t& x, uint32_t& y) {
+    const uint32_t rl = row_len < kRecLenEsc ? row_len : kRecLenEsc;
+    const uint32_t ro = (tail && run_off < off_limit && run_off < kRecNoOff) ? (uint32_t)run_off : kRecNoOff;
+    x = rel | (tail ? 1u << kRecSlotBits : 0u) | (rl << 16);
+    y = (rl >> 16) | (ro << 4);
+}
+struct CandRec {
+    uint32_t rel;       // slot - the block's first slot
+    bool tail;          // the list has more than two entries
+    uint32_t row_len;   // kRecLenEsc: read row_len[slot]
+    uint32_t run_off;   // kRecNoOff: no inline offset
+};
+__host__ __device__ inline CandRec rec_decode(uint32_t x, uint32_t y) {
+    return CandRec{x & ((1u << kRecSlotBits) - 1), ((x >> kRecSlotBits) & 1u) != 0, (x >> 16) | ((y & 15u) << 16), y >> 4};
+}
 constexpr int kDoneGroups = 16;         // two-level completion counters (last-block epilogues)
 constexpr int kDoneStride = 16;         // 128 B apart
 #ifndef FGI_FINAL_BLOCKS
@@ -520,9 +547,15 @@ struct fgi_graph {
     // (slot, list heads, row length | more-than-two-entries bit << 31). A pull level reads the
     // static list (first pull of a wave) or the survivors of the previous pull level, and writes its
     // own survivors (still unvisited) into the other survivor buffer at the same segment bases.
-    // One 16-byte entry per candidate: {slot, row length | more << 31, head 0, head 1}.
+    // One 16-byte entry per candidate: rec_encode's two words, head 0, head 1.
     uint4* cand = nullptr;
     uint32_t* cand_seg = nullptr;      // [pull grid + 1]
+    // Tail runs: for each pull block, for each of its candidates with more than two list entries, in
+    // candidate order: [list length, entry 2, entry 3, ...] — what a queued candidate's scan reads, found
+    // from the record's offset alone (block b's runs start at run_seg[b]). Built with the candidates.
+    uint32_t* trun = nullptr;
+    uint64_t trun_cap = 0;
+    uint64_t* run_seg = nullptr;       // [pull grid + 1]
     uint32_t* wl = nullptr;            // [n_slots] a pull level's expandable winners, per block at cand_seg
     // Hot heads: the (at most kHot) handles that head the most lists get a rank; candidate entries
     // name them by a bit index past the bitmap's end (hot_w0), where a pull level finds a snapshot of their
@@ -552,6 +585,7 @@ struct fgi_graph {
     int opt_pull_alpha = 28;           // profiles/r2y_direction_sweep.jsonl: 28 beats 14 on configs[0] (-6%) and [1] (-1%)
     int opt_pull_tpb = 0;             // pull tiles per block (0: from the CU count; tests)
     int opt_hot_heads = 0;            // FGI_OPT_HOT_HEADS: cap on the hot heads (0: by graph size)
+    int opt_run_off_bits = (int)fgi::kRecOffBits;  // FGI_OPT_RUN_OFFSET_BITS: runs past 2^bits words take the uin_off path
     // probe summary: one bit per 64-bit word of the invalidated bitmap (set iff the word is nonzero),
     // built before a pull level while few words can be nonzero, so cold head and tail probes that
     // would miss are answered from an L2-resident table (FGI_OPT_PROBE_SUMMARY)

@@ -1207,26 +1207,63 @@ __device__ __forceinline__ uint32_t head_code(uint32_t h, const uint32_t* hot_ra
     return r != FGI_NONE ? (hot_bit0 + r) : h;
 }
 
+// words of slot d's tail run (fgi_graph::trun): its list's length and its entries past the two heads
+__global__ void k_run_words(uint32_t n, const uint32_t* __restrict__ uin_len, uint64_t* words) {
+    const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d < n) words[d] = uin_len[d] > 2 ? uin_len[d] - 1 : 0u;
+}
+
+// span = slots per pull block; rpos[d] = the run words of the slots before d
 __global__ void k_cand_fill(uint32_t n, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos,
                             const uint64_t* __restrict__ uin_head, const uint32_t* __restrict__ uin_len,
                             const uint32_t* __restrict__ row_len, const uint32_t* __restrict__ hot_rank,
-                            uint32_t hot_bit0, uint4* cand, unsigned long long* too_long) {
+                            uint32_t hot_bit0, uint32_t span, const uint64_t* __restrict__ rpos, uint64_t off_limit,
+                            uint4* cand, unsigned long long* too_long) {
     const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= n || !flag[d]) return;
     const uint32_t p = pos[d], rl = row_len[d];
     if (rl >> 31) atomicAdd(too_long, 1ull);
     const uint64_t h = uin_head[d];
-    cand[p] = make_uint4(d, (rl & 0x7FFFFFFFu) | (uin_len[d] > 2 ? 0x80000000u : 0u),
-                         head_code((uint32_t)h, hot_rank, hot_bit0), head_code((uint32_t)(h >> 32), hot_rank, hot_bit0));
+    const uint32_t rel = d % span;
+    uint32_t x, y;
+    rec_encode(rel, uin_len[d] > 2, rl, rpos[d] - rpos[d - rel], off_limit, x, y);
+    cand[p] = make_uint4(x, y, head_code((uint32_t)h, hot_rank, hot_bit0), head_code((uint32_t)(h >> 32), hot_rank, hot_bit0));
 }
 
-// segment base of pull block b: the candidates before its first slot b * tpb * kPullTile
+// segment bases of pull block b: the candidates, and the run words, before its first slot b * tpb * kPullTile
 __global__ void k_cand_seg(uint32_t G, uint64_t span, uint32_t n, const uint32_t* __restrict__ pos, uint32_t total,
-                           uint32_t* seg) {
+                           const uint64_t* __restrict__ rpos, uint64_t run_total, uint32_t* seg, uint64_t* run_seg) {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b > G) return;
     const uint64_t s0 = (uint64_t)b * span;
     seg[b] = s0 < n ? pos[s0] : total;
+    run_seg[b] = s0 < n ? rpos[s0] : run_total;
+}
+
+// The tail runs: slot d's [list length, entries 2..] at trun[rpos[d]]. A lane copies the first kRunOwn
+// entries of its own slot's list; the wave copies the rest of a longer list together.
+constexpr uint32_t kRunOwn = 32;
+__global__ void k_run_fill(uint32_t n, const uint32_t* __restrict__ uin_len, const uint64_t* __restrict__ uin_off,
+                           const uint32_t* __restrict__ uin_src, const uint64_t* __restrict__ rpos, uint32_t* trun) {
+    const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t len = d < n ? uin_len[d] : 0u;
+    unsigned long long off = 0, ro = 0;
+    if (len > 2) {
+        off = uin_off[d];
+        ro = rpos[d];
+        trun[ro] = len;
+    }
+    const uint32_t own = len > 2 ? (len < kRunOwn ? len : kRunOwn) : 0u;
+    for (uint32_t k = 2; k < own; ++k) trun[ro + k - 1] = uin_src[off + k];
+    unsigned long long m = __ballot(len > kRunOwn);
+    const uint32_t lane = threadIdx.x & 63;
+    while (m) {   // wave-uniform
+        const int l = __ffsll(m) - 1;
+        m &= m - 1;
+        const uint32_t ln = __shfl(len, l);
+        const unsigned long long o_s = __shfl(off, l), o_r = __shfl(ro, l);
+        for (uint32_t k = kRunOwn + lane; k < ln; k += 64) trun[o_r + k - 1] = uin_src[o_s + k];
+    }
 }
 
 __global__ void k_invalidate_all_roots(uint32_t n_slots, const unsigned long long* node, uint32_t* roots,
@@ -1501,6 +1538,7 @@ fgi_status build_candidates(fgi_graph* g) {
     }
     if (!g->cand_seg) {   // sized for the largest pull grid
         FGI_TRY(dmalloc(g, &g->cand_seg, (size_t)kStatBlocks + 1));
+        FGI_TRY(dmalloc(g, &g->run_seg, (size_t)kStatBlocks + 1));
         FGI_TRY(dmalloc(g, &g->sv_cnt[0], kStatBlocks));
         FGI_TRY(dmalloc(g, &g->sv_cnt[1], kStatBlocks));
     }
@@ -1518,6 +1556,30 @@ fgi_status build_candidates(fgi_graph* g) {
     FGI_TRY(d2h(g, &lp, pos + N - 1, 1));
     FGI_TRY(d2h(g, &lf, flag + N - 1, 1));
     const uint32_t total = lp + lf;
+    // the tail runs, in slot (= candidate) order
+    Tmp tw, tr, trs;
+    uint64_t *rwords, *rpos;
+    FGI_TRY(tmalloc(g, tw, &rwords, N));
+    FGI_TRY(tmalloc(g, tr, &rpos, N));
+    hipLaunchKernelGGL(k_run_words, dim3(nblk(N)), dim3(256), 0, s, N, g->uin_len, rwords);
+    size_t rb = 0;
+    FGI_HIP(g, rocprim::exclusive_scan(nullptr, rb, rwords, rpos, (uint64_t)0, (size_t)N, rocprim::plus<uint64_t>(), s));
+    char* rtmp;
+    FGI_TRY(tmalloc(g, trs, &rtmp, rb));
+    FGI_HIP(g, rocprim::exclusive_scan(rtmp, rb, rwords, rpos, (uint64_t)0, (size_t)N, rocprim::plus<uint64_t>(), s));
+    uint64_t rlp = 0, rlw = 0;
+    FGI_TRY(d2h(g, &rlp, rpos + N - 1, 1));
+    FGI_TRY(d2h(g, &rlw, rwords + N - 1, 1));
+    const uint64_t run_total = rlp + rlw;
+    if (g->trun_cap < run_total || !g->trun) {
+        dfree(g->trun);
+        g->trun = nullptr;
+        g->trun_cap = 0;
+        const uint64_t cap = std::max<uint64_t>(run_total, 1024);
+        FGI_TRY(dmalloc(g, &g->trun, cap + 2));   // a pull level reads three words of a two-word run
+        g->trun_cap = cap;
+    }
+    hipLaunchKernelGGL(k_run_fill, dim3(nblk(N)), dim3(256), 0, s, N, g->uin_len, g->uin_off, g->uin_src, rpos, g->trun);
     // hot heads (a partition's heads are global ids: ranked over all n_global slots, their snapshot
     // taken from the all-gathered invalidated bitmap)
     Tmp th;
@@ -1557,16 +1619,18 @@ fgi_status build_candidates(fgi_graph* g) {
     }
     FGI_HIP(g, hipMemsetAsync(g->misc_dev + 15, 0, sizeof(unsigned long long), s));
     hipLaunchKernelGGL(k_cand_fill, dim3(nblk(N)), dim3(256), 0, s, N, flag, pos, g->uin_head, g->uin_len, g->row_len,
-                       hot_rank, (uint32_t)(g->hot_w0 * 32), g->cand, g->misc_dev + 15);
-    hipLaunchKernelGGL(k_cand_seg, dim3(nblk(G + 1)), dim3(256), 0, s, G, (uint64_t)tpb * kPullTile, N, pos, total,
-                       g->cand_seg);
+                       hot_rank, (uint32_t)(g->hot_w0 * 32), tpb * (uint32_t)kPullTile, rpos,
+                       (uint64_t)1 << g->opt_run_off_bits, g->cand, g->misc_dev + 15);
+    hipLaunchKernelGGL(k_cand_seg, dim3(nblk(G + 1)), dim3(256), 0, s, G, (uint64_t)tpb * kPullTile, N, pos, total, rpos,
+                       run_total, g->cand_seg, g->run_seg);
     FGI_HIP(g, hipGetLastError());
     unsigned long long too_long = 0;
     FGI_TRY(d2h(g, &too_long, g->misc_dev + 15, 1));
     if (too_long == 0) g->cand_grid = G;
     if (getenv("FGI_TRACE"))
-        fprintf(stderr, "[fgi] candidates: %u of %u slots, pull grid %u x %u tiles, %u hot heads, %llu rows too long\n", total,
-                N, G, tpb, g->n_hot, (unsigned long long)too_long);
+        fprintf(stderr,
+                "[fgi] candidates: %u of %u slots, pull grid %u x %u tiles, %u hot heads, %llu rows too long, %llu tail-run words\n",
+                total, N, G, tpb, g->n_hot, (unsigned long long)too_long, (unsigned long long)run_total);
     return FGI_OK;
 }
 
@@ -1957,6 +2021,8 @@ fgi_status fgi_destroy(fgi_graph* g) {
     dfree(g->cand);
     dfree(g->wl);
     dfree(g->cand_seg);
+    dfree(g->run_seg);
+    dfree(g->trun);
     dfree(g->hot_id);
     for (int k = 0; k < 2; ++k) {
         dfree(g->sv[k]);
@@ -2439,6 +2505,17 @@ fgi_status fgi_set_option(fgi_graph* g, int option, int64_t value) {
         if (value < 0 || value > (int64_t)kHot) return set_err(g, FGI_EINVAL, "hot heads must be 0..%u", kHot);
         g->opt_hot_heads = (int)value;
         // the candidates' head codes depend on the hot set: rebuilt (as for FGI_OPT_PULL_TPB)
+        if (!g->part) {
+            g->uin_epoch = 0;
+        } else if (g->uin_src && g->uin_epoch == g->mut_epoch) {
+            hipSetDevice(g->device);
+            return build_candidates(g);
+        }
+        return FGI_OK;
+    case FGI_OPT_RUN_OFFSET_BITS:
+        if (value < 1 || value > (int64_t)kRecOffBits) return set_err(g, FGI_EINVAL, "run offset bits must be 1..%u", kRecOffBits);
+        g->opt_run_off_bits = (int)value;
+        // the candidates' records carry the offsets: rebuilt (as for FGI_OPT_PULL_TPB)
         if (!g->part) {
             g->uin_epoch = 0;
         } else if (g->uin_src && g->uin_epoch == g->mut_epoch) {

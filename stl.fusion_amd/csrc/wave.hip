@@ -1052,6 +1052,9 @@ struct PullArgs {
     uint32_t* wl;                            // per block (at its segment base): expandable winners
     unsigned long long* bsum;                // [3][grid] per-block sums, then [3][grid] prefixes
     const uint32_t* __restrict__ cand_seg;   // [grid + 1] segment bases
+    const uint32_t* __restrict__ trun;       // tail runs ([length, entries 2..] per tail-flagged candidate)
+    const uint64_t* __restrict__ run_seg;    // [grid + 1] a block's first run word
+    const uint32_t* __restrict__ row_len;    // a winner's row length past the record's field
     const uint4* c[3];                       // [0] the static candidates, [1 + k] survivors buffer k
     uint4* sv[2];
     uint32_t* sv_cnt[2];                     // [grid] survivors per block
@@ -1082,6 +1085,8 @@ constexpr uint32_t kCandBatch = kCPL * kBlock; // candidates per block step (kCP
 constexpr uint32_t kWaveBatch = kCPL * 64;     // a wave's run per step
 constexpr uint32_t kWaveTailCap = kTailCap / (kBlock / 64);   // queued candidates per wave
 constexpr uint32_t kLaneTail = 12;          // lists a lane scans alone in a tail pass (entries 4..11)
+static_assert(kMaxIter * kPullTile <= (1u << kRecSlotBits), "a candidate's record holds a block-relative slot");
+static_assert(kLaneTail < (1u << 15), "pass 2a's queue entry holds the list length above the candidate index");
 
 // visits / winners / classes of the owned tiles in LDS: 32-bit words (two lanes of a wave that
 // share a word serialise their atomics; narrower words halve how many do)
@@ -1129,29 +1134,51 @@ __device__ __forceinline__ bool front_bit(const PullArgs& p, uint32_t u, bool su
 }
 
 // an entry past the list reads as a dead candidate at the block's first slot
-__device__ __forceinline__ uint4 load_cand(const uint4* p, bool in, uint32_t s_lo) {
-    if (!in) return make_uint4(s_lo, 0u, FGI_NONE, FGI_NONE);
+__device__ __forceinline__ uint4 load_cand(const uint4* p, bool in) {
+    if (!in) return make_uint4(0u, 0u, FGI_NONE, FGI_NONE);
     const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-// one lane's hit (tails): visit bits, and a winner's sums and list entry
-__device__ __forceinline__ void pull_hit(const PullArgs& p, PullLds& s, uint64_t s_lo, uint64_t seg, uint32_t d, bool win,
-                                         uint32_t aux, WinSum& ws) {
-    const uint32_t rel = (uint32_t)(d - s_lo);
-    const uint32_t bit = 1u << (d & 31);
+// a candidate's row length: from its record, or (a row of kRecLenEsc entries or more) from the row table
+__device__ __forceinline__ uint32_t cand_row_len(const PullArgs& p, uint32_t d, const uint4& c) {
+    const uint32_t rl = rec_decode(c.x, c.y).row_len;
+    return rl == kRecLenEsc ? p.row_len[d] : rl;
+}
+
+// A tail-flagged candidate's list: its length, and lp with entry k (k >= 2) at lp[k - 1] — its run in the
+// block's tail runs (`run`), or, for a record without an offset, the dependency-list cache itself.
+__device__ __forceinline__ const uint32_t* list_at(const PullArgs& p, const uint32_t* run, uint32_t s_lo, const uint4& c,
+                                                   uint32_t& len) {
+    const uint32_t ro = rec_decode(c.x, c.y).run_off;
+    if (ro != kRecNoOff) {
+        len = run[ro];
+        return run + ro;
+    }
+    const uint32_t d = s_lo + rec_decode(c.x, c.y).rel;
+    len = p.uin_len[d];
+    return p.uin_src + p.uin_off[d] + 1;
+}
+
+// one lane's hit (tails): visit bits, and a winner's sums and list entry; true: a first-time flag
+__device__ __forceinline__ bool pull_hit(const PullArgs& p, PullLds& s, uint32_t s_lo, uint64_t seg, const uint4& c,
+                                         const unsigned long long* node, WinSum& ws) {
+    const uint32_t rel = rec_decode(c.x, c.y).rel, d = s_lo + rel;
+    const uint32_t bit = 1u << (rel & 31);
+    const bool win = (s.cs[rel >> 5] & bit) != 0;
     if (win) {
         atomicOr(&s.wm[rel >> 5], bit);
-        const uint32_t rl = aux & 0x7FFFFFFFu;
+        const uint32_t rl = cand_row_len(p, d, c);
         ++ws.w;
         if (rl) {
             ++ws.e;
             ws.l += rl;
             p.wl[seg + atomicAdd(&s.wn, 1u)] = d;
         }
-    } else {
-        atomicOr(&s.vm[rel >> 5], bit);
+        return false;
     }
+    atomicOr(&s.vm[rel >> 5], bit);
+    return first_visit(node[d]) == 2;
 }
 
 // A wave's queued candidates (both heads missed, the list goes on). Pass 1: one lane per candidate
@@ -1160,38 +1187,43 @@ __device__ __forceinline__ void pull_hit(const PullArgs& p, PullLds& s, uint64_t
 // all of entries 4.. in flight (configs[0]'s 8-entry lists of nodes two levels ahead: 64 per step
 // instead of 8). Pass 2b: the longer lists, 8 lanes per candidate over entries 4.. in steps of 8
 // (early exit); the next candidate's list is located while the current one is scanned. q (the wave's
-// queue of candidate indices) is reused for pass 2's lists (bit 31: longer than kLaneTail).
+// queue of candidate indices, below 2^15) is reused for pass 2's lists (bit 31: longer than kLaneTail;
+// a shorter list's length at bit 16). A candidate's list is found from its record (list_at): pass 1 reads
+// the run's length and entries 2 and 3 in one go — the run array is padded, so the word after a 3-entry
+// list's run can be read and dropped.
 __device__ __forceinline__ void pull_tails(const PullArgs& p, const uint4* src, uint4* sv_out, const unsigned long long* node,
-                                           uint64_t s_lo, uint64_t seg, uint32_t* q, uint32_t nq, PullLds& s,
-                                           uint32_t& flagged, uint32_t& examined, uint32_t& tails, WinSum& ws, bool sum) {
+                                           uint32_t s_lo, uint64_t seg, const uint32_t* run, uint32_t* q, uint32_t nq,
+                                           PullLds& s, uint32_t& flagged, uint32_t& examined, uint32_t& tails, WinSum& ws,
+                                           bool sum) {
     const uint32_t lane = lane_id();
     uint32_t nlong = 0;
     for (uint32_t r0 = 0; r0 < nq; r0 += 64) {   // wave-uniform
         const uint32_t e = r0 + lane;
         const bool in = e < nq;
-        uint32_t qi = 0, len = 0;
-        uint64_t off = 0;
+        uint32_t qi = 0, len = 0, u2 = FGI_NONE, u3 = FGI_NONE;
         uint4 c = make_uint4(0u, 0u, 0u, 0u);
         if (in) {
             qi = q[e];
             c = src[seg + qi];
-            len = p.uin_len[c.x];
-            off = p.uin_off[c.x];
+            const uint32_t ro = rec_decode(c.x, c.y).run_off;
+            if (ro != kRecNoOff) {
+                len = run[ro];
+                u2 = run[ro + 1];
+                const uint32_t t3 = run[ro + 2];
+                u3 = len > 3 ? t3 : FGI_NONE;
+            } else {
+                const uint32_t* lp = list_at(p, run, s_lo, c, len);
+                u2 = lp[1];
+                if (len > 3) u3 = lp[2];
+            }
         }
-        const uint32_t u2 = (in && len > 2) ? p.uin_src[off + 2] : FGI_NONE;
-        const uint32_t u3 = (in && len > 3) ? p.uin_src[off + 3] : FGI_NONE;
         const bool hit = (u2 != FGI_NONE && front_bit(p, u2, sum)) || (u3 != FGI_NONE && front_bit(p, u3, sum));
         examined += (u2 != FGI_NONE ? 1u : 0u) + (u3 != FGI_NONE ? 1u : 0u);
         const bool more = in && !hit && len > 4;
         const unsigned long long mm = __ballot(more);
-        if (more) q[nlong + rank_in(mm)] = qi | (len > kLaneTail ? 0x80000000u : 0u);   // below every entry still unread
+        if (more) q[nlong + rank_in(mm)] = qi | (len > kLaneTail ? 0x80000000u : len << 16);   // below every entry still unread
         nlong += (uint32_t)__popcll(mm);
-        if (in && hit) {
-            const uint32_t d = c.x, rel = (uint32_t)(d - s_lo);
-            const bool win = (s.cs[rel >> 5] >> (d & 31)) & 1u;
-            pull_hit(p, s, s_lo, seg, d, win, c.y, ws);
-            if (!win) flagged += first_visit(node[d]) == 2 ? 1u : 0u;
-        }
+        if (in && hit) flagged += pull_hit(p, s, s_lo, seg, c, node, ws) ? 1u : 0u;
         const bool surv = in && !hit && !more;
         const unsigned long long sm = __ballot(surv);
         if (sm) {
@@ -1215,15 +1247,15 @@ __device__ __forceinline__ void pull_tails(const PullArgs& p, const uint4* src, 
         nl2 += (uint32_t)__popcll(lm);
         uint4 c = make_uint4(0u, 0u, 0u, 0u);
         uint32_t len = 0;
-        uint64_t off = 0;
+        const uint32_t* lp = nullptr;
         if (in) {
-            c = src[seg + v];
-            len = p.uin_len[c.x];
-            off = p.uin_off[c.x];
+            c = src[seg + (v & 0xFFFFu)];
+            lp = list_at(p, run, s_lo, c, len);
+            len = v >> 16;   // as pass 1 read it
         }
         uint32_t u[kLaneTail - 4];
 #pragma unroll
-        for (uint32_t k = 0; k < kLaneTail - 4; ++k) u[k] = (in && 4 + k < len) ? p.uin_src[off + 4 + k] : FGI_NONE;
+        for (uint32_t k = 0; k < kLaneTail - 4; ++k) u[k] = (in && 4 + k < len) ? lp[3 + k] : FGI_NONE;
         bool found = false;
 #pragma unroll
         for (uint32_t k = 0; k < kLaneTail - 4; ++k)
@@ -1231,12 +1263,7 @@ __device__ __forceinline__ void pull_tails(const PullArgs& p, const uint4* src, 
                 found |= front_bit(p, u[k], sum);
                 ++examined;
             }
-        if (in && found) {
-            const uint32_t d = c.x, rel = (uint32_t)(d - s_lo);
-            const bool win = (s.cs[rel >> 5] >> (d & 31)) & 1u;
-            pull_hit(p, s, s_lo, seg, d, win, c.y, ws);
-            if (!win) flagged += first_visit(node[d]) == 2 ? 1u : 0u;
-        }
+        if (in && found) flagged += pull_hit(p, s, s_lo, seg, c, node, ws) ? 1u : 0u;
         const bool surv = in && !found;
         const unsigned long long sm = __ballot(surv);
         if (sm) {
@@ -1252,35 +1279,29 @@ __device__ __forceinline__ void pull_tails(const PullArgs& p, const uint4* src, 
     constexpr uint32_t G8 = 8;
     uint4 c_n = make_uint4(0u, 0u, 0u, 0u);
     uint32_t len_n = 0;
-    uint64_t off_n = 0;
+    const uint32_t* lp_n = nullptr;
     if (grp < nlong) {
         c_n = src[seg + q[grp]];
-        len_n = p.uin_len[c_n.x];
-        off_n = p.uin_off[c_n.x];
+        lp_n = list_at(p, run, s_lo, c_n, len_n);
     }
     for (uint32_t e = grp; e < nlong; e += G8) {
         const uint4 c = c_n;
         const uint32_t len = len_n;
-        const uint64_t off = off_n;
+        const uint32_t* lp = lp_n;
         if (e + G8 < nlong) {
             c_n = src[seg + q[e + G8]];
-            len_n = p.uin_len[c_n.x];
-            off_n = p.uin_off[c_n.x];
+            lp_n = list_at(p, run, s_lo, c_n, len_n);
         }
         bool found = false;
         for (uint32_t r = 4; r < len && !found; r += 8) {   // group-uniform
             const uint32_t k = r + sub;
-            const bool x = k < len && front_bit(p, p.uin_src[off + k], sum);
+            const bool x = k < len && front_bit(p, lp[k - 1], sum);
             examined += (k < len) ? 1u : 0u;
             found = ((__ballot(x) >> (lane & ~7u)) & 0xFFull) != 0;
         }
         if (sub == 0) {
-            const uint32_t d = c.x;
             if (found) {
-                const uint32_t rel = (uint32_t)(d - s_lo);
-                const bool win = (s.cs[rel >> 5] >> (d & 31)) & 1u;
-                pull_hit(p, s, s_lo, seg, d, win, c.y, ws);
-                if (!win) flagged += first_visit(node[d]) == 2 ? 1u : 0u;
+                flagged += pull_hit(p, s, s_lo, seg, c, node, ws) ? 1u : 0u;
             } else {
                 sv_out[atomicAdd(&s.sn, 1u)] = c;
             }
@@ -1306,12 +1327,13 @@ __device__ __forceinline__ void pull_level(int L, const PullArgs& p, const WaveP
     const uint32_t cnt = npull == 0 ? seg_n : min(p.sv_cnt[sid - 1][b], seg_n);
     uint4* const sv_out = p.sv[dst] + seg;     // this level's survivors (the block's segment)
     uint32_t* const wl_out = p.wl + seg;       // this level's expandable winners
+    const uint32_t* const run = p.trun + p.run_seg[b];   // the block's tail runs
     // the first batch's entries are requested before the owned words are staged
     uint4 c[kCPL];
 #pragma unroll
     for (int j = 0; j < (int)kCPL; ++j) {
         const uint32_t i = (threadIdx.x >> 6) * kWaveBatch + j * 64 + lane;
-        c[j] = load_cand(src + seg + i, i < cnt, (uint32_t)s_lo);
+        c[j] = load_cand(src + seg + i, i < cnt);
     }
     {
         // every word's loads are issued before the first LDS store (one memory round trip, not one
@@ -1364,8 +1386,8 @@ __device__ __forceinline__ void pull_level(int L, const PullArgs& p, const WaveP
 #pragma unroll
         for (int j = 0; j < (int)kCPL; ++j) {
             const bool in = base + j * 64 + lane < cnt;
-            const uint32_t rel = c[j].x - (uint32_t)s_lo;
-            lv[j] = in && !((s.vm[rel >> 5] >> (c[j].x & 31)) & 1u);
+            const uint32_t rel = rec_decode(c[j].x, c[j].y).rel;
+            lv[j] = in && !((s.vm[rel >> 5] >> (rel & 31)) & 1u);
             f0[j] = lv[j] ? head_bits(p, s, c[j].z, sum) : 0u;
             f1[j] = (lv[j] && c[j].w != FGI_NONE) ? head_bits(p, s, c[j].w, sum) : 0u;
         }
@@ -1374,27 +1396,27 @@ __device__ __forceinline__ void pull_level(int L, const PullArgs& p, const WaveP
 #pragma unroll
         for (int j = 0; j < (int)kCPL; ++j) {
             const uint32_t i = base + kCandBatch + j * 64 + lane;
-            cn[j] = load_cand(src + seg + i, i < cnt, (uint32_t)s_lo);
+            cn[j] = load_cand(src + seg + i, i < cnt);
         }
 #pragma unroll
         for (int j = 0; j < (int)kCPL; ++j) {
             const uint32_t i = base + j * 64 + lane;
-            const uint32_t d = c[j].x, h0 = c[j].z, h1 = c[j].w, aux = c[j].y;
+            const uint32_t rel = rec_decode(c[j].x, c[j].y).rel, d = (uint32_t)s_lo + rel, h0 = c[j].z, h1 = c[j].w;
             const bool b0 = lv[j] && ((f0[j] >> (h0 & 31)) & 1u);
             const bool b1 = lv[j] && h1 != FGI_NONE && ((f1[j] >> (h1 & 31)) & 1u);
             const bool hit = b0 || b1;
-            const bool tail = lv[j] && !hit && (aux >> 31);
+            const bool tail = lv[j] && !hit && rec_decode(c[j].x, c[j].y).tail;
             const bool surv = lv[j] && !hit && !tail;
             live += lv[j] ? 1u : 0u;
             examined += (lv[j] ? 1u : 0u) + ((lv[j] && h1 != FGI_NONE && !b0) ? 1u : 0u);
             bool win = false;
+            uint32_t rl = 0;
             if (hit) {
-                const uint32_t rel = d - (uint32_t)s_lo;
-                const uint32_t bit = 1u << (d & 31);
+                const uint32_t bit = 1u << (rel & 31);
                 win = (s.cs[rel >> 5] & bit) != 0;
                 if (win) {   // a winner's visit bit is folded in from wm at the write-back
                     atomicOr(&s.wm[rel >> 5], bit);
-                    const uint32_t rl = aux & 0x7FFFFFFFu;
+                    rl = cand_row_len(p, d, c[j]);
                     ++ws.w;
                     ws.e += rl ? 1u : 0u;
                     ws.l += rl;
@@ -1403,7 +1425,7 @@ __device__ __forceinline__ void pull_level(int L, const PullArgs& p, const WaveP
                     flagged += first_visit(node[d]) == 2 ? 1u : 0u;
                 }
             }
-            const bool xw = win && (aux & 0x7FFFFFFFu);
+            const bool xw = win && rl;
             const unsigned long long xm = __ballot(xw);
             if (xm) {
                 uint32_t xb = 0;
@@ -1426,7 +1448,7 @@ __device__ __forceinline__ void pull_level(int L, const PullArgs& p, const WaveP
         if (base + kCandBatch >= cnt) PROBE(L, 7);
         if (qn > kWaveTailCap - kWaveBatch || base + kCandBatch >= cnt) {
             __builtin_amdgcn_wave_barrier();
-            pull_tails(p, src, sv_out, node, s_lo, seg, wq, qn, s, flagged, examined_tail, tails, ws,
+            pull_tails(p, src, sv_out, node, (uint32_t)s_lo, seg, run, wq, qn, s, flagged, examined_tail, tails, ws,
                        sum);
             __builtin_amdgcn_wave_barrier();
             qn = 0;
@@ -2988,6 +3010,9 @@ PullArgs pull_args(fgi_graph* g, uint32_t n_slots, const uint32_t* front_rd) {
     p.cls = g->cls_bm;
     p.bsum = g->bsum;
     p.cand_seg = g->cand_seg;
+    p.trun = g->trun;
+    p.run_seg = g->run_seg;
+    p.row_len = g->row_len;
     p.c[0] = g->cand;
     for (int k = 0; k < 2; ++k) {
         p.c[1 + k] = g->sv[k];

@@ -30,6 +30,7 @@ OPT_PART_PLAN = 13
 OPT_PART_BUCKET = 14
 OPT_FAULT_INJECT_TAIL = 16
 OPT_PROBE_SUMMARY = 15
+OPT_RUN_OFFSET_BITS = 17
 DIR_AUTO, DIR_PUSH, DIR_PULL = 0, 1, 2
 NONE = 0xFFFFFFFF
 COMPUTING, CONSISTENT, INVALIDATED = 0, 1, 2
