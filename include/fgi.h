@@ -272,7 +272,8 @@ fgi_status fgi_last_wave_ids(fgi_graph* g, uint32_t* out_ids, uint64_t cap, uint
  * handle names the new node when the call returns; the displaced node is out_detached[i]). FGI_ECAPACITY
  * with *out_n set if cap is short; out_ids NULL = count only. Valid until the next call that runs a wave.
  * After fgi_run_batch: FGI_ENOTSUP (a batch's cascades report through fgi_last_batch_flagged); after any
- * fgi_part_* call: FGI_ENOTSUP (their cascades report no flagged sets).
+ * fgi_part_* call, and on any partitioned graph: FGI_ENOTSUP (a partition's cascades report through
+ * fgi_part_last_flagged, rank by rank).
  * A graph that never held a Computing node or one with hasDelay reports empty sets at no cost: its waves
  * launch nothing for them. */
 fgi_status fgi_last_wave_flagged(fgi_graph* g, uint32_t* out_ids, uint32_t* out_flags, uint64_t cap, uint64_t* out_n);
@@ -356,7 +357,8 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
  * the batch copies them (one device-to-host copy, one wait). Valid until the next call that runs a wave or
  * a batch, or fgi_restore. After a batch that failed with FGI_ECAPACITY at step k (out of detached
  * handles): the cascades of the steps before k. FGI_ENOTSUP if the last call that ran cascades was not
- * fgi_run_batch, and after any fgi_part_* call; FGI_ESTATE on a poisoned graph. A graph that never held a
+ * fgi_run_batch, and on a partitioned graph (fgi_part_run_batch reports through fgi_part_last_flagged);
+ * FGI_ESTATE on a poisoned graph. A graph that never held a
  * Computing node or one with hasDelay reports empty sets at no cost: its batches allocate and launch
  * nothing for them (the records take 16 bytes of device memory per handle otherwise). */
 fgi_status fgi_last_batch_flagged(fgi_graph* g, uint32_t* out_step, uint32_t* out_ids, uint32_t* out_flags,
@@ -557,6 +559,30 @@ fgi_status fgi_part_local_run_batch(fgi_graph* const* gs, uint32_t p, uint32_t n
                                     uint32_t* out_ids, uint64_t cap, uint64_t* out_n,
                                     fgi_batch_stats* stats /*p entries*/);
 fgi_status fgi_part_local_prune(fgi_graph* const* gs, uint32_t p, fgi_prune_stats* stats /*p entries*/);
+/* This rank's share of the flagged sets of the last fgi_part_* call that ran cascades (C-ABI 0.4): the
+ * partitioned counterpart of fgi_last_wave_flagged and fgi_last_batch_flagged, from which a multi-GPU host
+ * starts its invalidation-delay timers.
+ * A call of one cascade (fgi_part_invalidate, fgi_part_begin_compute, fgi_part_set_output,
+ * fgi_part_invalidate_all, each rank of fgi_part_local_invalidate) reports one run, out_step[i] = 0.
+ * fgi_part_run_batch (each rank of fgi_part_local_run_batch) reports cascade after cascade in step order,
+ * out_step[i] = the step's index, under fgi_last_batch_flagged's contract: a slot may appear under several
+ * steps, and a begin_compute step's own slots are not listed under that step.
+ * A cascade's set is fgi_last_wave_flagged's, restricted to the slots this rank owns: every owned slot whose
+ * canonical state_flags gained FGI_F_INVALIDATE_ON_SET_OUTPUT and / or FGI_F_INVALIDATION_DELAY_STARTED
+ * during the cascade and that the cascade did not invalidate, whatever the visit order and whichever rank
+ * the visit came from. out_ids are global slot ids in the host's numbering (partition codes mapped back),
+ * ascending within a step; out_flags[i] = the node's canonical state_flags right after that cascade.
+ * Detached handles cannot occur: a partition's roots are slots, and no edge resolves to a detached node.
+ * out_step and out_flags are nullable; out_ids NULL = count only; FGI_ECAPACITY with *out_n set if cap is
+ * short. The cascades wait for nothing and copy nothing for this: the records stay on the device and the
+ * rank's first call after them waits and copies once. No collective runs: each rank asks for itself, at
+ * any time, in any order. Valid until this rank's next fgi_part_* call that runs a cascade. After
+ * fgi_restore, and before any cascade has run: FGI_OK with 0 records. FGI_ENOTSUP on a graph that is not
+ * partitioned; FGI_ESTATE on a poisoned graph. A partition that never held a Computing node or one with
+ * hasDelay reports empty sets at no cost: its waves allocate and launch nothing for them (the records take
+ * 16 bytes of device memory per local handle otherwise). */
+fgi_status fgi_part_last_flagged(fgi_graph* g, uint32_t* out_step, uint32_t* out_ids, uint32_t* out_flags,
+                                 uint64_t cap, uint64_t* out_n);
 /* Frontier exchanges of a partition rank so far (full all-gathers, delta exchanges) and the bytes it
  * received through them (FGI_OPT_FRONT_EXCHANGE). */
 fgi_status fgi_part_front_stats(fgi_graph* g, uint64_t* full, uint64_t* delta, uint64_t* bytes);

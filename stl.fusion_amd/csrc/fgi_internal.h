@@ -661,6 +661,30 @@ struct fgi_graph {
     int opt_part_plan = 1;             // FGI_OPT_PART_PLAN
 
     std::string err;
+
+    // (behind every older member: their places in the struct stay what they were)
+    // The flagged sets of a partition's last call that ran cascades (fgi_part_last_flagged):
+    // this rank's share. Every cascade of the call (run_part_wave) queues k_flag_list's partition
+    // instantiation behind its last final collect; it appends to prec (global slot << 32 | canonical
+    // state_flags) through one device cursor, pcur[0], which the call clears once and no cascade resets.
+    // After cascade k's post-pass the cursor is copied to pcur[1 + k] on the device, so run k is the
+    // records [pcur[k], pcur[1 + k]) (pcur[0] read as 0). Nothing waits: the accessor downloads the cursor,
+    // the marks and the records on its first call, sorts each run, drops a begin_compute step's own slots
+    // (PartRun::drop, host numbering) and caches the result. pflg_batch: fgi_part_run_batch is running,
+    // which opened the call itself (part_flagged_begin) and numbers the cascades by pflg_step.
+    unsigned long long* prec = nullptr;
+    uint64_t prec_cap = 0;
+    unsigned long long* pcur = nullptr;   // [1 + pcur_cap]
+    uint64_t pcur_cap = 0;
+    struct PartRun {
+        uint32_t step = 0;
+        std::vector<uint32_t> drop;    // sorted
+    };
+    std::vector<PartRun> pflg_runs;
+    std::vector<uint32_t> pflg_steps;  // the accessor's cache: step, then global slot << 32 | state_flags
+    std::vector<uint64_t> pflg_set;
+    bool pflg_read = false, pflg_batch = false;
+    uint32_t pflg_step = 0;
 };
 
 // ---- internal entry points shared between translation units ----------------------------------
@@ -863,6 +887,11 @@ fgi_status part_ensure_lists(fgi_graph* g);
 // Partitioned wave over global root ids (wave.hip): run_part_wave drives the phases below.
 fgi_status run_part_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, const uint8_t* imm_dev,
                          fgi_wave_stats* stats);
+// Opens a partitioned call's flagged records (fgi_part_last_flagged): forgets the previous call's, and on a
+// graph that can flag sizes the record buffer for 2 * (n_handles + extra) records and `cascades` marks
+// and clears the cursor. run_part_wave opens a call of one cascade itself; fgi_part_run_batch opens its
+// own (pflg_batch) with its begin_compute entries as `extra`.
+fgi_status part_flagged_begin(fgi_graph* g, uint64_t cascades, uint64_t extra);
 // Append (used, dependant slot, tag) entries to rows (set semantics, no state checks).
 fgi_status append_edges(fgi_graph* g, uint64_t m, const uint32_t* used_dev, const uint32_t* dep_dev,
                         const uint64_t* tag_dev, const uint32_t* dep_handle_dev);

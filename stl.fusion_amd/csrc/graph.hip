@@ -1899,7 +1899,8 @@ extern "C" {
 
 fgi_status fgi_version(uint32_t* major, uint32_t* minor) {
     if (major) *major = 0;
-    if (minor) *minor = 3;   // 0.2: fgi_last_wave_flagged, fgi_wave_wait_flagged; 0.3: fgi_last_batch_flagged
+    // 0.2: fgi_last_wave_flagged, fgi_wave_wait_flagged; 0.3: fgi_last_batch_flagged; 0.4: fgi_part_last_flagged
+    if (minor) *minor = 4;
     return FGI_OK;
 }
 
@@ -2034,6 +2035,8 @@ fgi_status fgi_destroy(fgi_graph* g) {
     if (g->flg_cnt) (void)hipFree(g->flg_cnt);
     for (int k = 0; k < 2; ++k)
         if (g->flg_out[k]) (void)hipFree(g->flg_out[k]);
+    if (g->prec) (void)hipFree(g->prec);
+    if (g->pcur) (void)hipFree(g->pcur);
     dfree(g->cls_bm);
     dfree(g->uin_more);
     dfree(g->sum_bm);
@@ -2436,6 +2439,10 @@ fgi_status fgi_restore(fgi_graph* g) {
     g->flag_gate = g->snap_flag_gate;
     g->flg_last = -1;
     g->flg_drop.clear();
+    g->pflg_runs.clear();   // a partition's records too (fgi_part_last_flagged: 0 records)
+    g->pflg_steps.clear();
+    g->pflg_set.clear();
+    g->pflg_read = false;
     // the visit bits are forgotten: the clean spare bitmap takes the visit bitmap's place, and the next
     // wave's list kernel clears the old one; without a clean spare, the next wave's init kernel clears it
     // (or flush_vis before any other use)
@@ -2731,7 +2738,7 @@ fgi_status fgi_last_wave_flagged(fgi_graph* g, uint32_t* out_ids, uint32_t* out_
     FGI_TRY(usable(g));
     if (g->part || g->flg_last == -2)
         return set_err(g, FGI_ENOTSUP, "fgi_last_wave_flagged: the cascades of fgi_run_batch report through "
-                                       "fgi_last_batch_flagged, those of the fgi_part_* calls report no flagged sets");
+                                       "fgi_last_batch_flagged, those of the fgi_part_* calls through fgi_part_last_flagged");
     hipSetDevice(g->device);
     std::vector<uint64_t> set;
     FGI_TRY(read_flagged(g, g->flg_last, false, &set));
@@ -2744,7 +2751,7 @@ fgi_status fgi_wave_wait_flagged(fgi_graph* g, uint64_t ticket, uint32_t* out_id
     FGI_TRY(usable_now(g));
     if (g->part || g->flg_last == -2)
         return set_err(g, FGI_ENOTSUP, "fgi_wave_wait_flagged: the cascades of fgi_run_batch report through "
-                                       "fgi_last_batch_flagged, those of the fgi_part_* calls report no flagged sets");
+                                       "fgi_last_batch_flagged, those of the fgi_part_* calls through fgi_part_last_flagged");
     hipSetDevice(g->device);
     FGI_TRY(wave_wait(g, ticket, nullptr, nullptr, nullptr));
     // the ticket's buffer is its own until the wave two tickets later is queued (as its ids); a blocking
@@ -3838,7 +3845,15 @@ fgi_status part_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, co
     // the displacement cascade (ComputedRegistry.cs:91-94) on every rank, then versions and installs
     if (cnt[0]) hipLaunchKernelGGL(k_add_base, dim3(nblk(cnt[0])), dim3(256), 0, st, (uint32_t)cnt[0], droots, pv.base);
     g->last_wave_n = 0;
+    g->flag_gate = true;   // Computing nodes from here on (flagged sets), on every rank alike
     FGI_TRY(run_part_wave(g, (uint32_t)cnt[0], droots, nullptr, stats));
+    // the call's slots hold new nodes when it returns: a node the displacement cascade flagged under one of
+    // them is not in the cascade's set (fgi_begin_compute's rule); kept as the host numbers the slots
+    if (!g->pflg_runs.empty()) {
+        std::vector<uint32_t>& drop = g->pflg_runs.back().drop;
+        for (uint32_t j = 0; j < m; ++j) drop.push_back(part_slot_of(g, ls[j] + pv.base));
+        std::sort(drop.begin(), drop.end());
+    }
     FGI_TRY(part_take_ids(g, pv, ids));
     if (n) {
         uint32_t* as = nullptr;
@@ -4110,9 +4125,33 @@ fgi_status fgi_part_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* st
                 if (sp.version[i] == 0 || sp.version[i] > kVMask)
                     return set_err(g, FGI_EINVAL, "step %u: bad version (%u)", k, i);
     }
+    // The batch's flagged records (fgi_part_last_flagged): one buffer and one cursor for all its cascades,
+    // sized before anything is queued. begin_compute steps open the gate up front, so the cascades of the
+    // steps before them report too, as fgi_run_batch's do. A batch without a cascade keeps the last call's.
+    uint64_t n_casc = 0, n_begin = 0, own_begin = 0;
+    for (uint32_t k = 0; k < n_steps; ++k) {
+        const fgi_step& sp = steps[k];
+        if (sp.kind != FGI_STEP_ADD_USED) ++n_casc;
+        if (sp.kind != FGI_STEP_BEGIN_COMPUTE) continue;
+        n_begin += sp.n;
+        std::vector<uint32_t> mh;
+        const uint32_t* h = part_codes_in(g, sp.n, sp.handles, mh);
+        for (uint32_t i = 0; i < sp.n; ++i) own_begin += (h[i] - pv.base < pv.n_local) ? 1 : 0;
+    }
+    if (n_begin) g->flag_gate = true;
+    struct BatchScope {
+        fgi_graph* g;
+        ~BatchScope() { g->pflg_batch = false; }
+    } scope{g};
+    if (n_casc) {
+        hipSetDevice(g->device);
+        FGI_TRY(part_flagged_begin(g, n_casc, own_begin));
+        g->pflg_batch = true;
+    }
     std::vector<uint32_t> ids;
     fgi_wave_stats ws{};
     for (uint32_t k = 0; k < n_steps; ++k) {
+        g->pflg_step = k;
         fgi_step sp = steps[k];   // its slots as codes (partition codes)
         std::vector<uint32_t> mh, mu;
         sp.handles = part_codes_in(g, sp.n, sp.handles, mh);
@@ -4153,6 +4192,57 @@ fgi_status fgi_part_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* st
         stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     return part_copy_ids(g, ids, out_ids, cap, out_n);
+}
+
+// The call's cascades left their records on the device (pflg_runs): the first call waits for the post-passes,
+// copies the cursor, the marks and the records once, sorts each run by slot and drops a begin_compute step's
+// own slots. No collective: every rank reads its own share.
+fgi_status fgi_part_last_flagged(fgi_graph* g, uint32_t* out_step, uint32_t* out_ids, uint32_t* out_flags, uint64_t cap,
+                                 uint64_t* out_n) {
+    if (!g) return FGI_EINVAL;
+    FGI_TRY(usable(g));
+    if (!g->part)
+        return set_err(g, FGI_ENOTSUP, "fgi_part_last_flagged: not a partitioned graph (fgi_last_wave_flagged, "
+                                       "fgi_wave_wait_flagged and fgi_last_batch_flagged report a single device's cascades)");
+    if (!g->pflg_read) {
+        const uint64_t nr = g->pflg_runs.size();
+        if (nr) {
+            hipSetDevice(g->device);
+            std::vector<uint64_t> marks(1 + nr);
+            FGI_TRY(d2h(g, marks.data(), reinterpret_cast<const uint64_t*>(g->pcur), 1 + nr));
+            const uint64_t total = marks[0];
+            if (total > g->prec_cap)   // writes were clamped: no truncated set is returned
+                return set_err(g, FGI_EDEVICE, "the call's cascades flagged %llu nodes, their buffer holds %llu",
+                               (unsigned long long)total, (unsigned long long)g->prec_cap);
+            std::vector<uint64_t> raw(total);
+            FGI_TRY(d2h(g, raw.data(), reinterpret_cast<const uint64_t*>(g->prec), total));
+            uint64_t lo = 0;
+            for (uint64_t k = 0; k < nr; ++k) {
+                const fgi_graph::PartRun& r = g->pflg_runs[k];
+                const uint64_t hi = marks[1 + k];
+                if (hi < lo || hi > total) return set_err(g, FGI_EDEVICE, "flagged records: run %llu ends out of order", (unsigned long long)k);
+                std::sort(raw.begin() + (ptrdiff_t)lo, raw.begin() + (ptrdiff_t)hi);   // by slot: the high half
+                for (uint64_t i = lo; i < hi; ++i) {
+                    if (std::binary_search(r.drop.begin(), r.drop.end(), (uint32_t)(raw[i] >> 32))) continue;
+                    g->pflg_steps.push_back(r.step);
+                    g->pflg_set.push_back(raw[i]);
+                }
+                lo = hi;
+            }
+        }
+        g->pflg_read = true;
+    }
+    const uint64_t n = g->pflg_set.size();
+    if (out_n) *out_n = n;
+    if (!out_ids) return FGI_OK;
+    if (n > cap) return set_err(g, FGI_ECAPACITY, "the call's flagged sets hold %llu slots, the buffer %llu",
+                                (unsigned long long)n, (unsigned long long)cap);
+    for (uint64_t i = 0; i < n; ++i) {
+        out_ids[i] = (uint32_t)(g->pflg_set[i] >> 32);
+        if (out_step) out_step[i] = g->pflg_steps[i];
+        if (out_flags) out_flags[i] = (uint32_t)g->pflg_set[i];
+    }
+    return FGI_OK;
 }
 
 }  // extern "C"

@@ -1901,6 +1901,11 @@ fgi_status fgi_part_register_nodes(fgi_graph* g, uint32_t n, const uint32_t* slo
         if (state_flags && (state_flags[i] & 3u) == 3u) return set_err(g, FGI_EINVAL, "bad state for slot %u", slot[i]);
     }
     if (n == 0) return FGI_OK;
+    // a Computing node, or one with an invalidation delay, can be flagged by a visit (flagged sets). Any
+    // listed node counts, owned or not: every rank sees the same list, so every rank decides alike.
+    for (uint32_t i = 0; i < n && state_flags && !g->flag_gate; ++i)
+        if (version[i] && ((state_flags[i] & FGI_STATE_MASK) == FGI_COMPUTING || (state_flags[i] & FGI_F_HAS_DELAY)))
+            g->flag_gate = true;
     std::vector<uint32_t> mapped;
     slot = part_codes_in(g, n, slot, mapped);   // partition codes
     hipSetDevice(g->device);

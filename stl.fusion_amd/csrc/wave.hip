@@ -2786,14 +2786,20 @@ struct FlagArgs {
     const unsigned long long* inv64;
     uint64_t words;                    // 64-bit words of the bitmaps
     const unsigned long long* node;
-    const uint32_t* l2s;               // hot label -> slot (labels below K)
-    uint32_t K;
+    const uint32_t* l2s;               // hot label -> slot (labels below K); kPart: code -> slot, null without codes
+    uint32_t K;                        // kPart: the rank's base
+    uint32_t n_own;                    // kPart: the rank's slots (local indices from there on are detached handles)
     unsigned long long* out;           // handle << 32 | canonical state_flags
     unsigned long long* cnt;
     uint64_t cap;                      // entries of out (n_handles: the set cannot hold more)
 };
 
-__global__ __launch_bounds__(kBlock) void k_flag_list(FlagArgs a) {
+// kPart: a rank of a partition (fgi_part_last_flagged). The bitmaps run over the rank's local indices; a hit at
+// l is written as the host's global slot: l2s[K + l] when the partition has codes (l2s = the code -> slot
+// table, K = the rank's base), else K + l. Local indices from n_own on are detached handles, which no edge
+// resolves to: their bits are not listed. cnt is the call's cursor: a batch's cascades append.
+template <bool kPart>
+__device__ __forceinline__ void flag_list(const FlagArgs& a) {
     const uint32_t lane = lane_id();
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
@@ -2806,6 +2812,10 @@ __global__ __launch_bounds__(kBlock) void k_flag_list(FlagArgs a) {
             if (hit) {
                 e = hit & ~a.inv64[x];
                 a.flg64[x] = f & ~hit;
+                if (kPart) {
+                    const uint64_t lo = x * 64;
+                    if (lo + 64 > a.n_own) e = lo >= a.n_own ? 0ull : e & ((1ull << (a.n_own - lo)) - 1ull);
+                }
             }
         }
         uint32_t total = (uint32_t)__popcll(e);
@@ -2824,13 +2834,19 @@ __global__ __launch_bounds__(kBlock) void k_flag_list(FlagArgs a) {
                 const uint32_t l = (uint32_t)((w0 + (uint64_t)src) * 64 + lane);
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
                 const unsigned long long o = base + rank;
-                const uint32_t id = l < a.K ? a.l2s[l] : l - a.K;
+                const uint32_t id = kPart ? (a.l2s ? a.l2s[a.K + l] : a.K + l) : (l < a.K ? a.l2s[l] : l - a.K);
                 if (o < a.cap) a.out[o] = ((unsigned long long)id << 32) | word_to_flags(visited_word(a.node[l]));
             }
             base += (unsigned long long)__popcll(b);
         }
     }
 }
+
+__global__ __launch_bounds__(kBlock) void k_flag_list(FlagArgs a) { flag_list<false>(a); }
+// The partition instantiation beside it. A template only so that its code is emitted where it is first used
+// (launch_part_flagged), behind every other kernel of this file: the code object keeps the others where they were.
+template <bool kPart>
+__global__ __launch_bounds__(kBlock) void k_flag_list_part(FlagArgs a) { flag_list<kPart>(a); }
 
 }  // namespace
 
@@ -3846,6 +3862,7 @@ static fgi_status launch_flagged(fgi_graph* g, int k) {
                      reinterpret_cast<const unsigned long long*>(g->node),
                      g->l2s,
                      g->lbl_K,
+                     0u,
                      g->flg_out[k],
                      g->flg_cnt + k,
                      (uint64_t)g->n_handles};
@@ -4356,6 +4373,67 @@ static fgi_status launch_part_level(fgi_graph* g, const PartView& pv, const Part
     return FGI_OK;   // the caller checks the launches with its own that follow
 }
 
+// Queues the flagged-set post-pass of this rank behind a partitioned wave's last final collect (flag_gate;
+// fgi_part_last_flagged) and marks the run's end: an 8-byte device copy of the cursor. Nothing waits. The
+// wave began with k_wave_init and its final collect left the invalidated bitmap intact. A planned wave
+// calls this after its last round only: an earlier post-pass would clear flaggable bits that a later
+// round's visits still need, and list nodes a later round invalidates.
+static fgi_status launch_part_flagged(fgi_graph* g, const PartView& pv) {
+    hipStream_t s = g->stream;
+    const uint64_t k = g->pflg_runs.size();
+    if (!g->prec || !g->pcur || k >= g->pcur_cap)
+        return set_err(g, FGI_ESTATE, "a partitioned cascade's flagged records were not opened (%llu runs)", (unsigned long long)k);
+    const uint64_t words = ((uint64_t)pv.n_local + 63) / 64;
+    const FlagArgs a{reinterpret_cast<unsigned long long*>(g->flg_bm),
+                     reinterpret_cast<const unsigned long long*>(g->vis_bm),
+                     reinterpret_cast<const unsigned long long*>(g->inv_bm),
+                     words,
+                     reinterpret_cast<const unsigned long long*>(g->node),
+                     g->lbl_perm ? g->pg_ig : (const uint32_t*)nullptr,
+                     pv.base,
+                     pv.n_local,
+                     g->prec,
+                     g->pcur,
+                     g->prec_cap};
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, (words + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(k_flag_list_part<true>, dim3(grid), dim3(kBlock), 0, s, a);
+    FGI_HIP(g, hipGetLastError());
+    FGI_HIP(g, hipMemcpyAsync(g->pcur + 1 + k, g->pcur, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    fgi_graph::PartRun r;
+    r.step = g->pflg_step;
+    g->pflg_runs.push_back(std::move(r));
+    return FGI_OK;
+}
+
+fgi_status part_flagged_begin(fgi_graph* g, uint64_t cascades, uint64_t extra) {
+    g->pflg_runs.clear();
+    g->pflg_steps.clear();
+    g->pflg_set.clear();
+    g->pflg_read = false;
+    if (!g->flag_gate) return FGI_OK;   // nothing is allocated, queued or launched
+    // fgi_last_batch_flagged's argument: each of the two bits goes 0 -> 1 at most once in a
+    // node's life and every record reports such a change; a call holds at most the nodes of this rank's
+    // handles plus one new node per begin_compute entry it owns
+    const uint64_t need = 2 * ((uint64_t)g->n_handles + extra);
+    if (g->prec_cap < need) {   // before anything is queued: the previous call's records are forgotten
+        if (g->prec) FGI_HIP(g, hipFree(g->prec));
+        g->prec = nullptr;
+        g->prec_cap = 0;
+        FGI_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->prec), need * sizeof(unsigned long long)));
+        g->prec_cap = need;
+    }
+    if (g->pcur_cap < cascades) {
+        if (g->pcur) FGI_HIP(g, hipFree(g->pcur));
+        g->pcur = nullptr;
+        g->pcur_cap = 0;
+        const uint64_t c = std::max<uint64_t>(cascades, 16);
+        FGI_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->pcur), (1 + c) * sizeof(unsigned long long)));
+        g->pcur_cap = c;
+    }
+    FGI_HIP(g, hipMemsetAsync(g->pcur, 0, sizeof(unsigned long long), g->stream));
+    return FGI_OK;
+}
+
 static fgi_status run_part_planned(fgi_graph* g, const PartView& pv, const WaveParams& wp, const PartBuckets& pb,
                                    uint32_t n_roots, fgi_wave_stats* stats, std::chrono::steady_clock::time_point t0) {
     hipStream_t s = g->stream;
@@ -4466,6 +4544,10 @@ fgi_status run_part_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_d
     if (!part_view(g, &pv)) return set_err(g, FGI_ESTATE, "partition not initialised");
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t s = g->stream;
+    if (!g->pflg_batch) {   // a call of one cascade (a batch opened its records itself)
+        g->pflg_step = 0;
+        FGI_TRY(part_flagged_begin(g, 1, 0));
+    }
     FGI_TRY(part_ensure_lists(g));
     FGI_TRY(ensure_cstart(g, g->pool_top));
     FGI_TRY(ensure_cls(g));
@@ -4515,8 +4597,11 @@ fgi_status run_part_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_d
         }
     }
     const WaveParams wp = wave_params(g, 1, g->opt_direction, sums[0], pv.n_global);
-    if (sums[4] == pv.world)   // every rank follows the plan: no host synchronisation until the wave's end
-        return run_part_planned(g, pv, wp, pb, n_roots, stats, t0);
+    if (sums[4] == pv.world) {   // every rank follows the plan: no host synchronisation until the wave's end
+        FGI_TRY(run_part_planned(g, pv, wp, pb, n_roots, stats, t0));
+        // behind the last round's final collect, after the wave's one wait: outside its span and its syncs
+        return g->flag_gate ? launch_part_flagged(g, pv) : FGI_OK;
+    }
     g->part_plan.clear();      // learnt again by this wave's levels
     g->part_plan_key = key;
     g->part_plan_pull = sums[3] == 0;   // every rank's pull lists were ready (the same on all ranks)
@@ -4593,7 +4678,7 @@ fgi_status run_part_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_d
     g->last_wave_n = c.inv;
     g->ids_valid = true;
     if (stats) fill_wave_stats(stats, c, n_roots, t, wave_span_ms(g, c, part_events(g)), t0);
-    return FGI_OK;
+    return g->flag_gate ? launch_part_flagged(g, pv) : FGI_OK;   // queued, not waited for
 }
 
 }  // namespace fgi

@@ -148,6 +148,7 @@ SIGNATURES = {
     "fgi_rccl_info": [C.POINTER(C.c_int), C.c_char_p, C.c_uint64],
     "fgi_run_batch": [_G, C.c_uint32, C.POINTER(Step), _u32p, C.c_uint64, _u64p, C.POINTER(BatchStats)],
     "fgi_last_batch_flagged": [_G, _u32p, _u32p, _u32p, C.c_uint64, _u64p],
+    "fgi_part_last_flagged": [_G, _u32p, _u32p, _u32p, C.c_uint64, _u64p],
     "fgi_part_begin_compute": [_G, C.c_uint32, _u32p, _u64p, _u8p, _u32p, _u32p, C.c_uint64, _u64p,
                                C.POINTER(WaveStats)],
     "fgi_part_add_used": [_G, C.c_uint32, _u32p, _u32p, _u32p],
@@ -515,6 +516,19 @@ class Graph:
         self._check(self.lib.fgi_last_batch_flagged(self.h, _ptr(steps, C.c_uint32), _ptr(ids, C.c_uint32),
                                                     _ptr(flags, C.c_uint32), len(ids), C.byref(n)),
                     "last_batch_flagged")
+        return steps, ids, flags
+
+    def part_last_flagged(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """fgi_part_last_flagged: this rank's (steps, global slots, state_flags) of the nodes the last
+        partitioned call's cascades flagged without invalidating them, cascade after cascade in step order
+        (step 0 for a call of one cascade), slots ascending within a step. No collective: each rank asks for
+        itself. A multi-GPU host starts its InvalidationDelay timers from the records carrying DelayStarted."""
+        n = C.c_uint64()
+        self._check(self.lib.fgi_part_last_flagged(self.h, None, None, None, 0, C.byref(n)), "part_last_flagged")
+        steps, ids, flags = (np.zeros(n.value, np.uint32) for _ in range(3))
+        self._check(self.lib.fgi_part_last_flagged(self.h, _ptr(steps, C.c_uint32), _ptr(ids, C.c_uint32),
+                                                   _ptr(flags, C.c_uint32), len(ids), C.byref(n)),
+                    "part_last_flagged")
         return steps, ids, flags
 
     def wave_wait_flagged(self, ticket: int) -> Tuple[np.ndarray, np.ndarray]:
