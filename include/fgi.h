@@ -492,14 +492,17 @@ fgi_status fgi_part_init_host(fgi_graph* g, uint32_t n_global, fgi_allgather_fn 
 fgi_status fgi_part_synth_rmat(fgi_graph* g, uint32_t scale, uint32_t edge_factor, uint64_t seed,
                                uint32_t stale_pct, uint64_t stale_seed);
 /* Bulk import into a partitioned graph (ComputedRegistry.Register, ComputedRegistry.cs:72-105, without
- * displacement; the single-device fgi_register_nodes refuses a partition). Every rank is given the
- * same global node list (the host broadcasts it): each rank installs the nodes of the slots it owns
- * and records every listed version in its replica (ver_all), against which it checks the tags of
- * edges into other ranks' slots. No collective runs. */
+ * displacement; the single-device fgi_register_nodes refuses a partition). The replicated form: every
+ * rank is given the same global node list (a host that holds the whole registry in every process; one
+ * that holds a shard per process calls fgi_part_register_shard instead): each rank installs the nodes
+ * of the slots it owns and records every listed version in its replica (ver_all), against which it
+ * checks the tags of edges into other ranks' slots. No collective runs. */
 fgi_status fgi_part_register_nodes(fgi_graph* g, uint32_t n, const uint32_t* slot, const uint64_t* version,
                                    const uint32_t* state_flags);
 /* Bulk import of `_usedBy` entries with global ids (IComputedImpl.AddUsedBy body, Computed.cs:381-382;
- * set semantics). Every rank is given the same batch: it keeps the rows of the `used` slots it owns
+ * set semantics). The replicated form (fgi_part_load_edges_shard takes a shard per rank instead and
+ * cannot number the slots differently): every rank is given the same batch. It keeps the rows of the
+ * `used` slots it owns
  * (entries keep global dependant ids) and the dependency entries of the dependants it owns, from
  * which it rebuilds its pull lists (the reference's `_used`, Computed.cs:36, 365-366). No collective
  * runs. The first bulk load of a partition that uses partition codes (labels: automatic from 2^25
@@ -508,6 +511,37 @@ fgi_status fgi_part_register_nodes(fgi_graph* g, uint32_t n, const uint32_t* slo
  * the next collective wave then fails on every rank with FGI_ESTATE. */
 fgi_status fgi_part_load_edges(fgi_graph* g, uint64_t m, const uint32_t* used, const uint32_t* dependant,
                                const uint64_t* tag);
+/* The same imports from per-rank shards (C-ABI 0.5; ComputedRegistry.Register, ComputedRegistry.cs:72-105,
+ * and the AddUsedBy body, Computed.cs:381-382, with global ids). Collective: every rank joins every call and
+ * passes ITS OWN shard — any nodes / edges, whoever owns them, possibly none (n / m = 0 with null arrays).
+ * The engine routes them to their owners over the partition's transport. With A the concatenation of the
+ * ranks' shards in rank order, every rank is left in the state fgi_part_register_nodes / fgi_part_load_edges
+ * given A on every rank would have left: owned node words, the version replica, rows and dependency entries
+ * (set semantics across shards and across earlier loads), list weights and pull lists, the flag gate of the
+ * flagged sets, and the partition codes if this is the first bulk load of a partition that wants them (every
+ * rank then holds the same weights by construction, so the ranks cannot number the slots differently).
+ * Sharded and replicated calls may be mixed on one partition, in any order.
+ * Errors strand no peer: each rank checks its own shard (slot range, version <= 2^56-1, state != 3, tag != 0)
+ * and its verdict travels with the call's first collective, the counts; if any rank's shard is bad every rank
+ * returns FGI_EINVAL, nothing is applied and fgi_last_error names the rank and the item. A listed slot that
+ * already holds a current node — a slot listed in two shards included — fails fgi_part_register_shard with
+ * FGI_ESTATE on every rank (the owners' counts are all-reduced). FGI_ESTATE on a graph that is not
+ * partitioned or is poisoned; FGI_EDEVICE naming the rank and the collective when a peer is lost.
+ * Buffers: one round per call. A rank stages 2 x 16 bytes per edge of its shard for sending (beside the
+ * 16-byte upload of the edge itself) plus 16 bytes per record it receives (two per edge whose ends it owns).
+ * A host that wants less peak memory calls several times with smaller shards: set semantics hold across calls.
+ * fgi_part_local_register_shards / fgi_part_local_load_shards run the same on every rank of an in-process
+ * group (fgi_part_init_local), one host thread per rank: entry r of each array is rank r's shard. */
+fgi_status fgi_part_register_shard(fgi_graph* g, uint32_t n, const uint32_t* slot, const uint64_t* version,
+                                   const uint32_t* state_flags /*nullable*/);
+fgi_status fgi_part_load_edges_shard(fgi_graph* g, uint64_t m, const uint32_t* used, const uint32_t* dependant,
+                                     const uint64_t* tag);
+fgi_status fgi_part_local_register_shards(fgi_graph* const* gs, uint32_t p, const uint32_t* n,
+                                          const uint32_t* const* slot, const uint64_t* const* version,
+                                          const uint32_t* const* state_flags /*nullable, entries nullable*/);
+fgi_status fgi_part_local_load_shards(fgi_graph* const* gs, uint32_t p, const uint64_t* m,
+                                      const uint32_t* const* used, const uint32_t* const* dependant,
+                                      const uint64_t* const* tag);
 /* Collective wave: every rank passes the same global root list; each rank reports the
  * invalidated slots it owns (global ids) and its own share of the statistics. */
 fgi_status fgi_part_invalidate(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev,

@@ -17,6 +17,7 @@
 
 #include <chrono>
 #include <cstdlib>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -892,6 +893,27 @@ fgi_status run_part_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_d
 // and clears the cursor. run_part_wave opens a call of one cascade itself; fgi_part_run_batch opens its
 // own (pflg_batch) with its begin_compute entries as `extra`.
 fgi_status part_flagged_begin(fgi_graph* g, uint64_t cascades, uint64_t extra);
+// ---- sharded loads (shard.hip) ----
+// The collectives they add to a partition's transport (part.hip, PartComm): host words (at most kShardWords
+// per rank) all-gathered on the host; device byte ranges with per-peer counts, all-gathered (src[0,
+// bytes[rank]) of every rank in rank order at dst) or exchanged (src + soff[q], sbytes[q] bytes, to rank q;
+// rbytes[q] bytes from rank q at dst + roff[q]). Each returns with the data in place.
+constexpr uint32_t kShardWords = 24;
+fgi_status part_allgather_words(fgi_graph* g, const uint64_t* mine, uint32_t words, uint64_t* all);
+fgi_status part_allgatherv(fgi_graph* g, const void* src, const uint64_t* bytes, void* dst);
+fgi_status part_alltoallv(fgi_graph* g, const void* src, const uint64_t* soff, const uint64_t* sbytes, void* dst,
+                          const uint64_t* roff, const uint64_t* rbytes);
+uint32_t* part_weight(fgi_graph* g);   // [n_global] live dependencies per slot (code order once codes exist)
+// the first bulk load of a partition that wants codes; the choice (weight_dev: [n_global] by slot, left in code
+// order); the pull lists rebuilt from the dependency-entry store
+bool part_codes_now(fgi_graph* g);
+fgi_status part_codes_choose(fgi_graph* g, uint32_t* weight_dev);
+fgi_status part_rebuild_lists(fgi_graph* g);
+// fn(rank) on one host thread per rank of the in-process group gs[0, P)
+fgi_status part_local_run(fgi_graph* const* gs, uint32_t P, const std::function<fgi_status(uint32_t)>& fn);
+// load_rows from device arrays (left untouched)
+fgi_status load_rows_dev(fgi_graph* g, uint64_t m, const uint64_t* dev_keys, const uint64_t* dev_tags, uint32_t src_base,
+                         uint32_t dst_base);
 // Append (used, dependant slot, tag) entries to rows (set semantics, no state checks).
 fgi_status append_edges(fgi_graph* g, uint64_t m, const uint32_t* used_dev, const uint32_t* dep_dev,
                         const uint64_t* tag_dev, const uint32_t* dep_handle_dev);

@@ -1697,19 +1697,30 @@ fgi_status build_rows_from_keys(fgi_graph* g, uint64_t m, uint64_t* keys, uint64
 
 // Existing live rows + m new entries (host keys: used handle << 32 | dependant id, host tags),
 // rebuilt in one sort (set semantics across both).
-fgi_status load_rows(fgi_graph* g, uint64_t m, const uint64_t* host_keys, const uint64_t* host_tags, uint32_t src_base,
-                     uint32_t dst_base) {
+static fgi_status load_rows_from(fgi_graph* g, uint64_t m, const uint64_t* new_keys, const uint64_t* new_tags,
+                                 hipMemcpyKind kind, uint32_t src_base, uint32_t dst_base) {
     FGI_TRY(fold(g));
     Tmp tk, tt;
     uint64_t *keys, *tags, m0 = 0;
     FGI_TRY(gather_live(g, tk, tt, &keys, &tags, m, &m0));
-    FGI_TRY(h2d(g, keys + m0, host_keys, m));
-    FGI_TRY(h2d(g, tags + m0, host_tags, m));
+    if (m) {
+        FGI_HIP(g, hipMemcpyAsync(keys + m0, new_keys, m * 8, kind, g->stream));
+        FGI_HIP(g, hipMemcpyAsync(tags + m0, new_tags, m * 8, kind, g->stream));
+    }
     if (!g->part) {   // boundary handles -> labels (the first bulk load chooses the hot labels)
         if (m0 == 0) FGI_TRY(labels_choose(g, keys, m));
         FGI_TRY(labels_map_keys(g, keys + m0, m));
     }
     return build_rows_from_keys(g, m0 + m, keys, tags, 0, 0, 0, src_base, dst_base);
+}
+fgi_status load_rows(fgi_graph* g, uint64_t m, const uint64_t* host_keys, const uint64_t* host_tags, uint32_t src_base,
+                     uint32_t dst_base) {
+    return load_rows_from(g, m, host_keys, host_tags, hipMemcpyHostToDevice, src_base, dst_base);
+}
+// the same with the new entries in device memory (sharded loads: the keys arrive by the partition's transport)
+fgi_status load_rows_dev(fgi_graph* g, uint64_t m, const uint64_t* dev_keys, const uint64_t* dev_tags, uint32_t src_base,
+                         uint32_t dst_base) {
+    return load_rows_from(g, m, dev_keys, dev_tags, hipMemcpyDeviceToDevice, src_base, dst_base);
 }
 
 namespace {
@@ -1899,8 +1910,9 @@ extern "C" {
 
 fgi_status fgi_version(uint32_t* major, uint32_t* minor) {
     if (major) *major = 0;
-    // 0.2: fgi_last_wave_flagged, fgi_wave_wait_flagged; 0.3: fgi_last_batch_flagged; 0.4: fgi_part_last_flagged
-    if (minor) *minor = 4;
+    // 0.2: fgi_last_wave_flagged, fgi_wave_wait_flagged; 0.3: fgi_last_batch_flagged; 0.4: fgi_part_last_flagged;
+    // 0.5: fgi_part_register_shard, fgi_part_load_edges_shard and their in-process drivers
+    if (minor) *minor = 5;
     return FGI_OK;
 }
 

@@ -68,6 +68,24 @@ struct PartComm {
     // (synchronises); every rank's cur_local (W64 words) into cur_all[q * W64, + W64) (stream-ordered)
     virtual fgi_status allreduce_u32(fgi_graph* g, uint32_t* dev, uint64_t n) = 0;
     virtual fgi_status allgather_cur_async(fgi_graph* g) = 0;
+    // Sharded loads (shard.hip). Each returns with the data in place (the stream is synchronised).
+    // every rank's `words` host u64 (<= kShardWords) into all[world][words] on the host
+    virtual fgi_status allgather_words(fgi_graph* g, const uint64_t* mine, uint32_t words, uint64_t* all) = 0;
+    // device byte ranges with per-peer counts: src + soff[q] (sbytes[q] bytes) goes to rank q, which finds it
+    // at its dst + roff[this rank]; rbytes[q] bytes arrive from rank q. src and dst do not overlap.
+    virtual fgi_status alltoallv(fgi_graph* g, const void* src, const uint64_t* soff, const uint64_t* sbytes, void* dst,
+                                 const uint64_t* roff, const uint64_t* rbytes) = 0;
+    // src[0, bytes[rank]) of every rank, concatenated in rank order at dst (bytes: [world], known to all)
+    virtual fgi_status allgatherv(fgi_graph* g, const void* src, const uint64_t* bytes, void* dst) {
+        uint64_t soff[8], sb[8], roff[8], at = 0;
+        for (uint32_t q = 0; q < (uint32_t)g->world; ++q) {
+            soff[q] = 0;
+            sb[q] = bytes[g->rank];
+            roff[q] = at;
+            at += bytes[q];
+        }
+        return alltoallv(g, src, soff, sb, dst, roff, bytes);
+    }
 };
 
 struct PartState {
@@ -415,6 +433,45 @@ struct RcclComm final : PartComm {
         *n_recv = recv;
         return FGI_OK;
     }
+    fgi_status allgather_words(fgi_graph* g, const uint64_t* mine, uint32_t words, uint64_t* all) override {
+        PartState* p = ps(g);
+        const uint32_t W = p->v.world;
+        if (W == 1 && !g->opt_part_coll) {
+            std::memcpy(all, mine, 8ull * words);
+            return FGI_OK;
+        }
+        unsigned long long* d = nullptr;   // [1 + W][words]: mine, then everyone's
+        FGI_HIP(g, hipMalloc(&d, (size_t)(W + 1) * words * 8));
+        fgi_status st = FGI_OK;
+        auto run = [&]() -> fgi_status {
+            FGI_HIP(g, hipMemcpyAsync(d, mine, 8ull * words, hipMemcpyHostToDevice, g->stream));
+            FGI_NCCL(g, rccl().AllGather(d, d + words, words, ncclUint64, p->comm, g->stream));
+            FGI_HIP(g, hipMemcpyAsync(all, d + words, (size_t)W * words * 8, hipMemcpyDeviceToHost, g->stream));
+            return comm_sync(g, g->stream, "all-gather of a sharded load's counts");
+        };
+        st = run();
+        hipFree(d);
+        return st;
+    }
+    fgi_status alltoallv(fgi_graph* g, const void* src, const uint64_t* soff, const uint64_t* sbytes, void* dst,
+                         const uint64_t* roff, const uint64_t* rbytes) override {
+        PartState* p = ps(g);
+        const uint32_t W = p->v.world;
+        const char* s8 = static_cast<const char*>(src);
+        char* d8 = static_cast<char*>(dst);
+        if (W == 1 && !g->opt_part_coll) {
+            if (rbytes[0])
+                FGI_HIP(g, hipMemcpyAsync(d8 + roff[0], s8 + soff[0], rbytes[0], hipMemcpyDeviceToDevice, g->stream));
+            return comm_sync(g, g->stream, "sharded load (copy)");
+        }
+        FGI_NCCL(g, rccl().GroupStart());
+        for (uint32_t q = 0; q < W; ++q) {
+            if (sbytes[q]) FGI_NCCL(g, rccl().Send(s8 + soff[q], sbytes[q], ncclUint8, (int)q, p->comm, g->stream));
+            if (rbytes[q]) FGI_NCCL(g, rccl().Recv(d8 + roff[q], rbytes[q], ncclUint8, (int)q, p->comm, g->stream));
+        }
+        FGI_NCCL(g, rccl().GroupEnd());
+        return comm_sync(g, g->stream, "variable-size exchange of a sharded load");
+    }
 };
 
 // ---- host collectives (one process per rank, the host's own transport) -------------------------------
@@ -565,6 +622,57 @@ struct HostComm final : PartComm {
         FGI_TRY(gather(g, p->cur_w64 * 8));
         return upload(g, p->cur_all, rbuf.data(), (uint64_t)p->v.world * p->cur_w64 * 8);
     }
+    fgi_status allgather_words(fgi_graph* g, const uint64_t* mine, uint32_t words, uint64_t* all) override {
+        sbuf.resize(std::max<size_t>(sbuf.size(), 8ull * words));
+        std::memcpy(sbuf.data(), mine, 8ull * words);
+        FGI_TRY(gather(g, 8ull * words));
+        std::memcpy(all, rbuf.data(), (size_t)ps(g)->v.world * words * 8);
+        return FGI_OK;
+    }
+    // one all-gather of [max] padded bytes per rank
+    fgi_status allgatherv(fgi_graph* g, const void* src, const uint64_t* bytes, void* dst) override {
+        const uint32_t W = ps(g)->v.world, R = ps(g)->v.rank;
+        uint64_t mx = 0;
+        for (uint32_t q = 0; q < W; ++q) mx = std::max(mx, bytes[q]);
+        FGI_HIP(g, hipStreamSynchronize(g->stream));
+        if (!mx) return FGI_OK;
+        sbuf.assign(mx, 0);
+        FGI_TRY(stage(g, src, bytes[R]));
+        FGI_TRY(gather(g, mx));
+        uint64_t at = 0;
+        for (uint32_t q = 0; q < W; ++q) {
+            if (bytes[q])
+                FGI_HIP(g, hipMemcpyAsync(static_cast<char*>(dst) + at, rbuf.data() + (size_t)q * mx, bytes[q],
+                                          hipMemcpyHostToDevice, g->stream));
+            at += bytes[q];
+        }
+        FGI_HIP(g, hipStreamSynchronize(g->stream));
+        return FGI_OK;
+    }
+    // the largest range of any pair first (one word per rank), then one all-gather of [world][max] padded bytes
+    fgi_status alltoallv(fgi_graph* g, const void* src, const uint64_t* soff, const uint64_t* sbytes, void* dst,
+                         const uint64_t* roff, const uint64_t* rbytes) override {
+        const uint32_t W = ps(g)->v.world, R = ps(g)->v.rank;
+        uint64_t mine = 0, mx = 0, all[8];
+        for (uint32_t q = 0; q < W; ++q) mine = std::max(mine, sbytes[q]);
+        FGI_TRY(allgather_words(g, &mine, 1, all));
+        for (uint32_t q = 0; q < W; ++q) mx = std::max(mx, all[q]);
+        FGI_HIP(g, hipStreamSynchronize(g->stream));
+        if (!mx) return FGI_OK;
+        sbuf.assign((size_t)W * mx, 0);
+        for (uint32_t q = 0; q < W; ++q)
+            if (sbytes[q])
+                FGI_HIP(g, hipMemcpyAsync(sbuf.data() + (size_t)q * mx, static_cast<const char*>(src) + soff[q], sbytes[q],
+                                          hipMemcpyDeviceToHost, g->stream));
+        FGI_HIP(g, hipStreamSynchronize(g->stream));
+        FGI_TRY(gather(g, (uint64_t)W * mx));
+        for (uint32_t q = 0; q < W; ++q)
+            if (rbytes[q])
+                FGI_HIP(g, hipMemcpyAsync(static_cast<char*>(dst) + roff[q], rbuf.data() + ((size_t)q * W + R) * mx, rbytes[q],
+                                          hipMemcpyHostToDevice, g->stream));
+        FGI_HIP(g, hipStreamSynchronize(g->stream));
+        return FGI_OK;
+    }
 };
 
 // ---- in-process group (P graphs, one host thread per rank) ---------------------------------------
@@ -582,8 +690,13 @@ struct LocalGroup {
     // stream-ordered exchanges (planned waves): rank r records ready[r] when its source is final and
     // done[r] when its copies from the others are queued; the others' streams wait on them
     std::vector<hipEvent_t> ready, done;
+    // variable-size exchanges (sharded loads): rank r's source and its [P] byte offsets per destination
+    std::vector<const char*> xsrc;
+    std::vector<uint64_t> xoff;
 
     explicit LocalGroup(std::vector<fgi_graph*> g) : gs(std::move(g)) {
+        xsrc.assign(gs.size(), nullptr);
+        xoff.assign(gs.size() * gs.size(), 0);
         vals.assign(gs.size() * kPartRedMax, 0);
         cnt.assign(gs.size() * (gs.size() + 2), 0);
         ready.assign(gs.size(), nullptr);
@@ -611,7 +724,9 @@ struct LocalGroup {
             return true;
         }
         cv.wait(lk, [&] { return gen != my || failed; });
-        return !failed;
+        // a barrier every rank reached has completed, also for a rank that wakes after a peer left the call
+        // with an error of its own behind that barrier (a refused shard: every rank returns FGI_EINVAL)
+        return gen != my;
     }
     void fail() {
         std::lock_guard<std::mutex> lk(mu);
@@ -788,6 +903,38 @@ struct LocalComm final : PartComm {
         FGI_HIP(g, hipStreamSynchronize(g->stream));
         return FGI_OK;
     }
+    fgi_status allgather_words(fgi_graph* g, const uint64_t* mine, uint32_t words, uint64_t* all) override {
+        const size_t W = grp->gs.size();
+        {
+            std::lock_guard<std::mutex> lk(grp->mu);
+            for (uint32_t i = 0; i < words; ++i) grp->vals[(size_t)rank * kPartRedMax + i] = mine[i];
+        }
+        if (!grp->arrive()) return peer_failed(g);
+        for (size_t q = 0; q < W; ++q)
+            for (uint32_t i = 0; i < words; ++i) all[q * words + i] = grp->vals[q * kPartRedMax + i];
+        if (!grp->arrive()) return peer_failed(g);   // nobody overwrites vals before all have read them
+        return FGI_OK;
+    }
+    // device copies out of the senders' buffers, between two barriers (as exchange_delta)
+    fgi_status alltoallv(fgi_graph* g, const void* src, const uint64_t* soff, const uint64_t* sbytes, void* dst,
+                         const uint64_t* roff, const uint64_t* rbytes) override {
+        (void)sbytes;
+        const size_t W = grp->gs.size();
+        FGI_HIP(g, hipStreamSynchronize(g->stream));   // this rank's source is complete
+        {
+            std::lock_guard<std::mutex> lk(grp->mu);
+            grp->xsrc[rank] = static_cast<const char*>(src);
+            for (size_t q = 0; q < W; ++q) grp->xoff[rank * W + q] = soff[q];
+        }
+        if (!grp->arrive()) return peer_failed(g);
+        for (size_t q = 0; q < W; ++q)
+            if (rbytes[q])
+                FGI_HIP(g, hipMemcpyAsync(static_cast<char*>(dst) + roff[q], grp->xsrc[q] + grp->xoff[q * W + rank], rbytes[q],
+                                          hipMemcpyDefault, g->stream));
+        FGI_HIP(g, hipStreamSynchronize(g->stream));
+        if (!grp->arrive()) return peer_failed(g);     // the senders keep their buffers until every copy is done
+        return FGI_OK;
+    }
 };
 
 fgi_status part_exchange(fgi_graph* g, uint64_t* n_recv, uint64_t* n_sent, uint64_t* glob) {
@@ -822,6 +969,20 @@ fgi_status part_cur_buffers(fgi_graph* g, unsigned long long** local, unsigned l
 }
 
 fgi_status part_allgather_cur(fgi_graph* g) { return ps(g)->ops->allgather_cur_async(g); }
+
+// the sharded loads' collectives (shard.hip)
+fgi_status part_allgather_words(fgi_graph* g, const uint64_t* mine, uint32_t words, uint64_t* all) {
+    if (words < 1 || words > kShardWords) return set_err(g, FGI_EINVAL, "part_allgather_words: %u words", words);
+    return ps(g)->ops->allgather_words(g, mine, words, all);
+}
+fgi_status part_allgatherv(fgi_graph* g, const void* src, const uint64_t* bytes, void* dst) {
+    return ps(g)->ops->allgatherv(g, src, bytes, dst);
+}
+fgi_status part_alltoallv(fgi_graph* g, const void* src, const uint64_t* soff, const uint64_t* sbytes, void* dst,
+                          const uint64_t* roff, const uint64_t* rbytes) {
+    return ps(g)->ops->alltoallv(g, src, soff, sbytes, dst, roff, rbytes);
+}
+uint32_t* part_weight(fgi_graph* g) { return ps(g)->weight; }
 
 static fgi_status part_store_in(fgi_graph* g, const uint64_t* keys, const uint64_t* tags, uint64_t m);
 
@@ -1239,7 +1400,7 @@ fgi_status scan_flags(fgi_graph* g, const uint32_t* flag, uint32_t* pos, uint64_
 // Choose the codes from every slot's weight (weight_dev: [n_global], by slot; replaced by the weights in
 // code order) and move what is already installed: the owned node words and |_used| counts, the version
 // replica. Only before any row or dependency entry exists and while no detached handle is taken.
-static fgi_status part_codes_choose(fgi_graph* g, uint32_t* weight_dev) {
+fgi_status part_codes_choose(fgi_graph* g, uint32_t* weight_dev) {
     PartState* p = ps(g);
     const uint32_t N = p->v.n_global, B = p->v.block, base = p->v.base, nl = p->v.n_local;
     hipStream_t s = g->stream;
@@ -1310,13 +1471,13 @@ static fgi_status part_codes_choose(fgi_graph* g, uint32_t* weight_dev) {
 }
 
 // the first bulk load of a partition that wants codes (nothing loaded, no detached handle taken)
-static bool part_codes_now(fgi_graph* g) {
+bool part_codes_now(fgi_graph* g) {
     PartState* p = ps(g);
     return !g->lbl_perm && part_codes_wanted(g, p->v.n_global) && g->pool_top == 0 && p->in_n == 0 &&
            g->free_detached.size() == g->n_detached;
 }
 
-static fgi_status part_rebuild_lists(fgi_graph* g) {
+fgi_status part_rebuild_lists(fgi_graph* g) {
     PartState* p = ps(g);
     hipStream_t s = g->stream;
     const uint64_t m = p->in_n;
@@ -2038,3 +2199,11 @@ fgi_status fgi_part_export_ids(fgi_graph* g, uint32_t* out_ids, uint64_t cap, ui
 }
 
 }  // extern "C"
+
+namespace fgi {
+fgi_status part_local_run(fgi_graph* const* gs, uint32_t P, const std::function<fgi_status(uint32_t)>& fn) {
+    LocalComm* c0 = nullptr;
+    FGI_TRY(local_group(gs, P, &c0));
+    return local_run(gs, P, c0, fn);
+}
+}  // namespace fgi

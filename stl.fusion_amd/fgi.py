@@ -164,6 +164,12 @@ SIGNATURES = {
     "fgi_part_local_run_batch": [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.POINTER(Step), _u32p, C.c_uint64,
                                  _u64p, C.POINTER(BatchStats)],
     "fgi_part_local_prune": [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(PruneStats)],
+    "fgi_part_register_shard": [_G, C.c_uint32, _u32p, _u64p, _u32p],
+    "fgi_part_load_edges_shard": [_G, C.c_uint64, _u32p, _u32p, _u64p],
+    "fgi_part_local_register_shards": [C.POINTER(C.c_void_p), C.c_uint32, _u32p, C.POINTER(_u32p), C.POINTER(_u64p),
+                                       C.POINTER(_u32p)],
+    "fgi_part_local_load_shards": [C.POINTER(C.c_void_p), C.c_uint32, _u64p, C.POINTER(_u32p), C.POINTER(_u32p),
+                                   C.POINTER(_u64p)],
 }
 
 _lib = None
@@ -631,6 +637,19 @@ class Graph:
         self._check(self.lib.fgi_part_load_edges(self.h, len(u), _ptr(u, C.c_uint32), _ptr(d, C.c_uint32),
                                                  _ptr(t, C.c_uint64)), "part_load_edges")
 
+    def part_register_shard(self, slots, versions, state_flags=None):
+        """fgi_part_register_shard (collective): this rank's own nodes, global slot ids, whoever owns them."""
+        s, v = _u32(slots), _u64(versions)
+        f = None if state_flags is None else _u32(state_flags)
+        self._check(self.lib.fgi_part_register_shard(self.h, len(s), _ptr(s, C.c_uint32), _ptr(v, C.c_uint64),
+                                                     _ptr(f, C.c_uint32)), "part_register_shard")
+
+    def part_load_edges_shard(self, used, dependant, tags):
+        """fgi_part_load_edges_shard (collective): this rank's own edges, global ids, whoever owns them."""
+        u, d, t = _u32(used), _u32(dependant), _u64(tags)
+        self._check(self.lib.fgi_part_load_edges_shard(self.h, len(u), _ptr(u, C.c_uint32), _ptr(d, C.c_uint32),
+                                                       _ptr(t, C.c_uint64)), "part_load_edges_shard")
+
     def part_invalidate(self, n_roots: int, roots_ptr: int, imm_ptr: int = 0,
                         stats: Optional[WaveStats] = None) -> int:
         n = C.c_uint64()
@@ -806,6 +825,40 @@ def part_local_prune(graphs):
     if st != OK:
         _local_error(lib, graphs, st, "fgi_part_local_prune")
     return list(stats)
+
+
+def _ptr_array(arrays, ct):
+    return (C.POINTER(ct) * len(arrays))(*[_ptr(a, ct) for a in arrays])
+
+
+def part_local_register_shards(graphs, shards):
+    """fgi_part_local_register_shards: shards[r] = (slots, versions[, state_flags or None]) is rank r's
+    own node list (global slot ids, whoever owns them; empty arrays are legal)."""
+    lib = load_library()
+    arr_g = (C.c_void_p * len(graphs))(*[g.h.value for g in graphs])
+    s = [_u32(x[0]) for x in shards]
+    v = [_u64(x[1]) for x in shards]
+    f = [None if len(x) < 3 or x[2] is None else _u32(x[2]) for x in shards]
+    n = _u32([len(a) for a in s])
+    flags = None if all(a is None for a in f) else _ptr_array(f, C.c_uint32)
+    st = lib.fgi_part_local_register_shards(arr_g, len(graphs), _ptr(n, C.c_uint32), _ptr_array(s, C.c_uint32),
+                                            _ptr_array(v, C.c_uint64), flags)
+    if st != OK:
+        _local_error(lib, graphs, st, "fgi_part_local_register_shards")
+
+
+def part_local_load_shards(graphs, shards):
+    """fgi_part_local_load_shards: shards[r] = (used, dependant, tags) is rank r's own edge list."""
+    lib = load_library()
+    arr_g = (C.c_void_p * len(graphs))(*[g.h.value for g in graphs])
+    u = [_u32(x[0]) for x in shards]
+    d = [_u32(x[1]) for x in shards]
+    t = [_u64(x[2]) for x in shards]
+    m = _u64([len(a) for a in u])
+    st = lib.fgi_part_local_load_shards(arr_g, len(graphs), _ptr(m, C.c_uint64), _ptr_array(u, C.c_uint32),
+                                        _ptr_array(d, C.c_uint32), _ptr_array(t, C.c_uint64))
+    if st != OK:
+        _local_error(lib, graphs, st, "fgi_part_local_load_shards")
 
 
 def header_symbols(header_path: str) -> list:
