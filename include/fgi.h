@@ -171,6 +171,90 @@ fgi_status fgi_get_used_count(fgi_graph* g, uint32_t handle, uint32_t* out);
 /* Out-degree (|_usedBy|) of every handle, and the total. */
 fgi_status fgi_get_degrees(fgi_graph* g, uint32_t* degree /*n_slots+n_detached, nullable*/, uint64_t* total);
 
+/* ---- host-memory state view (C-ABI 0.6) ------------------------------------------------------- */
+/* IComputed.ConsistencyState as the reference reads it: a plain field (Computed.cs:46), on its most
+ * frequent path, the cache hit of ComputedExt.TryUseExisting (Internal/ComputedExt.cs:13-22). The view is
+ * a state table in host memory that the device keeps current, so a state read is a load and no call.
+ * Layout: six bit planes of `words` 64-bit words each, in host memory the engine owns and the device
+ * writes. Bit h % 64 of word h / 64 addresses boundary handle h, detached handles included.
+ *   registered     handle h holds a node (version != 0)
+ *   consistent     state == Consistent
+ *   computing      registered and state == Computing
+ *   ioso           canonical FGI_F_INVALIDATE_ON_SET_OUTPUT (Computing nodes only)
+ *   delay_started  canonical FGI_F_INVALIDATION_DELAY_STARTED (never on an Invalidated node)
+ *   has_delay      FGI_F_HAS_DELAY
+ * fgi_view_flags(v, h) is the state_flags word fgi_get_state reports for h (0 for an empty handle). A wave
+ * clears bits of `consistent` only (and of `delay_started` where an `immediately` root invalidates a
+ * delayed node), so a dense wave moves one plane, and fgi_view_is_consistent is one load and one bit test.
+ * Guarantee: when a synchronous entry point returns — fgi_state_view_open itself included, on a graph
+ * already populated — the view is exact. After fgi_wave_wait* returns for ticket t the view holds at
+ * least the waves up to t. With waves in flight each 64-bit plane word is either its old or its new
+ * value. *seq is written by the calling host thread: odd from a call's first launch that may touch the
+ * view (an asynchronous wave: from its queueing) until the wait that makes the view exact, even
+ * otherwise. Any thread may read the planes at any time (relaxed atomic loads: the helpers below); a
+ * reader that needs several planes consistent with each other reads seq before and after and retries
+ * if it was odd or has changed.
+ * Reading the view and keeping it current have no other observable effect: no wave result, flagged set
+ * or statistic changes. A graph that never opened a view allocates and launches nothing for it. With a
+ * view open a wave keeps its invalidated bitmap to its end, so the next wave starts with its init
+ * kernel again (as on a graph that can flag), and a call on a graph that can flag waits once more for
+ * the device (fgi_view_stats.extra_waits); on a graph that cannot flag a wave's view update is queued
+ * before the wave's own publish and costs no further wait.
+ * FGI_ENOTSUP on a partitioned graph (a partition's view is out of scope: each rank would hold its
+ * slots' share); FGI_ESTATE on a poisoned graph. After a call that failed with FGI_EDEVICE the view is
+ * undefined until fgi_restore; fgi_restore with a view open returns only once the view shows the
+ * snapshot's states (it waits for the device; without a view it stays stream-ordered). fgi_destroy
+ * closes the view; the planes stay mapped until then, a closed view is no longer updated, and a second
+ * open returns the same planes, rebuilt. */
+typedef struct fgi_state_view {
+    uint32_t struct_size;          /* in: sizeof(fgi_state_view) */
+    uint32_t n_handles;            /* n_slots + n_detached */
+    uint64_t words;                /* 64-bit words per plane = (n_handles + 63) / 64 */
+    const uint64_t* registered;
+    const uint64_t* consistent;
+    const uint64_t* computing;
+    const uint64_t* ioso;
+    const uint64_t* delay_started;
+    const uint64_t* has_delay;
+    const uint64_t* seq;           /* even: no update in progress; odd: one is */
+} fgi_state_view;
+fgi_status fgi_state_view_open(fgi_graph* g, fgi_state_view* out);
+fgi_status fgi_state_view_close(fgi_graph* g);
+/* updates: calls that updated the view; words_published: 64-bit plane words written to host memory
+ * (a full build writes every plane); full_builds: passes over every handle (open, bulk loads,
+ * fgi_restore); extra_waits: device waits made for the view alone. All zero on a graph that never
+ * opened a view. */
+typedef struct fgi_view_stats {
+    uint64_t updates, words_published, full_builds, extra_waits;
+} fgi_view_stats;
+fgi_status fgi_state_view_stats(fgi_graph* g, fgi_view_stats* out);
+
+/* The read path. The helpers are inline C for hosts that include this header; the library also exports
+ * them under the same names for bindings that cannot inline C (its own build defines
+ * FGI_VIEW_OUT_OF_LINE). */
+#define FGI_VIEW_BIT(plane, h) ((__atomic_load_n((plane) + ((h) >> 6), __ATOMIC_RELAXED) >> ((h) & 63u)) & 1u)
+#ifdef FGI_VIEW_OUT_OF_LINE
+#define FGI_VIEW_INLINE
+#else
+#define FGI_VIEW_INLINE static inline
+#endif
+/* one load, one bit test */
+FGI_VIEW_INLINE int fgi_view_is_consistent(const fgi_state_view* v, uint32_t h) {
+    return h < v->n_handles && FGI_VIEW_BIT(v->consistent, h);
+}
+/* the canonical state_flags of handle h (what fgi_get_state reports); 0 for an empty handle */
+FGI_VIEW_INLINE uint32_t fgi_view_flags(const fgi_state_view* v, uint32_t h) {
+    uint32_t f;
+    if (h >= v->n_handles || !FGI_VIEW_BIT(v->registered, h)) return 0u;
+    f = FGI_VIEW_BIT(v->has_delay, h) ? FGI_F_HAS_DELAY : 0u;
+    if (FGI_VIEW_BIT(v->consistent, h))
+        return f | FGI_CONSISTENT | (FGI_VIEW_BIT(v->delay_started, h) ? FGI_F_INVALIDATION_DELAY_STARTED : 0u);
+    if (FGI_VIEW_BIT(v->computing, h))
+        return f | FGI_COMPUTING | (FGI_VIEW_BIT(v->ioso, h) ? FGI_F_INVALIDATE_ON_SET_OUTPUT : 0u) |
+               (FGI_VIEW_BIT(v->delay_started, h) ? FGI_F_INVALIDATION_DELAY_STARTED : 0u);
+    return f | FGI_INVALIDATED;
+}
+
 /* ---- dependency capture (compute-method call path) ----------------------------------------- */
 /* ComputeMethodFunctionBase.Compute (ComputeMethodFunctionBase.cs:19-27): a new Computing node of
  * version[i] becomes the current node of slot[i] (registered in its ctor,

@@ -71,6 +71,17 @@ __host__ __device__ inline uint64_t flags_to_word(uint64_t version, uint32_t f) 
     return w;
 }
 
+// The node word after a (non-immediate) visit: canonical, flags of an Invalidated node cleared
+// (wave.hip's visits; view.hip reads unfolded visits through it).
+__host__ __device__ inline unsigned long long visited_word(unsigned long long w) {
+    if ((w & kVMask) == 0) return w;
+    const uint32_t st = word_state(w);
+    if (st == FGI_COMPUTING) return w | kW_IOSO;
+    if (st == FGI_CONSISTENT)
+        return (w & kW_HasDelay) ? (w | kW_DS) : ((w & (kVMask | kW_HasDelay)) | kW_Invalidated);
+    return w;
+}
+
 // splitmix64 finaliser
 __host__ __device__ inline uint64_t sm64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
@@ -364,6 +375,25 @@ __device__ inline bool last_block_arrive(unsigned long long* done, uint64_t G) {
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+};
+
+// The host-memory state view (fgi_state_view_open; view.hip). Six bit planes over the
+// boundary's handles (kViewPlanes x words 64-bit words, plane p at word p * words), kept twice: on the
+// device (dev), where the update kernels change them with atomics and mark what they changed in a dirty
+// bitmap (one bit per plane word), and in fine-grained host memory (host), where the flush kernel copies
+// the dirty words. host[kViewPlanes * words] is the view's sequence word, written by the host alone.
+constexpr uint32_t kViewPlanes = 6;
+enum { kVpRegistered = 0, kVpConsistent, kVpComputing, kVpIoso, kVpDelayStarted, kVpHasDelay };
+struct View {
+    bool open = false;
+    uint64_t words = 0;                    // 64-bit words per plane
+    unsigned long long* host = nullptr;    // [kViewPlanes * words + 8]
+    unsigned long long* dev = nullptr;     // [kViewPlanes * words]
+    unsigned long long* dirty = nullptr;   // [dirty_words] bit p * words + x: dev word x of plane p differs from host
+    uint64_t dirty_words = 0;
+    unsigned long long* pub_dev = nullptr; // words the flush kernels copied so far
+    uint64_t pub_base = 0;                 // words the full builds copied
+    uint64_t updates = 0, full_builds = 0, extra_waits = 0;
 };
 
 }  // namespace fgi
@@ -686,6 +716,7 @@ struct fgi_graph {
     std::vector<uint64_t> pflg_set;
     bool pflg_read = false, pflg_batch = false;
     uint32_t pflg_step = 0;
+    fgi::View* view = nullptr;         // the host-memory state view (null until fgi_state_view_open)
 };
 
 // ---- internal entry points shared between translation units ----------------------------------
@@ -823,6 +854,31 @@ fgi_status ensure_cls(fgi_graph* g);
 fgi_status read_flagged(fgi_graph* g, int k, bool blocking_copy, std::vector<uint64_t>* out);
 // Pull tiles of a level over n slots with `grid` blocks.
 __host__ __device__ inline uint64_t pull_iters(uint64_t n, uint32_t grid) { return (n + (uint64_t)grid * kPullTile - 1) / ((uint64_t)grid * kPullTile); }
+// ---- the host-memory state view (view.hip) ----
+// Everything below but view_on is a no-op returning FGI_OK while no view is open; the queueing calls
+// launch on the graph's stream and do not wait.
+inline bool view_on(const fgi_graph* g) { return g->view && g->view->open; }
+// the view's sequence word: odd from a call's first launch that may touch the view ...
+void view_begin(fgi_graph* g);
+// ... even again once the view is exact (no asynchronous wave in flight)
+void view_end(fgi_graph* g);
+// every plane from the node words and the unfolded visit bits (one pass over the handles), copied to the host
+fgi_status view_rebuild(fgi_graph* g);
+// a wave's invalidated bitmap (g->inv_bm, over labels) cleared out of `consistent` and `delay_started`
+fgi_status view_wave(fgi_graph* g);
+// the planes' bits of listed handles from their node words (and unfolded visit bits). kind: kViewHandles
+// u32 boundary handles, kViewLabels u32 labels, kViewRecords u64 flagged records (handle << 32 | flags).
+// The list holds n entries, or *n_dev of them if that is less (n_dev nullable). FGI_NONE entries are skipped.
+enum { kViewHandles = 0, kViewLabels = 1, kViewRecords = 2 };
+fgi_status view_refresh(fgi_graph* g, int kind, const void* list_dev, uint64_t n, const unsigned long long* n_dev = nullptr);
+// the same for a host list of boundary handles (uploaded on the stream)
+fgi_status view_refresh_host(fgi_graph* g, const uint32_t* handles, uint64_t n);
+// the dirty words to the host planes, system-scope fenced
+fgi_status view_flush(fgi_graph* g);
+// flush, wait for the stream (counted in extra_waits), and end the update
+fgi_status view_commit(fgi_graph* g);
+void view_destroy(fgi_graph* g);
+
 // ---- multi-GPU partition (part.hip) ----
 // Release multi-GPU resources.
 fgi_status part_destroy(fgi_graph* g);

@@ -1912,7 +1912,8 @@ fgi_status fgi_version(uint32_t* major, uint32_t* minor) {
     if (major) *major = 0;
     // 0.2: fgi_last_wave_flagged, fgi_wave_wait_flagged; 0.3: fgi_last_batch_flagged; 0.4: fgi_part_last_flagged;
     // 0.5: fgi_part_register_shard, fgi_part_load_edges_shard and their in-process drivers
-    if (minor) *minor = 5;
+    // 0.6: the host-memory state view (fgi_state_view_open / _close / _stats, fgi_view_flags, fgi_view_is_consistent)
+    if (minor) *minor = 6;
     return FGI_OK;
 }
 
@@ -2000,6 +2001,7 @@ fgi_status fgi_destroy(fgi_graph* g) {
     hipSetDevice(g->device);
     if (g->stream) hipStreamSynchronize(g->stream);
     fgi::part_destroy(g);
+    fgi::view_destroy(g);
     fgi::tmp_drain(g);
     dfree(g->node);
     dfree(g->row_off);
@@ -2132,6 +2134,7 @@ fgi_status fgi_register_nodes(fgi_graph* g, uint32_t n, const uint32_t* slot, co
     FGI_HIP(g, hipGetLastError());
     unsigned long long bad = 0;
     FGI_TRY(d2h(g, &bad, g->misc_dev, 1));
+    FGI_TRY(view_rebuild(g));   // a bulk import: the state view's full build
     if (bad) return set_err(g, FGI_ESTATE, "%llu slots already had a current node", bad);
     return FGI_OK;
 }
@@ -2471,7 +2474,7 @@ fgi_status fgi_restore(fgi_graph* g) {
         // nothing but waves ran since the snapshot: rows and |_used| counts are unchanged. The
         // copies are stream-ordered before every later call on this graph, so no host wait here.
         FGI_HIP(g, hipGetLastError());
-        return FGI_OK;
+        return view_rebuild(g);   // with a state view open the call waits until the view shows the snapshot
     }
     FGI_HIP(g, hipMemcpyAsync(g->row_off, g->snap_row_off, H * 8, hipMemcpyDeviceToDevice, s));
     FGI_HIP(g, hipMemcpyAsync(g->row_len, g->snap_row_len, H * 4, hipMemcpyDeviceToDevice, s));
@@ -2485,7 +2488,7 @@ fgi_status fgi_restore(fgi_graph* g) {
     FGI_HIP(g, hipStreamSynchronize(s));
     g->mut_epoch = g->snap_mut_epoch;   // rows and versions are those of the snapshot again
     g->failed = false;
-    return FGI_OK;
+    return view_rebuild(g);
 }
 
 fgi_status fgi_set_option(fgi_graph* g, int option, int64_t value) {
@@ -2844,6 +2847,7 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
     // displacement cascade first (ComputedRegistry.cs:91-94), then detach + install
     g->last_wave_n = 0;
     if (cnt[0]) FGI_TRY(run_wave(g, (uint32_t)cnt[0], droots, nullptr, stats));
+    view_begin(g);   // the cascade's share of the state view is in; the install's follows below
     // the call's slots hold new nodes when it returns: a displaced node the cascade flagged is not in the
     // call's flagged set under its slot (it lives on as out_detached[i])
     g->flg_drop.assign(slot, slot + n);
@@ -2861,8 +2865,13 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
     hipLaunchKernelGGL(k_bc_install, dim3(nblk(n)), dim3(256), 0, st, n, ia);
     FGI_HIP(g, hipGetLastError());
     FGI_TRY(labels_map_out(g, dout, n));   // detached handles as the boundary numbers them
+    // the state view: the slots' new nodes and the detached handles handed out, from their words
+    FGI_TRY(view_refresh(g, kViewLabels, ds, n));
+    FGI_TRY(view_refresh(g, kViewHandles, dout, n));
+    FGI_TRY(view_flush(g));
     std::vector<uint32_t> od(n);
     FGI_TRY(d2h(g, od.data(), dout, n));
+    view_end(g);   // the copy waited for the flush
     g->free_detached.resize(g->free_detached.size() - take.size());
     if (out_detached) std::memcpy(out_detached, od.data(), n * sizeof(uint32_t));
     return FGI_OK;
@@ -2895,6 +2904,7 @@ fgi_status fgi_add_used(fgi_graph* g, uint32_t n, const uint32_t* dependant, con
     FGI_TRY(labels_map_in(g, ddep, n));
     FGI_TRY(labels_map_in(g, duse, n));
     FGI_TRY(fold(g));
+    view_begin(g);
     note_words(g);   // may set InvalidateOnSetOutput (Computed.cs:376-378)
     FGI_HIP(g, hipMemsetAsync(dhash, 0xFF, hcap * sizeof(unsigned long long), st));
     FGI_HIP(g, hipMemsetAsync(g->misc_dev, 0, 8 * sizeof(unsigned long long), st));
@@ -2926,8 +2936,12 @@ fgi_status fgi_add_used(fgi_graph* g, uint32_t n, const uint32_t* dependant, con
         }
     }
     FGI_HIP(g, hipGetLastError());
+    // the state view: a dependant may have gained InvalidateOnSetOutput
+    FGI_TRY(view_refresh(g, kViewLabels, ddep, n));
+    FGI_TRY(view_flush(g));
     if (out_result) FGI_TRY(d2h(g, out_result, dres, n));
     else FGI_HIP(g, hipStreamSynchronize(st));
+    view_end(g);   // the wait above covers the flush
     return FGI_OK;
 }
 
@@ -2950,6 +2964,7 @@ fgi_status fgi_set_output(fgi_graph* g, uint32_t n, const uint32_t* handle, uint
     FGI_TRY(h2d(g, dh, handle, n));
     FGI_TRY(labels_map_in(g, dh, n));
     FGI_TRY(fold(g));
+    view_begin(g);
     note_words(g);
     FGI_HIP(g, hipMemsetAsync(g->misc_dev, 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_set_output, dim3(nblk(n)), dim3(256), 0, st, n, dh, g->n_handles,
@@ -2959,6 +2974,11 @@ fgi_status fgi_set_output(fgi_graph* g, uint32_t n, const uint32_t* handle, uint
     if (out_set) FGI_TRY(d2h(g, out_set, dset, n));
     g->last_wave_n = 0;
     if (nr) FGI_TRY(run_wave(g, (uint32_t)nr, droots, nullptr, stats));   // Invalidate() (Computed.cs:153-156)
+    if (view_on(g)) {   // the handles' new states (Consistent, or what the cascade left) from their words and visit bits
+        view_begin(g);
+        FGI_TRY(view_refresh(g, kViewLabels, dh, n));
+        FGI_TRY(view_commit(g));
+    }
     return copy_ids(g, out_ids, cap, out_n);
 }
 
@@ -3353,6 +3373,21 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
             g->bflg_runs.push_back(r);
         }
     };
+    // The state view after a batch: every handle a step may have changed, refreshed once from the post-batch
+    // words (a slot one step's cascade invalidated and a later step began again ends Computing): the steps'
+    // own handles, the detached handles handed out, the cascades' invalidated ids and their flagged records.
+    // Queued behind the batch's own wait, so one more wait (fgi_view_stats.extra_waits).
+    auto view_sync = [&]() -> fgi_status {
+        if (!view_on(g)) return FGI_OK;
+        for (uint32_t k = 0; k < n_steps; ++k) {
+            FGI_TRY(view_refresh(g, kViewLabels, bs[k].h, steps[k].n));
+            if (steps[k].kind == FGI_STEP_BEGIN_COMPUTE) FGI_TRY(view_refresh(g, kViewLabels, bs[k].out32, steps[k].n));
+        }
+        FGI_TRY(view_refresh(g, kViewHandles, g->bout, std::min<uint64_t>(scr_h[1], g->bout_cap)));
+        if (rec_on) FGI_TRY(view_refresh(g, kViewRecords, g->brec, std::min<uint64_t>(scr_h[rcur_word], g->brec_cap)));
+        return view_commit(g);
+    };
+    view_begin(g);
     while (true) {
         fgi_status s = batch_launch(g, from, n_steps, steps, bs, scr, take, n_take, timed, wave_ev, rec_on ? &sink : nullptr);
         if (s != FGI_OK) return s;
@@ -3404,11 +3439,13 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
         // out of detached handles at step k: steps before it are applied
         note_runs(k);
         g->free_detached.resize(g->free_detached.size() - (size_t)scr_h[2]);
+        FGI_TRY(view_sync());   // the steps before k are applied
         return set_err(g, FGI_ECAPACITY, "step %u: out of detached handles (%zu free)", k, g->free_detached.size());
     }
     // host bookkeeping: the cascades' record runs, the detached handles taken, the per-step outputs
     note_runs(n_steps);
     g->free_detached.resize(g->free_detached.size() - (size_t)scr_h[2]);
+    FGI_TRY(view_sync());
     for (uint32_t k = 0; k < n_steps; ++k) {
         const fgi_step& sp = steps[k];
         if (!sp.out || !sp.n) continue;
@@ -3710,12 +3747,20 @@ fgi_status fgi_release(fgi_graph* g, uint32_t n, const uint32_t* handle) {
     hipSetDevice(g->device);
     FGI_TRY(fold(g));
     if (n) note_words(g);
+    view_begin(g);
+    // the state view follows the handles released so far, also when a later one is refused
+    auto leave = [&](uint32_t released, fgi_status st) {
+        if (!view_on(g)) return st;
+        fgi_status vs = view_refresh_host(g, handle, released);
+        if (vs == FGI_OK) vs = view_commit(g);
+        return st != FGI_OK ? st : vs;
+    };
     for (uint32_t i = 0; i < n; ++i) {
         if (handle[i] < g->ext_slots || handle[i] >= g->ext_handles)
-            return set_err(g, FGI_EINVAL, "handle %u is not detached", handle[i]);
+            return leave(i, set_err(g, FGI_EINVAL, "handle %u is not detached", handle[i]));
         const uint32_t h = handle[i] + g->lbl_K;   // a detached handle's label
         if (std::find(g->free_detached.begin(), g->free_detached.end(), h) != g->free_detached.end())
-            return set_err(g, FGI_EINVAL, "handle %u released twice", h);
+            return leave(i, set_err(g, FGI_EINVAL, "handle %u released twice", h));
         const uint64_t zero = 0;
         const uint32_t z32 = 0;
         FGI_TRY(h2d(g, g->node + h, &zero, 1));
@@ -3726,7 +3771,7 @@ fgi_status fgi_release(fgi_graph* g, uint32_t n, const uint32_t* handle) {
         g->free_detached.push_back(h);
         touch(g);
     }
-    return FGI_OK;
+    return leave(n, FGI_OK);
 }
 
 // ---- partitioned mutations, prune and batches ----------------------

@@ -219,7 +219,7 @@ fgi_status fgi_synth_layered(fgi_graph* g, uint32_t levels, uint32_t width, uint
                        fanout, seed, keys);
     fgi_status st = hipGetLastError() == hipSuccess ? synth_rows(g, m, keys, seed, 0, 0) : FGI_EDEVICE;
     hipFree(keys);
-    return st;
+    return st == FGI_OK ? view_rebuild(g) : st;   // a new node table: the state view's full build
 }
 
 fgi_status fgi_synth_rmat(fgi_graph* g, uint32_t scale, uint32_t edge_factor, uint64_t seed, uint32_t stale_pct,
@@ -234,7 +234,7 @@ fgi_status fgi_synth_rmat(fgi_graph* g, uint32_t scale, uint32_t edge_factor, ui
     if (!g->lbl_K) FGI_TRY(exp_relabel(g, 1u << scale, keys, m));
     fgi_status st = synth_rows(g, m, keys, seed, stale_pct, stale_seed);
     hipFree(keys);
-    return st;
+    return st == FGI_OK ? view_rebuild(g) : st;
 }
 
 }  // extern "C"

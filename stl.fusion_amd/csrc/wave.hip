@@ -91,16 +91,6 @@ __device__ __forceinline__ int first_visit(unsigned long long w) {
     return 0;
 }
 
-// The node word after a (non-immediate) visit: canonical, flags of an Invalidated node cleared.
-__host__ __device__ __forceinline__ unsigned long long visited_word(unsigned long long w) {
-    if ((w & kVMask) == 0) return w;
-    const uint32_t st = word_state(w);
-    if (st == FGI_COMPUTING) return w | kW_IOSO;
-    if (st == FGI_CONSISTENT)
-        return (w & kW_HasDelay) ? (w | kW_DS) : ((w & (kVMask | kW_HasDelay)) | kW_Invalidated);
-    return w;
-}
-
 // Invalidate(immediately: true) on a canonical word (Computed.cs:162-191: the delay is ignored).
 __device__ __forceinline__ unsigned long long imm_word(unsigned long long w) {
     const uint32_t st = word_state(w);
@@ -3920,7 +3910,7 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
     // fused launches when the wave's directions are settled (lists ready, or push only); a wave that
     // may still have to build the dependency lists part-way runs as level groups below
 #if FGI_VARIANTS
-    if ((g->opt_fused & kFusedOn) && !g->lbl_K && !g->flag_gate && (allow_pull || wp0.direction == 1)) {   // labels, flagged sets: level groups
+    if ((g->opt_fused & kFusedOn) && !g->lbl_K && !g->flag_gate && !view_on(g) && (allow_pull || wp0.direction == 1)) {   // labels, flagged sets: level groups
         WaveParams wp = wp0;
         if (!allow_pull) wp.direction = 1;
         const fgi_status r = run_wave_fused(g, n_roots, roots_dev, imm_dev, stats, wp, timing, t0);
@@ -3930,6 +3920,10 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
     // the previous wave left the counters, statistics and invalidated bitmap zeroed (WaveEnd) and the visit
     // bitmap is clean (fgi_restore swapped in the spare): no init kernel, the roots kernel stamps t0
     const bool clean_start = g->wave_clean && !g->vis_stale && n_roots != 0;
+    // a state view (view.hip) follows the wave: its update rides on every level group, queued between the
+    // final collect and the publish the host waits for, so the view is exact when the wait returns
+    const bool view = view_on(g) && n_roots != 0;
+    if (view) view_begin(g);
     wave_start(g, !clean_start, true);
 #if FGI_PROBE
     {
@@ -3947,9 +3941,10 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
     // the list kernel and the publish of a group leave the state clean once the wave is over (WaveEnd):
     // only when the list kernel runs (ids wanted, not the measurement-only merged publish)
     static const bool list_pub = getenv("FGI_LIST_PUBLISH") && getenv("FGI_LIST_PUBLISH")[0] == '1';
-    const bool merged = FGI_SPIN_WAIT && g->want_ids && list_pub;
-    // (a graph that can flag keeps the invalidated bitmap for the flagged-set post-pass: launch_flagged)
-    const bool leave_clean = g->want_ids && !merged && FGI_SPIN_WAIT && !g->flag_gate;
+    const bool merged = FGI_SPIN_WAIT && g->want_ids && list_pub && !view;
+    // (a graph that can flag keeps the invalidated bitmap for the flagged-set post-pass: launch_flagged;
+    // one with a state view open keeps it for the view's update)
+    const bool leave_clean = g->want_ids && !merged && FGI_SPIN_WAIT && !g->flag_gate && !view_on(g);
     // Levels run in groups between host synchronisations (one ~30 us round trip each); the first
     // group is sized by the previous wave's depth, so a repeated workload syncs once per wave and an
     // overshoot costs only empty levels (two ~2 us launches each). Every group ends with the final
@@ -3995,6 +3990,10 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
         FGI_HIP(g, launch_final(g, g->n_handles, g->want_ids, nullptr, lp, we));   // idempotent: repeated if the wave goes on
         final_done = true;
         FGI_HIP(g, hipGetLastError());
+        if (view) {   // idempotent, as the final collect: repeated if the wave goes on
+            FGI_TRY(view_wave(g));
+            FGI_TRY(view_flush(g));
+        }
         // the wave's end marker rides on the group's synchronisation (re-recorded if the wave goes on):
         // recording it after the wait would cost the call a further device round trip
         if (merged) FGI_TRY(counters_published(g, s, events, lp.seq));
@@ -4073,7 +4072,14 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
     if (g->flag_gate && final_done) {
         FGI_TRY(launch_flagged(g, 0));
         g->flg_last = 0;
+        // the nodes the wave only flagged reach the view from the post-pass's records, which are queued
+        // behind the wait above: one more wait (fgi_view_stats.extra_waits)
+        if (view) {
+            FGI_TRY(view_refresh(g, kViewRecords, g->flg_out[0], g->n_handles, g->flg_cnt));
+            FGI_TRY(view_commit(g));
+        }
     }
+    if (view) view_end(g);
     if (imm_dev && n_roots) note_words(g);   // immediate roots changed node words
     // the last group's list kernel and publish saw the wave over (the host's loop ends on the same test)
     g->wave_clean = leave_clean && final_done;
@@ -4144,7 +4150,9 @@ fgi_status run_wave_async(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_
     // publish leave the state clean for the next wave (WaveEnd)
     // (not on a graph that can flag: the flagged-set post-pass reads the invalidated bitmap after the list)
     WaveEnd we{};
-    if (!g->flag_gate) {
+    const bool view = view_on(g) && n_roots != 0;   // the wave's view update is queued before its publish
+    if (view) view_begin(g);
+    if (!g->flag_gate && !view_on(g)) {
         we = WaveEnd{g->ctr, group, 1, g->blk_stats, g->inv_bm, ((uint64_t)g->n_handles + 63) / 64,
                      g->spare_dirty ? g->vis_spare : nullptr};
         g->spare_dirty = false;
@@ -4152,6 +4160,11 @@ fgi_status run_wave_async(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_
     FGI_HIP(g, launch_final(g, g->n_handles, true, out, ListPub{}, we));
     const bool flg = g->flag_gate && n_roots != 0;
     if (flg) FGI_TRY(launch_flagged(g, (int)(t & 1)));
+    if (view) {
+        FGI_TRY(view_wave(g));
+        if (flg) FGI_TRY(view_refresh(g, kViewRecords, g->flg_out[t & 1], g->n_handles, g->flg_cnt + (t & 1)));
+        FGI_TRY(view_flush(g));
+    }
     const unsigned long long seq = ++g->apub_seq;
     hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, s, reinterpret_cast<const unsigned long long*>(g->ctr),
                        (uint32_t)kPubWords, g->apub[t & 1], seq, we);
@@ -4230,6 +4243,7 @@ fgi_status wave_wait(fgi_graph* g, uint64_t ticket, uint64_t* out_n, const uint3
         return ws;
     }
     a.busy = false;
+    view_end(g);   // exact again unless the other ticket's wave is still in flight
     const WaveCtr& c = *reinterpret_cast<const WaveCtr*>(pub);
     if (c.broken) {
         // the wave's tail left at a timed-out grid barrier: the wave is half applied (as run_wave's level

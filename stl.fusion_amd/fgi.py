@@ -94,6 +94,58 @@ class PruneStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class StateViewStruct(C.Structure):
+    """fgi_state_view: the six bit planes of the host-memory state view and its sequence word."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_handles", C.c_uint32), ("words", C.c_uint64),
+                ("registered", C.c_void_p), ("consistent", C.c_void_p), ("computing", C.c_void_p),
+                ("ioso", C.c_void_p), ("delay_started", C.c_void_p), ("has_delay", C.c_void_p), ("seq", C.c_void_p)]
+
+
+class ViewStats(C.Structure):
+    _fields_ = [("updates", C.c_uint64), ("words_published", C.c_uint64), ("full_builds", C.c_uint64),
+                ("extra_waits", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+VIEW_PLANES = ("registered", "consistent", "computing", "ioso", "delay_started", "has_delay")
+
+
+class StateView:
+    """Read-only numpy views of a graph's state planes (host memory the device keeps current): bit h % 64
+    of word h // 64 of each plane addresses boundary handle h. Reading costs no engine call."""
+
+    def __init__(self, sv: StateViewStruct):
+        self.struct = sv
+        self.n_handles = int(sv.n_handles)
+        self.words = int(sv.words)
+
+        def plane(addr, n):
+            a = np.ctypeslib.as_array((C.c_uint64 * n).from_address(addr))
+            a.setflags(write=False)
+            return a
+        for name in VIEW_PLANES:
+            setattr(self, name, plane(getattr(sv, name), self.words))
+        self._seq = plane(sv.seq, 1)
+
+    @property
+    def seq(self) -> int:
+        return int(self._seq[0])
+
+    def _bits(self, plane: np.ndarray) -> np.ndarray:
+        return np.unpackbits(plane.copy().view(np.uint8), bitorder="little")[:self.n_handles].astype(np.uint32)
+
+    def flags(self) -> np.ndarray:
+        """The canonical state_flags of every handle (dump_states' encoding; 0 for an empty handle)."""
+        reg, con, cmp_, ioso, ds, hd = (self._bits(getattr(self, n)) for n in VIEW_PLANES)
+        f = np.where(con == 1, 1 | (ds << 3), np.where(cmp_ == 1, (ioso << 2) | (ds << 3), 2)).astype(np.uint32)
+        return ((f | (hd << 4)) * reg).astype(np.uint32)
+
+    def is_consistent(self, h: int) -> bool:
+        return bool((int(self.consistent[h >> 6]) >> (h & 63)) & 1) if 0 <= h < self.n_handles else False
+
+
 _u32p = C.POINTER(C.c_uint32)
 _u64p = C.POINTER(C.c_uint64)
 _u8p = C.POINTER(C.c_uint8)
@@ -170,6 +222,12 @@ SIGNATURES = {
                                        C.POINTER(_u32p)],
     "fgi_part_local_load_shards": [C.POINTER(C.c_void_p), C.c_uint32, _u64p, C.POINTER(_u32p), C.POINTER(_u32p),
                                    C.POINTER(_u64p)],
+    "fgi_state_view_open": [_G, C.POINTER(StateViewStruct)],
+    "fgi_state_view_close": [_G],
+    "fgi_state_view_stats": [_G, C.POINTER(ViewStats)],
+    # the exported copies of fgi.h's inline read helpers (they return an int / the state_flags word, not a status)
+    "fgi_view_is_consistent": [C.POINTER(StateViewStruct), C.c_uint32],
+    "fgi_view_flags": [C.POINTER(StateViewStruct), C.c_uint32],
 }
 
 _lib = None
@@ -571,6 +629,22 @@ class Graph:
     def release(self, handles):
         h = _u32(handles)
         self._check(self.lib.fgi_release(self.h, len(h), _ptr(h, C.c_uint32)), "release")
+
+    # ---- host-memory state view ----
+    def open_state_view(self) -> StateView:
+        """Opens (or returns again) the state view: exact when this returns and after every synchronous call."""
+        sv = StateViewStruct()
+        sv.struct_size = C.sizeof(StateViewStruct)
+        self._check(self.lib.fgi_state_view_open(self.h, C.byref(sv)), "open_state_view")
+        return StateView(sv)
+
+    def close_state_view(self):
+        self._check(self.lib.fgi_state_view_close(self.h), "close_state_view")
+
+    def view_stats(self) -> ViewStats:
+        vs = ViewStats()
+        self._check(self.lib.fgi_state_view_stats(self.h, C.byref(vs)), "view_stats")
+        return vs
 
     def snapshot(self):
         self._check(self.lib.fgi_snapshot(self.h), "snapshot")

@@ -11,6 +11,11 @@ namespace {
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint64_t kParallelMin = 1u << 16;   // ids below this fan out on the dispatcher thread
 
+// every call into the engine is counted (ComputedRegistry::EngineCalls): in the registry's own methods,
+// and in Computed's through its registry
+#define FGI_CALL(fn, ...) (++calls_, fn(__VA_ARGS__))
+#define FGI_RCALL(fn, ...) (++reg_->calls_, fn(__VA_ARGS__))
+
 double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -60,17 +65,25 @@ ComputedRegistry::ComputedRegistry(uint32_t n_slots, uint32_t n_detached, int de
     cfg.n_slots = n_slots;
     cfg.n_detached = n_detached;
     cfg.world = 1;
-    fgi_status s = fgi_create(&cfg, &g_);
+    fgi_status s = FGI_CALL(fgi_create, &cfg, &g_);
     if (s != FGI_OK) throw FgiError(s, "fgi_create failed (no GPU?)");
+    // the nodes' states are read from host memory the engine keeps current (Computed::Flags)
+    view_.struct_size = sizeof(view_);
+    s = FGI_CALL(fgi_state_view_open, g_, &view_);
+    if (s != FGI_OK) {
+        const std::string why = fgi_last_error(g_);
+        fgi_destroy(g_);
+        throw FgiError(s, "fgi_state_view_open: " + why);
+    }
     n_handles_ = n_slots + n_detached;
     current_.resize(n_slots);
     has_obj_.assign(n_handles_, 0);
 }
 
-ComputedRegistry::~ComputedRegistry() { fgi_destroy(g_); }
+ComputedRegistry::~ComputedRegistry() { FGI_CALL(fgi_destroy, g_); }
 
 void ComputedRegistry::Check(fgi_status s, const char* what) const {
-    if (s != FGI_OK) throw FgiError(s, std::string(what) + ": " + fgi_last_error(g_));
+    if (s != FGI_OK) throw FgiError(s, std::string(what) + ": " + FGI_CALL(fgi_last_error, g_));
 }
 
 uint32_t ComputedRegistry::SlotOf(const std::string& input, bool create) {
@@ -128,7 +141,7 @@ std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& inpu
     const uint8_t hd = has_delay ? 1 : 0;
     uint32_t detached = FGI_NONE;
     fgi_wave_stats ws{};
-    Check(fgi_begin_compute(g_, 1, &s, &c->version_, &hd, &detached, &ws), "fgi_begin_compute");
+    Check(FGI_CALL(fgi_begin_compute, g_, 1, &s, &c->version_, &hd, &detached, &ws), "fgi_begin_compute");
     StartTimers(0);   // the delayed nodes the displacement cascade reached
     auto old = current_[s];
     if (detached != FGI_NONE) {   // displaced but alive (Computing / delayed): its handle moves
@@ -144,20 +157,20 @@ std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& inpu
                 timers_[detached] = it->second;
                 timers_.erase(s);
             } else {
-                uint64_t v = 0;
-                uint32_t f = 0;
-                Check(fgi_get_state(g_, 1, &detached, &v, &f), "fgi_get_state");
+                const uint32_t f = fgi_view_flags(&view_, detached);   // the handle names the old node alone
                 if ((f & FGI_STATE_MASK) == FGI_CONSISTENT && (f & FGI_F_INVALIDATION_DELAY_STARTED))
                     StartTimer(detached, old->version_, old->delay_);
             }
         }
         MoveSubs(s, detached);   // the replicas follow the old node
+    } else if (old) {
+        old->gone_ = true;   // the slot names the new node from here on (its handlers may still read its state)
     }
     // the displacement cascade's invalidated nodes (the old node among them) get their handlers
     if (ws.v_inv) {
         uint64_t n = 0;
         uint32_t* ids = IdsBuffer(ws.v_inv);
-        Check(fgi_last_wave_ids(g_, ids, ws.v_inv, &n), "fgi_last_wave_ids");
+        Check(FGI_CALL(fgi_last_wave_ids, g_, ids, ws.v_inv, &n), "fgi_last_wave_ids");
         last_ = ws;
         Dispatch(ids, n);
     }
@@ -177,7 +190,7 @@ uint32_t ComputedRegistry::AddUsed(Computed& dependant, Computed& used) {
     Sync();
     uint32_t out = 0;
     const uint32_t d = dependant.handle_, u = used.handle_;
-    Check(fgi_add_used(g_, 1, &d, &u, &out), "fgi_add_used");
+    Check(FGI_CALL(fgi_add_used, g_, 1, &d, &u, &out), "fgi_add_used");
     return out;
 }
 
@@ -187,10 +200,10 @@ bool ComputedRegistry::SetOutput(Computed& c) {
     const uint32_t h = c.handle_;
     uint64_t n = 0;
     uint32_t* ids = IdsBuffer(1024);
-    fgi_status s = fgi_set_output(g_, 1, &h, &set, ids, ids_cap_, &n, &last_);
+    fgi_status s = FGI_CALL(fgi_set_output, g_, 1, &h, &set, ids, ids_cap_, &n, &last_);
     if (s == FGI_ECAPACITY) {   // the cascade completed; fetch its ids with the right size
         ids = IdsBuffer(n);
-        s = fgi_last_wave_ids(g_, ids, n, &n);
+        s = FGI_CALL(fgi_last_wave_ids, g_, ids, n, &n);
     }
     Check(s, "fgi_set_output");
     StartTimers(0);
@@ -209,17 +222,17 @@ void ComputedRegistry::RunWave(const uint32_t* roots, size_t n_roots, const uint
     if (use_bits) {
         if (!bits_) bits_.reset(new uint64_t[words]);
         uint64_t* bits = bits_.get();
-        Check(fgi_invalidate_bits(g_, (uint32_t)n_roots, roots, imm, bits, words, &n, &last_), "fgi_invalidate_bits");
+        Check(FGI_CALL(fgi_invalidate_bits, g_, (uint32_t)n_roots, roots, imm, bits, words, &n, &last_), "fgi_invalidate_bits");
         pred_v_ = n;
         StartTimers(0);
         DispatchBits(bits, words, n);
         return;
     }
     uint32_t* ids = IdsBuffer(1024);
-    fgi_status s = fgi_invalidate(g_, (uint32_t)n_roots, roots, imm, ids, ids_cap_, &n, &last_);
+    fgi_status s = FGI_CALL(fgi_invalidate, g_, (uint32_t)n_roots, roots, imm, ids, ids_cap_, &n, &last_);
     if (s == FGI_ECAPACITY) {   // the wave itself completed; fetch the ids with the right size
         ids = IdsBuffer(n);
-        s = fgi_last_wave_ids(g_, ids, n, &n);
+        s = FGI_CALL(fgi_last_wave_ids, g_, ids, n, &n);
     }
     Check(s, "fgi_invalidate");
     pred_v_ = n;
@@ -331,7 +344,7 @@ void ComputedRegistry::DispatchImpl(const uint32_t* ids, const uint64_t* bits, u
             if (it != detached_.end() && it->second == o.second) {
                 detached_.erase(it);
                 has_obj_[h] = 0;
-                fgi_release(g_, 1, &h);
+                FGI_CALL(fgi_release, g_, 1, &h);
             }
         }
     fan.gather_ms = ms_since(t0);
@@ -472,7 +485,7 @@ uint64_t ComputedRegistry::InvalidateSlotsAsync(const std::vector<uint32_t>& roo
     // a third wave makes the library wait for the oldest: complete it here so its fan-out runs in order
     while (pending_.size() >= 2) Complete(pending_.front());
     uint64_t t = 0;
-    Check(fgi_invalidate_async_host(g_, (uint32_t)roots.size(), roots.data(),
+    Check(FGI_CALL(fgi_invalidate_async_host, g_, (uint32_t)roots.size(), roots.data(),
                                     imm && imm->size() == roots.size() ? imm->data() : nullptr, &t),
           "fgi_invalidate_async_host");
     pending_.push_back(t);
@@ -487,10 +500,10 @@ void ComputedRegistry::Complete(uint64_t ticket) {
         fgi_wave_stats ws{};
         uint64_t n = 0;
         uint32_t* ids = IdsBuffer(1024);
-        fgi_status s = fgi_wave_wait_ids(g_, t, ids, ids_cap_, &n, &ws);
+        fgi_status s = FGI_CALL(fgi_wave_wait_ids, g_, t, ids, ids_cap_, &n, &ws);
         if (s == FGI_ECAPACITY) {   // the wave completed; fetch its ids with the right size
             ids = IdsBuffer(n);
-            s = fgi_wave_wait_ids(g_, t, ids, n, &n, nullptr);
+            s = FGI_CALL(fgi_wave_wait_ids, g_, t, ids, n, &n, nullptr);
         }
         Check(s, "fgi_wave_wait_ids");
         last_ = ws;
@@ -526,7 +539,7 @@ void ComputedRegistry::StartTimer(uint32_t handle, LTag version, std::chrono::na
 
 void ComputedRegistry::StartTimers(uint64_t ticket) {
     auto read = [&](uint32_t* ids, uint32_t* flags, uint64_t cap, uint64_t* n) {
-        return ticket ? fgi_wave_wait_flagged(g_, ticket, ids, flags, cap, n) : fgi_last_wave_flagged(g_, ids, flags, cap, n);
+        return ticket ? FGI_CALL(fgi_wave_wait_flagged, g_, ticket, ids, flags, cap, n) : FGI_CALL(fgi_last_wave_flagged, g_, ids, flags, cap, n);
     };
     uint64_t n = 0;
     Check(read(nullptr, nullptr, 0, &n), "fgi_last_wave_flagged");
@@ -551,7 +564,7 @@ void ComputedRegistry::StartTimers(uint64_t ticket) {
     if (bare.empty() || DefaultInvalidationDelay <= std::chrono::nanoseconds::zero()) return;
     std::vector<uint64_t> ver(bare.size());
     std::vector<uint32_t> fl(bare.size());
-    Check(fgi_get_state(g_, (uint32_t)bare.size(), bare.data(), ver.data(), fl.data()), "fgi_get_state");
+    Check(FGI_CALL(fgi_get_state, g_, (uint32_t)bare.size(), bare.data(), ver.data(), fl.data()), "fgi_get_state");
     for (size_t i = 0; i < bare.size(); ++i) StartTimer(bare[i], ver[i], std::chrono::nanoseconds::zero());
 }
 
@@ -585,7 +598,7 @@ size_t ComputedRegistry::RunDueTimers() {
     // the entry fires only for the node it was started for, still waiting (Consistent, DelayStarted)
     std::vector<uint64_t> ver(due.size());
     std::vector<uint32_t> fl(due.size());
-    Check(fgi_get_state(g_, (uint32_t)due.size(), due.data(), ver.data(), fl.data()), "fgi_get_state");
+    Check(FGI_CALL(fgi_get_state, g_, (uint32_t)due.size(), due.data(), ver.data(), fl.data()), "fgi_get_state");
     std::vector<uint32_t> roots;
     for (size_t i = 0; i < due.size(); ++i)
         if (ver[i] == entries[i].second && (fl[i] & FGI_STATE_MASK) == FGI_CONSISTENT &&
@@ -635,10 +648,10 @@ void ComputedRegistry::InvalidateEverything() {
     uint64_t n = 0;
     last_ = fgi_wave_stats{};
     uint32_t* ids = IdsBuffer(1024);
-    fgi_status s = fgi_invalidate_all(g_, ids, ids_cap_, &n, &last_);
+    fgi_status s = FGI_CALL(fgi_invalidate_all, g_, ids, ids_cap_, &n, &last_);
     if (s == FGI_ECAPACITY) {
         ids = IdsBuffer(n);
-        s = fgi_last_wave_ids(g_, ids, n, &n);
+        s = FGI_CALL(fgi_last_wave_ids, g_, ids, n, &n);
     }
     Check(s, "fgi_invalidate_all");
     StartTimers(0);
@@ -648,20 +661,29 @@ void ComputedRegistry::InvalidateEverything() {
 std::pair<uint64_t, uint64_t> ComputedRegistry::Prune() {
     Sync();
     fgi_prune_stats ps{};
-    Check(fgi_prune(g_, &ps), "fgi_prune");
+    Check(FGI_CALL(fgi_prune, g_, &ps), "fgi_prune");
     return {ps.old_edges, ps.new_edges};
+}
+
+bool ComputedRegistry::Owns(const Computed& c) const {
+    if (c.gone_) return false;
+    if (c.handle_ < n_slots_) return current_[c.handle_].get() == &c;
+    auto it = detached_.find(c.handle_);
+    return it != detached_.end() && it->second.get() == &c;
 }
 
 // ---- Computed --------------------------------------------------------------------------------------
 ConsistencyState Computed::State() const { return (ConsistencyState)(Flags() & FGI_STATE_MASK); }
 
+bool Computed::IsConsistent() const {
+    reg_->CompletePending();
+    return reg_->Owns(*this) && fgi_view_is_consistent(&reg_->view_, handle_);
+}
+
 uint32_t Computed::Flags() const {
     reg_->CompletePending();   // the state includes the waves in flight (their handlers run first)
-    uint64_t v = 0;
-    uint32_t f = 0;
-    reg_->Check(fgi_get_state(reg_->g_, 1, &handle_, &v, &f), "fgi_get_state");
-    if (v != version_) return FGI_INVALIDATED;   // the slot moved on: this node is gone
-    return f;
+    if (!reg_->Owns(*this)) return FGI_INVALIDATED;   // the slot moved on, or the handle was released: this node is gone
+    return fgi_view_flags(&reg_->view_, handle_);
 }
 
 void Computed::Invalidate(bool immediately) {
@@ -708,10 +730,10 @@ std::shared_future<void> Computed::WhenInvalidated() {
 
 std::vector<std::pair<uint32_t, LTag>> Computed::UsedBy() const {
     uint64_t n = 0;
-    fgi_get_used_by(reg_->g_, handle_, nullptr, nullptr, 0, &n);
+    FGI_RCALL(fgi_get_used_by, reg_->g_, handle_, nullptr, nullptr, 0, &n);
     std::vector<uint32_t> d(n);
     std::vector<uint64_t> t(n);
-    reg_->Check(fgi_get_used_by(reg_->g_, handle_, d.data(), t.data(), n, &n), "fgi_get_used_by");
+    reg_->Check(FGI_RCALL(fgi_get_used_by, reg_->g_, handle_, d.data(), t.data(), n, &n), "fgi_get_used_by");
     std::vector<std::pair<uint32_t, LTag>> out;
     for (uint64_t i = 0; i < n; ++i) out.emplace_back(d[i], t[i]);
     return out;
@@ -719,7 +741,7 @@ std::vector<std::pair<uint32_t, LTag>> Computed::UsedBy() const {
 
 uint32_t Computed::UsedCount() const {
     uint32_t c = 0;
-    reg_->Check(fgi_get_used_count(reg_->g_, handle_, &c), "fgi_get_used_count");
+    reg_->Check(FGI_RCALL(fgi_get_used_count, reg_->g_, handle_, &c), "fgi_get_used_count");
     return c;
 }
 

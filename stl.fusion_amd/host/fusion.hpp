@@ -98,9 +98,13 @@ class Computed {
     const std::string& Input() const { return input_; }
     LTag Version() const { return version_; }
     uint32_t Handle() const { return handle_; }
+    // The node's state is read from the registry's host-memory state view (fgi_state_view_open): a load,
+    // no engine call, once the asynchronous waves in flight are completed (their handlers run first).
+    // A node that is gone — its slot holds a newer object, or its detached handle was released — reads
+    // as Invalidated; that is decided on the host (the slot's current object, the detached map).
     ConsistencyState State() const;
     uint32_t Flags() const;   // fgi state_flags (InvalidateOnSetOutput, DelayStarted, hasDelay)
-    bool IsConsistent() const { return State() == ConsistencyState::Consistent; }
+    bool IsConsistent() const;   // one load, one bit test
     bool IsInvalidated() const { return State() == ConsistencyState::Invalidated; }
     // IComputed.Invalidate(immediately): inside a Computed.Invalidate() scope the node joins the
     // scope's batch; otherwise one wave runs now.
@@ -125,6 +129,7 @@ class Computed {
     uint32_t slot_ = 0, handle_ = 0;
     LTag version_ = 0;
     bool fired_ = false;
+    bool gone_ = false;   // displaced without a detached handle: the slot names the newer node
     InvalidatedHandlerSet handlers_;
     std::chrono::nanoseconds delay_{0};          // ComputedOptions.InvalidationDelay (0: none, max(): never)
     std::shared_ptr<std::promise<void>> when_;   // WhenInvalidated's promise, once asked for
@@ -253,6 +258,10 @@ class ComputedRegistry {
     size_t BatchChunk = 65536;
 
     fgi_graph* Graph() const { return g_; }
+    // the registry's state view (opened at construction): any thread may read it
+    const fgi_state_view& View() const { return view_; }
+    // every fgi_* call the mirror has made so far (a state read makes none)
+    uint64_t EngineCalls() const { return calls_; }
     const fgi_wave_stats& LastWave() const { return last_; }
     const FanoutStats& LastFanout() const { return fan_; }
 
@@ -281,8 +290,12 @@ class ComputedRegistry {
     void ReportAccess(Computed& c, bool is_new);
     LTag NextVersion(LTag current);
     void MoveSubs(uint32_t from, uint32_t to);
+    // `c` is the object its handle names: the slot's current node, or the detached map's entry
+    bool Owns(const Computed& c) const;
 
     fgi_graph* g_ = nullptr;
+    fgi_state_view view_{};
+    mutable uint64_t calls_ = 0;
     uint32_t n_slots_ = 0, n_handles_ = 0;
     std::unordered_map<std::string, uint32_t> slots_;
     std::vector<std::shared_ptr<Computed>> current_;                 // slot -> newest node
