@@ -200,8 +200,8 @@ fgi_status fgi_get_degrees(fgi_graph* g, uint32_t* degree /*n_slots+n_detached, 
  * kernel again (as on a graph that can flag), and a call on a graph that can flag waits once more for
  * the device (fgi_view_stats.extra_waits); on a graph that cannot flag a wave's view update is queued
  * before the wave's own publish and costs no further wait.
- * FGI_ENOTSUP on a partitioned graph (a partition's view is out of scope: each rank would hold its
- * slots' share); FGI_ESTATE on a poisoned graph. After a call that failed with FGI_EDEVICE the view is
+ * FGI_ENOTSUP on a partitioned graph (each rank holds its slots' share: fgi_part_state_view_open
+ * below); FGI_ESTATE on a poisoned graph. After a call that failed with FGI_EDEVICE the view is
  * undefined until fgi_restore; fgi_restore with a view open returns only once the view shows the
  * snapshot's states (it waits for the device; without a view it stays stream-ordered). fgi_destroy
  * closes the view; the planes stay mapped until then, a closed view is no longer updated, and a second
@@ -229,6 +229,22 @@ typedef struct fgi_view_stats {
 } fgi_view_stats;
 fgi_status fgi_state_view_stats(fgi_graph* g, fgi_view_stats* out);
 
+/* The same view per rank of a partition (C-ABI 0.7), over the rank's local boundary handles exactly as
+ * fgi_get_state and fgi_dump_states address them on that rank: bit h with h < cfg.n_slots is global slot
+ * rank * block + h (block = ceil(n_global / world)) in the host's numbering (partition codes are never
+ * visible), the rank's detached handles follow the slots, n_handles = n_slots + n_detached. Slot bits
+ * past the rank's last owned slot (the last rank when it owns fewer than block slots, or n_slots > block) stay 0 in every plane.
+ * *out_base (nullable) = rank * block. The contract is fgi_state_view_open's, per rank: when a
+ * synchronous fgi_part_* call returns on a rank, that rank's view is exact (fgi_part_local_*: every
+ * rank's, when the group call returns); *seq is written by the rank's own calling thread. No collective
+ * runs: a rank opens, reads and closes (fgi_state_view_close, fgi_state_view_stats) on its own, at any
+ * time, and a partition that never opens a view allocates and launches nothing for it. A wave's update
+ * rides on the wave's own last wait; a rank whose graph can flag waits once more per cascade. A direct
+ * mutation call waits once more for its own items: fgi_part_begin_compute and fgi_part_set_output at
+ * most twice with a view open (their cascade's flagged records, then their items), fgi_part_add_used
+ * once, fgi_release once; fgi_part_run_batch once for the whole batch (all counted in extra_waits). FGI_ENOTSUP on a graph that is not partitioned, FGI_ESTATE on a poisoned one. */
+fgi_status fgi_part_state_view_open(fgi_graph* g, fgi_state_view* out, uint32_t* out_base /*nullable*/);
+
 /* The read path. The helpers are inline C for hosts that include this header; the library also exports
  * them under the same names for bindings that cannot inline C (its own build defines
  * FGI_VIEW_OUT_OF_LINE). */
@@ -241,6 +257,12 @@ fgi_status fgi_state_view_stats(fgi_graph* g, fgi_view_stats* out);
 /* one load, one bit test */
 FGI_VIEW_INLINE int fgi_view_is_consistent(const fgi_state_view* v, uint32_t h) {
     return h < v->n_handles && FGI_VIEW_BIT(v->consistent, h);
+}
+/* A global slot over the p views of a partition's ranks (rank order; block = ceil(n_global / p)), for a
+ * host that runs the ranks in one process: one divide, one load, one bit test; 0 for slot >= p * block. */
+FGI_VIEW_INLINE int fgi_part_view_is_consistent(const fgi_state_view* views, uint32_t p, uint32_t block, uint32_t slot) {
+    const uint32_t r = block ? slot / block : p;
+    return r < p && fgi_view_is_consistent(views + r, slot - r * block);
 }
 /* the canonical state_flags of handle h (what fgi_get_state reports); 0 for an empty handle */
 FGI_VIEW_INLINE uint32_t fgi_view_flags(const fgi_state_view* v, uint32_t h) {
@@ -534,6 +556,10 @@ fgi_status fgi_stream(fgi_graph* g, void** stream);
  *                            launch that runs a wave's last small push levels, synchronous or
  *                            asynchronous waves): fgi_invalidate* / fgi_wave_wait return FGI_EDEVICE and
  *                            the graph is poisoned until fgi_restore
+ *   FGI_OPT_PART_VIEW_PATH [0] partitions with codes and a state view open (fgi_part_state_view_open):
+ *                            how a wave's invalidated set reaches the planes: 0 by the wave's size (gather
+ *                            from n_local / 16 invalidated handles on), 1 scatter, 2 gather. Results never
+ *                            depend on it (tests pin both paths on small graphs).
  *   FGI_OPT_RUN_OFFSET_BITS [28] tests only: a pull candidate's record names its tail run by an offset
  *                            below 2^bits words from its pull block's base; a candidate past that is
  *                            found through the per-slot list offsets instead (tests pin that path on
@@ -553,6 +579,7 @@ fgi_status fgi_stream(fgi_graph* g, void** stream);
 #define FGI_OPT_PART_BUCKET 14
 #define FGI_OPT_FAULT_INJECT_TAIL 16
 #define FGI_OPT_RUN_OFFSET_BITS 17
+#define FGI_OPT_PART_VIEW_PATH 18
 /* 12 and 15: the measurement variants' options (include/fgi_variants.h); FGI_ENOTSUP here */
 fgi_status fgi_set_option(fgi_graph* g, int option, int64_t value);
 

@@ -394,7 +394,16 @@ struct View {
     unsigned long long* pub_dev = nullptr; // words the flush kernels copied so far
     uint64_t pub_base = 0;                 // words the full builds copied
     uint64_t updates = 0, full_builds = 0, extra_waits = 0;
+    // a partition rank's view (fgi_part_state_view_open): its first slot and its owned slots (else 0, 0)
+    uint32_t part_base = 0, part_n_local = 0;
+    // fgi_part_run_batch: its steps leave the view alone (view_on is false) and list the rank's boundary
+    // handles they changed here; the batch refreshes them once, behind itself, from the post-batch words
+    bool deferred = false;
+    std::vector<uint32_t> pending;
 };
+// A partition rank's wave with codes (k_view_part_wave) gathers from n_local / kPartViewGatherDen invalidated
+// handles on and scatters below (FGI_OPT_PART_VIEW_PATH pins either)
+constexpr uint32_t kPartViewGatherDen = 16;
 
 }  // namespace fgi
 
@@ -717,6 +726,7 @@ struct fgi_graph {
     bool pflg_read = false, pflg_batch = false;
     uint32_t pflg_step = 0;
     fgi::View* view = nullptr;         // the host-memory state view (null until fgi_state_view_open)
+    int opt_part_view_path = 0;        // FGI_OPT_PART_VIEW_PATH: 0 by the wave's count, 1 scatter, 2 gather
 };
 
 // ---- internal entry points shared between translation units ----------------------------------
@@ -857,7 +867,9 @@ __host__ __device__ inline uint64_t pull_iters(uint64_t n, uint32_t grid) { retu
 // ---- the host-memory state view (view.hip) ----
 // Everything below but view_on is a no-op returning FGI_OK while no view is open; the queueing calls
 // launch on the graph's stream and do not wait.
-inline bool view_on(const fgi_graph* g) { return g->view && g->view->open; }
+inline bool view_on(const fgi_graph* g) { return g->view && g->view->open && !g->view->deferred; }
+// a partitioned batch is running with a view open: its steps list what they changed (View::pending)
+inline bool view_deferred(const fgi_graph* g) { return g->view && g->view->open && g->view->deferred; }
 // the view's sequence word: odd from a call's first launch that may touch the view ...
 void view_begin(fgi_graph* g);
 // ... even again once the view is exact (no asynchronous wave in flight)
@@ -866,10 +878,15 @@ void view_end(fgi_graph* g);
 fgi_status view_rebuild(fgi_graph* g);
 // a wave's invalidated bitmap (g->inv_bm, over labels) cleared out of `consistent` and `delay_started`
 fgi_status view_wave(fgi_graph* g);
+// the same for a partition rank's wave (its own inv_bm, over engine indices): k_view_wave without codes,
+// k_view_part_wave with them
+fgi_status view_part_wave(fgi_graph* g);
 // the planes' bits of listed handles from their node words (and unfolded visit bits). kind: kViewHandles
-// u32 boundary handles, kViewLabels u32 labels, kViewRecords u64 flagged records (handle << 32 | flags).
+// u32 boundary handles, kViewLabels u32 labels (a partition: the rank's engine indices), kViewRecords u64
+// flagged records (handle << 32 | flags; a partition: global slot << 32 | flags), kViewCodes u32 global
+// engine ids of a partition (the ones this rank owns are refreshed).
 // The list holds n entries, or *n_dev of them if that is less (n_dev nullable). FGI_NONE entries are skipped.
-enum { kViewHandles = 0, kViewLabels = 1, kViewRecords = 2 };
+enum { kViewHandles = 0, kViewLabels = 1, kViewRecords = 2, kViewCodes = 3 };
 fgi_status view_refresh(fgi_graph* g, int kind, const void* list_dev, uint64_t n, const unsigned long long* n_dev = nullptr);
 // the same for a host list of boundary handles (uploaded on the stream)
 fgi_status view_refresh_host(fgi_graph* g, const uint32_t* handles, uint64_t n);

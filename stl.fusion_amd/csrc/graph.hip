@@ -1913,7 +1913,8 @@ fgi_status fgi_version(uint32_t* major, uint32_t* minor) {
     // 0.2: fgi_last_wave_flagged, fgi_wave_wait_flagged; 0.3: fgi_last_batch_flagged; 0.4: fgi_part_last_flagged;
     // 0.5: fgi_part_register_shard, fgi_part_load_edges_shard and their in-process drivers
     // 0.6: the host-memory state view (fgi_state_view_open / _close / _stats, fgi_view_flags, fgi_view_is_consistent)
-    if (minor) *minor = 6;
+    // 0.7: the same view per rank of a partition (fgi_part_state_view_open, fgi_part_view_is_consistent)
+    if (minor) *minor = 7;
     return FGI_OK;
 }
 
@@ -2550,6 +2551,10 @@ fgi_status fgi_set_option(fgi_graph* g, int option, int64_t value) {
         g->opt_pull_beta = (int)value;
         return FGI_OK;
     case FGI_OPT_PART_PLAN: g->opt_part_plan = value ? 1 : 0; return FGI_OK;
+    case FGI_OPT_PART_VIEW_PATH:
+        if (value < 0 || value > 2) return set_err(g, FGI_EINVAL, "partition view path must be 0, 1 or 2");
+        g->opt_part_view_path = (int)value;
+        return FGI_OK;
     case FGI_OPT_PART_BUCKET: return part_set_bucket(g, value);
     case FGI_OPT_PROBE_SUMMARY:
         if (value < -1 || value > (int64_t)FGI_NONE) return set_err(g, FGI_EINVAL, "probe summary: -1 or a word count");
@@ -3794,6 +3799,12 @@ fgi_status part_take_ids(fgi_graph* g, const PartView& pv, std::vector<uint32_t>
     ids->resize(at + g->last_wave_n);
     FGI_TRY(d2h(g, ids->data() + at, g->inv, g->last_wave_n));
     for (size_t i = at; i < ids->size(); ++i) (*ids)[i] = part_slot_of(g, (*ids)[i] + pv.base);
+    // A batch's view update: the cascade's slots as this rank's handles. They go through the host because the
+    // batch copies them to the host for its caller anyway (this function's own download above); the refresh
+    // behind the batch uploads them again, O(v_inv) for a dense cascade. fgi_part_run_batch always passes
+    // `ids` (its own vector, whatever the caller asked for), which this relies on.
+    if (view_deferred(g))
+        for (size_t i = at; i < ids->size(); ++i) g->view->pending.push_back((*ids)[i] - pv.base);
     if (g->lbl_perm) std::sort(ids->begin() + (ptrdiff_t)at, ids->end());   // the cascade's slots, ascending
     return FGI_OK;
 }
@@ -3935,6 +3946,17 @@ fgi_status part_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, co
         FGI_HIP(g, hipGetLastError());
         FGI_TRY(d2h(g, od.data(), dout, m));
         g->free_detached.resize(g->free_detached.size() - take.size());
+        if (view_on(g)) {   // the owned slots' new nodes and the detached handles handed out (the cascade's share is in)
+            view_begin(g);
+            FGI_TRY(view_refresh(g, kViewLabels, ds, m));
+            FGI_TRY(view_refresh(g, kViewHandles, dout, m));
+            FGI_TRY(view_commit(g));
+        }
+        if (view_deferred(g))
+            for (uint32_t j = 0; j < m; ++j) {
+                g->view->pending.push_back(part_code_local_h(g, ls[j], true));
+                if (od[j] != FGI_NONE) g->view->pending.push_back(od[j]);
+            }
     } else {
         FGI_HIP(g, hipStreamSynchronize(st));
     }
@@ -4030,6 +4052,14 @@ fgi_status part_add_used(fgi_graph* g, uint32_t n, const uint32_t* dep, const ui
     FGI_TRY(d2h(g, r.data(), dres, n));
     if (out_result)
         for (uint32_t i = 0; i < n; ++i) out_result[i] = (r[i] & 0xFFu) - 1u;
+    if (view_on(g)) {   // the owned dependants (InvalidateOnSetOutput), as fgi_add_used
+        view_begin(g);
+        FGI_TRY(view_refresh(g, kViewCodes, ddep, n));
+        FGI_TRY(view_commit(g));
+    }
+    if (view_deferred(g))
+        for (uint32_t i = 0; i < n; ++i)
+            if (dep[i] - pv.base < pv.n_local) g->view->pending.push_back(part_code_local_h(g, dep[i] - pv.base, true));
     return FGI_OK;
 }
 
@@ -4072,6 +4102,13 @@ fgi_status part_set_output(fgi_graph* g, uint32_t n, const uint32_t* slot, uint8
     g->last_wave_n = 0;
     FGI_TRY(run_part_wave(g, (uint32_t)nr, droots, nullptr, stats));   // Invalidate() (Computed.cs:153-156)
     FGI_TRY(part_take_ids(g, pv, ids));
+    if (view_on(g) && m) {   // the owned items' new states (Consistent, or what the cascade left)
+        view_begin(g);
+        FGI_TRY(view_refresh(g, kViewLabels, dh, m));
+        FGI_TRY(view_commit(g));
+    }
+    if (view_deferred(g))
+        for (uint32_t j = 0; j < m; ++j) g->view->pending.push_back(part_code_local_h(g, lh[j], true));
     if (n) {
         std::vector<uint32_t> all(n, 0);
         for (uint32_t j = 0; j < m; ++j) all[li[j]] = set[j];
@@ -4205,6 +4242,32 @@ fgi_status fgi_part_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* st
         FGI_TRY(part_flagged_begin(g, n_casc, own_begin));
         g->pflg_batch = true;
     }
+    // The state view follows the batch once, behind it, from the post-batch words (as fgi_run_batch's): the
+    // steps list this rank's handles they changed instead of refreshing them, and the view is made exact on
+    // every way out, also when a step is refused after earlier ones were applied.
+    struct ViewScope {
+        fgi_graph* g;
+        bool on;
+        fgi_status sync() {
+            if (!on) return FGI_OK;
+            on = false;
+            View* v = g->view;
+            v->deferred = false;
+            std::vector<uint32_t> hs;
+            hs.swap(v->pending);
+            fgi_status st = view_refresh_host(g, hs.data(), hs.size());
+            if (st == FGI_OK && g->flag_gate && g->prec && g->pcur && !g->pflg_runs.empty())
+                st = view_refresh(g, kViewRecords, g->prec, g->prec_cap, g->pcur);
+            return st == FGI_OK ? view_commit(g) : st;
+        }
+        ~ViewScope() { (void)sync(); }
+    } vscope{g, view_on(g)};
+    if (vscope.on) {
+        hipSetDevice(g->device);
+        view_begin(g);
+        g->view->pending.clear();
+        g->view->deferred = true;
+    }
     std::vector<uint32_t> ids;
     fgi_wave_stats ws{};
     for (uint32_t k = 0; k < n_steps; ++k) {
@@ -4237,6 +4300,7 @@ fgi_status fgi_part_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* st
         if (stats && sp.kind != FGI_STEP_ADD_USED) stats->waves += 1;
         (void)before;
     }
+    FGI_TRY(vscope.sync());
     if (stats) {
         stats->levels += ws.levels;
         stats->v_inv += ws.v_inv;

@@ -1467,7 +1467,7 @@ fgi_status part_codes_choose(fgi_graph* g, uint32_t* weight_dev) {
     touch(g);
     note_words(g);
     if (getenv("FGI_TRACE")) fprintf(stderr, "[fgi] partition codes: rank %u of %u, %u slots\n", p->v.rank, p->v.world, N);
-    return FGI_OK;
+    return FGI_OK;   // the installed words moved: the callers rebuild the state view once their load is in
 }
 
 // the first bulk load of a partition that wants codes (nothing loaded, no detached handle taken)
@@ -2048,7 +2048,7 @@ fgi_status fgi_part_synth_rmat(fgi_graph* g, uint32_t scale, uint32_t edge_facto
         st = part_rebuild_lists(g);
     } while (0);
     cleanup();
-    return st;
+    return st == FGI_OK ? view_rebuild(g) : st;   // a new node table: the state view's full build
 }
 
 fgi_status fgi_part_register_nodes(fgi_graph* g, uint32_t n, const uint32_t* slot, const uint64_t* version,
@@ -2095,7 +2095,7 @@ fgi_status fgi_part_register_nodes(fgi_graph* g, uint32_t n, const uint32_t* slo
     hipFree(df);
     touch(g);          // versions changed: the pull lists are rebuilt before the next wave
     note_words(g);
-    return st;
+    return st == FGI_OK ? view_rebuild(g) : st;   // a bulk import: the state view's full build
 }
 
 fgi_status fgi_part_load_edges(fgi_graph* g, uint64_t m, const uint32_t* used, const uint32_t* dependant,
@@ -2137,6 +2137,7 @@ fgi_status fgi_part_load_edges(fgi_graph* g, uint64_t m, const uint32_t* used, c
     }
     if (choose) {
         FGI_TRY(part_codes_choose(g, p->weight));
+        FGI_TRY(view_rebuild(g));   // the installed words moved: the state view's full build through the new map
         used = part_codes_in(g, m, used, mu);
         dependant = part_codes_in(g, m, dependant, md);
     }

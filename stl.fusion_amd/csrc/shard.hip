@@ -308,7 +308,7 @@ fgi_status fgi_part_register_shard(fgi_graph* g, uint32_t n, const uint32_t* slo
     if (bad)
         return set_err(g, FGI_ESTATE, "fgi_part_register_shard: %llu listed slots already had a current node "
                                       "(or are listed twice)", (unsigned long long)bad);
-    return FGI_OK;
+    return view_rebuild(g);   // a bulk import: the state view's full build
 }
 
 fgi_status fgi_part_load_edges_shard(fgi_graph* g, uint64_t m, const uint32_t* used, const uint32_t* dependant,
@@ -431,6 +431,7 @@ fgi_status fgi_part_load_edges_shard(fgi_graph* g, uint64_t m, const uint32_t* u
         // the first bulk load of a partition that wants codes: every rank holds the same global weights
         if (part_codes_now(g)) {
             FGI_TRY(part_codes_choose(g, part_weight(g)));
+            FGI_TRY(view_rebuild(g));   // the installed words moved: the state view's full build through the new map
             FGI_TRY(map_codes(g, n_row, rk, base));
             FGI_TRY(map_codes(g, n_in, ik, base));
         }

@@ -8,6 +8,9 @@
 //                   64 handles per wavefront, a ballot per plane (open, bulk loads, fgi_restore)
 //   k_view_wave     a wave's invalidated bitmap out of `consistent` and `delay_started`: streaming bit
 //                   operations over 16-byte loads, no node word read
+//   k_view_part_wave  the same for a partition rank whose engine runs on codes (fgi_part_state_view_open;
+//                   C-ABI 0.7): a sparse wave scatters its set bits through code -> slot, a dense one
+//                   gathers each plane word through slot -> code with one ballot
 //   k_view_refresh  listed handles (a call's own lists, a wave's flagged records) from their node words
 //   k_view_flush    dirty device words -> host planes, fenced at system scope
 // A node's state is its word plus its visit bit, so nothing here calls fold: a visited
@@ -23,13 +26,20 @@ namespace {
 
 constexpr int kVBlock = 256;
 
-// where the engine keeps boundary handles: handle h lives at label s2l[h] if it is a hot slot, else K + h
+// where the engine keeps boundary handles: handle h lives at label s2l[h] if it is a hot slot, else K + h.
+// A partition rank (K = 0) with codes keeps owned slot base + h (h < n_local) at engine index
+// gc[base + h] - base, and engine index e < n_local is handle ig[base + e] - base; every other handle
+// (the unowned slot bits, the detached handles) is its own index.
 struct ViewMap {
     const uint32_t* s2l;   // null: no hot labels
     const uint32_t* l2s;
     uint32_t ext_slots, ext_handles, K, n_labels;
+    const uint32_t* gc;    // null: no partition codes
+    const uint32_t* ig;
+    uint32_t base, n_local;   // a partition rank's first slot and its owned slots (0, 0 on a single device)
 };
 __device__ __forceinline__ uint32_t view_label(const ViewMap& m, uint32_t h) {
+    if (m.gc) return h < m.n_local ? m.gc[m.base + h] - m.base : h;
     if (m.s2l && h < m.ext_slots) {
         const uint32_t l = m.s2l[h];
         if (l != FGI_NONE) return l;
@@ -38,6 +48,7 @@ __device__ __forceinline__ uint32_t view_label(const ViewMap& m, uint32_t h) {
 }
 __device__ __forceinline__ uint32_t view_handle(const ViewMap& m, uint32_t l) {
     if (l >= m.n_labels) return FGI_NONE;
+    if (m.ig) return l < m.n_local ? m.ig[m.base + l] - m.base : l;
     if (l < m.K) return m.l2s ? m.l2s[l] : FGI_NONE;
     return l - m.K;
 }
@@ -123,6 +134,73 @@ __global__ __launch_bounds__(kVBlock) void k_view_wave(ViewMap m, const unsigned
         wave_word(m, inv64[lwords - 1], lwords - 1, k64, dev, dirty, words);
 }
 
+// A partition rank's wave with codes. Codes are dealt round-robin over the pull blocks' runs, so the 64
+// bits of one word of inv64 (over engine indices) belong to 64 unrelated plane words. inv_n: the rank's
+// invalidated count, left by the final collect queued before this kernel; every thread reads the same
+// value, so the choice below is grid-uniform and the host waits for nothing to make it.
+// path: 0 by the count (gather from n_local / den invalidated handles on), 1 scatter, 2 gather.
+//   scatter: as k_view_wave's hot labels: stream the bitmap, each set bit to its handle's plane words
+//   gather:  a wavefront per plane word x: lane l probes the bit of handle 64 x + l's engine index; the
+//            ballot is the word of newly invalidated handles, applied by lane 0 with plain loads and
+//            stores (the wavefront owns plane word x; nothing else runs on the stream)
+__global__ __launch_bounds__(kVBlock) void k_view_part_wave(ViewMap m, const unsigned long long* __restrict__ inv64,
+                                                            uint64_t lwords, const unsigned long long* __restrict__ inv_n,
+                                                            int path, uint32_t den, unsigned long long* dev,
+                                                            unsigned long long* dirty, uint64_t words) {
+    // (the count covers the rank's owned slots only and just steers the choice: no early return on 0, so a
+    // bit at a detached handle's index would still be applied, as k_view_wave would apply it)
+    const unsigned long long n_inv = *inv_n;
+    const bool gather = path == 2 || (path == 0 && n_inv * den >= m.n_local);
+    const uint64_t nthr = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (!gather) {
+        const uint64_t pairs = lwords / 2;
+        const ulonglong2* inv2 = reinterpret_cast<const ulonglong2*>(inv64);
+        for (uint64_t i = tid; i <= pairs; i += nthr) {
+            unsigned long long w[2] = {0ull, 0ull};
+            if (i < pairs) {
+                const ulonglong2 v = inv2[i];
+                w[0] = v.x;
+                w[1] = v.y;
+            } else if (lwords & 1) {
+                w[0] = inv64[lwords - 1];
+            }
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+                for (unsigned long long b = w[k]; b; b &= b - 1) {
+                    const uint32_t h = view_handle(m, (uint32_t)((2 * i + k) * 64) + (uint32_t)(__ffsll((long long)b) - 1));
+                    if (h < m.ext_handles) wave_clear(dev, dirty, words, h >> 6, 1ull << (h & 63));
+                }
+        }
+        return;
+    }
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t nwaves = nthr >> 6;
+    for (uint64_t x = tid >> 6; x < words; x += nwaves) {   // wave-uniform trip count
+        const uint32_t h = (uint32_t)(x * 64 + lane);
+        bool hit = false;
+        if (h < m.ext_handles) {
+            const uint32_t e = view_label(m, h);
+            hit = ((uint64_t)e >> 6) < lwords && ((inv64[e >> 6] >> (e & 63)) & 1ull);
+        }
+        const unsigned long long w = __ballot(hit);
+        if (lane == 0 && w) {
+            unsigned long long* c = dev + kVpConsistent * words + x;
+            const unsigned long long cv = *c;
+            if (cv & w) {
+                *c = cv & ~w;
+                mark_dirty(dirty, kVpConsistent * words + x);
+            }
+            unsigned long long* d = dev + kVpDelayStarted * words + x;
+            const unsigned long long dv = *d;
+            if (dv & w) {
+                *d = dv & ~w;
+                mark_dirty(dirty, kVpDelayStarted * words + x);
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(kVBlock) void k_view_refresh(ViewMap m, int kind, const void* __restrict__ list, uint64_t n,
                                                           const unsigned long long* __restrict__ n_dev,
                                                           const unsigned long long* __restrict__ node,
@@ -132,8 +210,11 @@ __global__ __launch_bounds__(kVBlock) void k_view_refresh(ViewMap m, int kind, c
     const uint64_t nthr = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += nthr) {
         uint32_t h;
-        if (kind == kViewRecords) h = (uint32_t)(static_cast<const unsigned long long*>(list)[i] >> 32);
-        else if (kind == kViewLabels) h = view_handle(m, static_cast<const uint32_t*>(list)[i]);
+        if (kind == kViewRecords) h = (uint32_t)(static_cast<const unsigned long long*>(list)[i] >> 32) - m.base;
+        else if (kind == kViewCodes) {   // a partition's global engine ids: the owned ones
+            const uint32_t l = static_cast<const uint32_t*>(list)[i] - m.base;
+            h = l < m.n_local ? view_handle(m, l) : FGI_NONE;
+        } else if (kind == kViewLabels) h = view_handle(m, static_cast<const uint32_t*>(list)[i]);
         else h = static_cast<const uint32_t*>(list)[i];
         if (h >= m.ext_handles) continue;
         const uint32_t b = plane_bits(node, vis, view_label(m, h));
@@ -178,8 +259,10 @@ __global__ __launch_bounds__(kVBlock) void k_view_flush(unsigned long long* dirt
 inline uint32_t vgrid(uint64_t n) { return (uint32_t)std::min<uint64_t>(2048, std::max<uint64_t>(1, (n + kVBlock - 1) / kVBlock)); }
 
 ViewMap view_map(const fgi_graph* g) {
+    const View* v = g->view;
     return ViewMap{g->lbl_hot ? g->s2l : nullptr, g->lbl_hot ? g->l2s : nullptr, g->ext_slots, g->ext_handles, g->lbl_K,
-                   g->n_handles};
+                   g->n_handles, g->lbl_perm ? g->pg_gc : nullptr, g->lbl_perm ? g->pg_ig : nullptr, v->part_base,
+                   v->part_n_local};
 }
 // the visit bitmap while it holds this graph's unfolded visits (fgi_restore may have left it stale)
 const uint32_t* view_vis(const fgi_graph* g) { return g->v_dirty && !g->vis_stale ? g->vis_bm : nullptr; }
@@ -227,6 +310,19 @@ fgi_status view_wave(fgi_graph* g) {
     const uint64_t lwords = ((uint64_t)g->n_handles + 63) / 64;
     hipLaunchKernelGGL(k_view_wave, dim3(vgrid(lwords / 2 + 1)), dim3(kVBlock), 0, g->stream, view_map(g),
                        reinterpret_cast<const unsigned long long*>(g->inv_bm), lwords, v->dev, v->dirty, v->words);
+    FGI_HIP(g, hipGetLastError());
+    return FGI_OK;
+}
+
+fgi_status view_part_wave(fgi_graph* g) {
+    if (!view_on(g)) return FGI_OK;
+    if (!g->lbl_perm) return view_wave(g);   // engine indices are the handles: k_view_wave with K = 0
+    View* v = g->view;
+    const uint64_t lwords = ((uint64_t)g->n_handles + 63) / 64;
+    // a grid for the gather (a wavefront per plane word); the scatter strides over it
+    hipLaunchKernelGGL(k_view_part_wave, dim3(vgrid(v->words * 64)), dim3(kVBlock), 0, g->stream, view_map(g),
+                       reinterpret_cast<const unsigned long long*>(g->inv_bm), lwords, &g->ctr->inv, g->opt_part_view_path,
+                       kPartViewGatherDen, v->dev, v->dirty, v->words);
     FGI_HIP(g, hipGetLastError());
     return FGI_OK;
 }
@@ -286,10 +382,8 @@ using namespace fgi;
 
 extern "C" {
 
-fgi_status fgi_state_view_open(fgi_graph* g, fgi_state_view* out) {
-    if (!g || !out || out->struct_size < sizeof(fgi_state_view)) return FGI_EINVAL;
-    if (g->part) return set_err(g, FGI_ENOTSUP, "fgi_state_view_open: a partitioned graph has no state view");
-    if (g->failed) return set_err(g, FGI_ESTATE, "fgi_state_view_open: the graph is poisoned; fgi_restore or fgi_destroy");
+// what both opens share: the planes on first use, a full build on every open, the caller's struct
+static fgi_status view_open(fgi_graph* g, fgi_state_view* out, uint32_t part_base, uint32_t part_n_local) {
     hipSetDevice(g->device);
     if (g->aw[0].busy || g->aw[1].busy) FGI_TRY(drain_async(g));
     if (!g->view) {
@@ -309,6 +403,8 @@ fgi_status fgi_state_view_open(fgi_graph* g, fgi_state_view* out) {
         FGI_HIP(g, hipMemsetAsync(v->pub_dev, 0, 8, g->stream));
     }
     View* v = g->view;
+    v->part_base = part_base;
+    v->part_n_local = part_n_local;
     if (!v->open) {
         v->open = true;
         g->wave_clean = false;   // a wave with a view open keeps its invalidated bitmap: the next one clears it
@@ -324,6 +420,25 @@ fgi_status fgi_state_view_open(fgi_graph* g, fgi_state_view* out) {
     out->delay_started = h + kVpDelayStarted * v->words;
     out->has_delay = h + kVpHasDelay * v->words;
     out->seq = h + kViewPlanes * v->words;
+    return FGI_OK;
+}
+
+fgi_status fgi_state_view_open(fgi_graph* g, fgi_state_view* out) {
+    if (!g || !out || out->struct_size < sizeof(fgi_state_view)) return FGI_EINVAL;
+    // (a partition's ranks each hold their slots' share: fgi_part_state_view_open)
+    if (g->part) return set_err(g, FGI_ENOTSUP, "fgi_state_view_open: a partitioned graph has a view per rank (fgi_part_state_view_open)");
+    if (g->failed) return set_err(g, FGI_ESTATE, "fgi_state_view_open: the graph is poisoned; fgi_restore or fgi_destroy");
+    return view_open(g, out, 0, 0);
+}
+
+fgi_status fgi_part_state_view_open(fgi_graph* g, fgi_state_view* out, uint32_t* out_base) {
+    if (!g || !out || out->struct_size < sizeof(fgi_state_view)) return FGI_EINVAL;
+    PartView pv;
+    if (!g->part || !part_view(g, &pv))
+        return set_err(g, FGI_ENOTSUP, "fgi_part_state_view_open: not a partitioned graph (fgi_state_view_open)");
+    if (g->failed) return set_err(g, FGI_ESTATE, "fgi_part_state_view_open: the graph is poisoned; fgi_restore or fgi_destroy");
+    FGI_TRY(view_open(g, out, pv.base, pv.n_local));   // no collective: the rank's own handles
+    if (out_base) *out_base = pv.base;
     return FGI_OK;
 }
 

@@ -4419,6 +4419,22 @@ static fgi_status launch_part_flagged(fgi_graph* g, const PartView& pv) {
     return FGI_OK;
 }
 
+// A partitioned cascade's end on this rank: the flagged-set post-pass if the graph can flag, and the state
+// view's close. The nodes a cascade only flags reach the view from the post-pass's records (every record
+// of the call so far: a refresh reads the words, so a repeated one changes nothing), which are queued
+// behind the wave's wait: one more wait, on a rank whose flag gate is on only (fgi_view_stats.extra_waits).
+static fgi_status part_wave_flagged(fgi_graph* g, const PartView& pv) {
+    if (g->flag_gate) {
+        FGI_TRY(launch_part_flagged(g, pv));
+        if (view_on(g)) {
+            FGI_TRY(view_refresh(g, kViewRecords, g->prec, g->prec_cap, g->pcur));
+            FGI_TRY(view_commit(g));
+        }
+    }
+    view_end(g);
+    return FGI_OK;
+}
+
 fgi_status part_flagged_begin(fgi_graph* g, uint64_t cascades, uint64_t extra) {
     g->pflg_runs.clear();
     g->pflg_steps.clear();
@@ -4488,6 +4504,10 @@ static fgi_status run_part_planned(fgi_graph* g, const PartView& pv, const WaveP
         }
         // the final collect may be repeated if the wave goes on (it only reads the invalidated bitmap)
         FGI_HIP(g, launch_final(g, pv.n_local));
+        // the rank's state view (fgi_part_state_view_open): idempotent like the collect, and queued ahead of
+        // the round's one wait, so a rank that cannot flag waits for nothing more
+        FGI_TRY(view_part_wave(g));
+        FGI_TRY(view_flush(g));
 #if FGI_SPIN_WAIT
         // the counters ride to fine-grained host memory ahead of the all-reduce's published result
         FGI_TRY(publish_async(g, s, reinterpret_cast<const unsigned long long*>(g->ctr), kPubWords, g->ctr_pub));
@@ -4569,6 +4589,7 @@ fgi_status run_part_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_d
     const bool coll = pv.world > 1 || g->opt_part_coll;
     if (coll) FGI_HIP(g, hipMemsetAsync(pv.sent_bm, 0, pv.sent_words * 4, s));
     if (coll) FGI_TRY(part_front_reset(g));
+    view_begin(g);   // also without roots of its own: other ranks' targets invalidate this rank's nodes
     wave_start(g, true, true);
     FGI_HIP(g, ensure_events(g, 2));
     // the wave's span: stream events with per-level timing, else the device wall clock (spin waits:
@@ -4614,7 +4635,7 @@ fgi_status run_part_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_d
     if (sums[4] == pv.world) {   // every rank follows the plan: no host synchronisation until the wave's end
         FGI_TRY(run_part_planned(g, pv, wp, pb, n_roots, stats, t0));
         // behind the last round's final collect, after the wave's one wait: outside its span and its syncs
-        return g->flag_gate ? launch_part_flagged(g, pv) : FGI_OK;
+        return part_wave_flagged(g, pv);
     }
     g->part_plan.clear();      // learnt again by this wave's levels
     g->part_plan_key = key;
@@ -4686,13 +4707,15 @@ fgi_status run_part_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_d
     }
     FGI_HIP(g, launch_final(g, pv.n_local));
     FGI_HIP(g, hipGetLastError());
+    FGI_TRY(view_part_wave(g));   // the rank's state view rides on the final collect's wait
+    FGI_TRY(view_flush(g));
     FGI_TRY(counters_to_host(g, s, part_events(g)));
     ++t.syncs;   // the final collect's
     const WaveCtr& c = *g->ctr_host;
     g->last_wave_n = c.inv;
     g->ids_valid = true;
     if (stats) fill_wave_stats(stats, c, n_roots, t, wave_span_ms(g, c, part_events(g)), t0);
-    return g->flag_gate ? launch_part_flagged(g, pv) : FGI_OK;   // queued, not waited for
+    return part_wave_flagged(g, pv);   // queued, not waited for (unless a state view is open)
 }
 
 }  // namespace fgi

@@ -31,6 +31,7 @@ OPT_PART_BUCKET = 14
 OPT_FAULT_INJECT_TAIL = 16
 OPT_PROBE_SUMMARY = 15
 OPT_RUN_OFFSET_BITS = 17
+OPT_PART_VIEW_PATH = 18   # partitions with codes and a state view: 0 by the wave's size, 1 scatter, 2 gather
 DIR_AUTO, DIR_PUSH, DIR_PULL = 0, 1, 2
 NONE = 0xFFFFFFFF
 COMPUTING, CONSISTENT, INVALIDATED = 0, 1, 2
@@ -228,6 +229,8 @@ SIGNATURES = {
     # the exported copies of fgi.h's inline read helpers (they return an int / the state_flags word, not a status)
     "fgi_view_is_consistent": [C.POINTER(StateViewStruct), C.c_uint32],
     "fgi_view_flags": [C.POINTER(StateViewStruct), C.c_uint32],
+    "fgi_part_state_view_open": [_G, C.POINTER(StateViewStruct), _u32p],
+    "fgi_part_view_is_consistent": [C.POINTER(StateViewStruct), C.c_uint32, C.c_uint32, C.c_uint32],
 }
 
 _lib = None
@@ -638,6 +641,15 @@ class Graph:
         self._check(self.lib.fgi_state_view_open(self.h, C.byref(sv)), "open_state_view")
         return StateView(sv)
 
+    def part_open_state_view(self) -> Tuple[StateView, int]:
+        """Opens (or returns again) this rank's state view of a partition, over the rank's local boundary
+        handles, and the rank's first global slot. No collective runs."""
+        sv = StateViewStruct()
+        sv.struct_size = C.sizeof(StateViewStruct)
+        base = C.c_uint32(0)
+        self._check(self.lib.fgi_part_state_view_open(self.h, C.byref(sv), C.byref(base)), "part_open_state_view")
+        return StateView(sv), int(base.value)
+
     def close_state_view(self):
         self._check(self.lib.fgi_state_view_close(self.h), "close_state_view")
 
@@ -855,6 +867,14 @@ def part_init_local(graphs, n_global: int):
     st = lib.fgi_part_init_local(arr, len(graphs), n_global)
     if st != OK:
         raise FgiError(st, "fgi_part_init_local: " + (lib.fgi_last_error(graphs[0].h) or b"").decode())
+
+
+def part_view_is_consistent(views, block: int, slot: int) -> bool:
+    """fgi_part_view_is_consistent over the ranks' views (rank order): whether global slot `slot` is Consistent."""
+    arr = (StateViewStruct * len(views))()
+    for r, v in enumerate(views):
+        C.memmove(C.byref(arr[r]), C.byref(v.struct), C.sizeof(StateViewStruct))
+    return bool(load_library().fgi_part_view_is_consistent(arr, len(views), block, slot))
 
 
 def part_local_invalidate(graphs, roots, immediately=None):
