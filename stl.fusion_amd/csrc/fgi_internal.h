@@ -512,7 +512,6 @@ struct fgi_graph {
     uint32_t* ar_d[2] = {nullptr, nullptr};
     uint64_t ar_cap[2] = {0, 0};
     bool lists_wanted = false;         // a wave met a frontier heavy enough to pull (async waves build lists first)
-    bool want_ids = true;              // run_wave writes the invalidated list (false: bitmap and count only)
     bool ids_valid = false;            // inv holds the last wave's list (else ensure_ids rebuilds it)
     int last_levels = 4;               // non-empty levels of the last wave (sizes the first level group)
     int last_head = 4;                 // levels up to the last one the tail cannot run (pull, or large push)
@@ -533,6 +532,15 @@ struct fgi_graph {
     // the last level-group wave left its counters, statistics and invalidated bitmap zeroed (its final
     // kernels and publish did, WaveEnd): the next wave runs without k_wave_init
     bool wave_clean = false;
+    // A count-only synchronous wave (run_wave without an id destination) keeps its invalidated bitmap until
+    // the next wave starts (ensure_ids, the bits download and xbm read it) and leaves everything else
+    // zeroed: wave_kept. Only run_wave honours it, by swapping in the clean second bitmap inv_spare (same
+    // size as inv_bm, hot-heads tail included; allocated by a single-device graph's first count-only
+    // wave); that wave's end kernel clears the swapped-out one (inv_spare_dirty). Every other driver sees
+    // wave_clean == false and starts with k_wave_init.
+    bool wave_kept = false;
+    uint32_t* inv_spare = nullptr;
+    bool inv_spare_dirty = false;
     bool v_dirty = false;              // vis_bm may hold set bits
     bool vis_stale = false;            // fgi_restore left vis_bm's clearing to the next wave (flush_vis)
     bool coop_clean = false;           // wave counters, statistics and bitmaps clear (a cooperative wave left them so)
@@ -793,8 +801,12 @@ fgi_status ensure_cstart(fgi_graph* g, uint64_t total_edges);
 // Run one cascade wave from `n_roots` device-resident roots. Fills stats (nullable).
 // ext_roots: the roots are boundary handles (the entry points' own arrays), mapped to labels by the
 // roots kernel; internal callers pass labels.
+// out: what the caller hands back from this call. kIds: the wave writes the ascending id list itself.
+// kCount / kBits: the wave only counts (its bitmap stays in device memory) and the list is made on demand
+// (ensure_ids); the two differ only in the variant build's fused waves, which list unless kBits.
+enum class WaveOut { kIds, kCount, kBits };
 fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, const uint8_t* imm_dev,
-                    fgi_wave_stats* stats, bool ext_roots = false);
+                    fgi_wave_stats* stats, bool ext_roots = false, WaveOut out = WaveOut::kIds);
 // The last single-device wave's invalidated list in g->inv (rebuilt from the invalidated bitmap if
 // the wave ran in bitmap mode).
 fgi_status ensure_ids(fgi_graph* g);

@@ -2056,6 +2056,7 @@ fgi_status fgi_destroy(fgi_graph* g) {
     dfree(g->uin_more);
     dfree(g->sum_bm);
     dfree(g->inv_bm);
+    dfree(g->inv_spare);
     dfree(g->bsum);
     dfree(g->done);
     dfree(g->ctr);
@@ -2432,9 +2433,12 @@ fgi_status fgi_restore(fgi_graph* g) {
         FGI_HIP(g, hipMemsetAsync(g->vis_bm, 0, g->bm_words * 4, s));
         FGI_HIP(g, hipMemsetAsync(g->vis_spare, 0, g->bm_words * 4, s));
         FGI_HIP(g, hipMemsetAsync(g->inv_bm, 0, g->bm_words * 4, s));
+        if (g->inv_spare) FGI_HIP(g, hipMemsetAsync(g->inv_spare, 0, g->bm_words * 4, s));
         FGI_HIP(g, hipMemsetAsync(g->gbar, 0, kGbarWords * sizeof(unsigned long long), s));
         g->spare_dirty = false;
+        g->inv_spare_dirty = false;
         g->wave_clean = false;
+        g->wave_kept = false;
         g->words_dirty = false;
         g->cls_valid = false;
         g->flg_valid = false;
@@ -2619,7 +2623,8 @@ fgi_status fgi_invalidate(fgi_graph* g, uint32_t n_roots, const uint32_t* roots,
     FGI_TRY(stage_roots(g, n_roots));
     FGI_TRY(h2d(g, g->roots_buf, roots, n_roots));
     if (immediately) FGI_TRY(h2d(g, g->imm_buf, immediately, n_roots));
-    FGI_TRY(run_wave(g, n_roots, g->roots_buf, immediately ? g->imm_buf : nullptr, stats, true));
+    FGI_TRY(run_wave(g, n_roots, g->roots_buf, immediately ? g->imm_buf : nullptr, stats, true,
+                     out_ids ? WaveOut::kIds : WaveOut::kCount));
     return copy_ids(g, out_ids, cap, out_n);
 }
 
@@ -2628,7 +2633,8 @@ fgi_status fgi_invalidate_dev(fgi_graph* g, uint32_t n_roots, const uint32_t* ro
     if (!g || (n_roots && !roots_dev)) return FGI_EINVAL;
     FGI_TRY(single_only(g, "fgi_invalidate_dev"));
     hipSetDevice(g->device);
-    FGI_TRY(run_wave(g, n_roots, roots_dev, imm_dev, stats, true));
+    // without a destination the wave only counts: the list is made when it is asked for (ensure_ids)
+    FGI_TRY(run_wave(g, n_roots, roots_dev, imm_dev, stats, true, out_ids_dev ? WaveOut::kIds : WaveOut::kCount));
     if (out_n) *out_n = g->last_wave_n;
     if (out_ids_dev && g->last_wave_n) {
         FGI_TRY(ensure_ids(g));
@@ -2650,10 +2656,8 @@ fgi_status fgi_invalidate_bits(fgi_graph* g, uint32_t n_roots, const uint32_t* r
     FGI_TRY(stage_roots(g, n_roots));
     FGI_TRY(h2d(g, g->roots_buf, roots, n_roots));
     if (immediately) FGI_TRY(h2d(g, g->imm_buf, immediately, n_roots));
-    g->want_ids = false;   // the final collect only counts; the list is made on demand (ensure_ids)
-    const fgi_status st = run_wave(g, n_roots, g->roots_buf, immediately ? g->imm_buf : nullptr, stats, true);
-    g->want_ids = true;
-    FGI_TRY(st);
+    // the final collect only counts; the list is made on demand (ensure_ids)
+    FGI_TRY(run_wave(g, n_roots, g->roots_buf, immediately ? g->imm_buf : nullptr, stats, true, WaveOut::kBits));
     if (out_n) *out_n = g->last_wave_n;
     if (!out_bits) return FGI_OK;
     // the wave's invalidated bitmap over boundary handles (bit h of 32-bit word h / 32 = bit h of 64-bit
@@ -2851,7 +2855,7 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
                        cnt[1]);
     // displacement cascade first (ComputedRegistry.cs:91-94), then detach + install
     g->last_wave_n = 0;
-    if (cnt[0]) FGI_TRY(run_wave(g, (uint32_t)cnt[0], droots, nullptr, stats));
+    if (cnt[0]) FGI_TRY(run_wave(g, (uint32_t)cnt[0], droots, nullptr, stats, false, WaveOut::kCount));
     view_begin(g);   // the cascade's share of the state view is in; the install's follows below
     // the call's slots hold new nodes when it returns: a displaced node the cascade flagged is not in the
     // call's flagged set under its slot (it lives on as out_detached[i])
@@ -2978,7 +2982,8 @@ fgi_status fgi_set_output(fgi_graph* g, uint32_t n, const uint32_t* handle, uint
     FGI_TRY(d2h(g, &nr, g->misc_dev, 1));
     if (out_set) FGI_TRY(d2h(g, out_set, dset, n));
     g->last_wave_n = 0;
-    if (nr) FGI_TRY(run_wave(g, (uint32_t)nr, droots, nullptr, stats));   // Invalidate() (Computed.cs:153-156)
+    if (nr)   // Invalidate() (Computed.cs:153-156)
+        FGI_TRY(run_wave(g, (uint32_t)nr, droots, nullptr, stats, false, out_ids ? WaveOut::kIds : WaveOut::kCount));
     if (view_on(g)) {   // the handles' new states (Consistent, or what the cascade left) from their words and visit bits
         view_begin(g);
         FGI_TRY(view_refresh(g, kViewLabels, dh, n));

@@ -407,7 +407,7 @@ static fgi_status view_open(fgi_graph* g, fgi_state_view* out, uint32_t part_bas
     v->part_n_local = part_n_local;
     if (!v->open) {
         v->open = true;
-        g->wave_clean = false;   // a wave with a view open keeps its invalidated bitmap: the next one clears it
+        g->wave_clean = g->wave_kept = false;   // a wave with a view open keeps its invalidated bitmap: the next one clears it
         FGI_TRY(view_rebuild(g));
     }
     out->n_handles = g->ext_handles;

@@ -692,7 +692,30 @@ struct WaveEnd {
     uint32_t* inv_bm;        // the labels' invalidated bitmap: ext words of it cleared (64-bit words)
     uint64_t words;          // 64-bit words of inv_bm the wave can have set (n_handles / 64, rounded up)
     uint32_t* spare;         // the other visit bitmap, cleared whether the wave is over or not (nullable)
+    uint32_t* inv_spare;     // the invalidated bitmap the previous count-only wave kept, swapped out at this
+                             // wave's start: cleared like spare (nullable)
 };
+// The last block of a synchronous wave's end kernel may publish the wave's counters itself: to fine-grained
+// host memory, then (after a system-scope fence) the sequence word the host spins on, k_publish's protocol
+// with one launch fewer.
+struct ListPub {
+    unsigned long long* dst;   // null: no publish
+    unsigned long long seq;
+    unsigned long long* done;
+    uint32_t words;
+};
+// every block's share of the swapped-out bitmaps (64-bit words [0, end.words) split over the grid)
+__device__ __forceinline__ void clear_spares(const WaveEnd& end) {
+    if (!end.spare && !end.inv_spare) return;
+    const uint64_t P = (end.words + gridDim.x - 1) / gridDim.x;
+    const uint64_t z0 = min(end.words, (uint64_t)blockIdx.x * P), z1 = min(end.words, z0 + P);
+    unsigned long long* sw = reinterpret_cast<unsigned long long*>(end.spare);
+    unsigned long long* iw = reinterpret_cast<unsigned long long*>(end.inv_spare);
+    for (uint64_t x = z0 + threadIdx.x; x < z1; x += blockDim.x) {
+        if (sw) sw[x] = 0ull;
+        if (iw) iw[x] = 0ull;
+    }
+}
 __device__ __forceinline__ bool wave_over(const WaveEnd& e) {
     const uint64_t stop = e.tail ? max((uint64_t)e.L, (uint64_t)e.ctr->cur) : (uint64_t)e.L;
     return lvl_F(e.ctr->lvl[stop % kRing]) == 0;
@@ -1669,8 +1692,10 @@ __global__ void k_part_tail(const WaveCtr* ctr, int L0, int L, uint32_t W, const
 // k_final_write — block t adds up its predecessors' counts (all of them in one round) and writes
 // every set bit's handle at that offset, in ascending order: one 1,024-handle tile per wave, 16
 // handles per lane, staged in LDS and stored coalesced.
-// total = 1 (bitmap mode, no k_final_write follows): the last block also sums the counts into
-// ctr->inv (V_inv).
+// total = 1 (count-only, no k_final_write follows): the last block also sums the counts into
+// ctr->inv (V_inv), and the kernel is the wave's end: with end.ctr it leaves the wave state clean but for
+// the invalidated bitmap, which a count-only wave keeps (fgi_graph::wave_kept), and with pub its last
+// block publishes the counters to the host.
 // Hub-first labels (labels.hip): the bitmap over boundary handles of fold tile t
 // (handles [t * kFoldTile, + kFoldTile), kFoldWords 64-bit words) is the labels' bitmap shifted by K
 // (K + x is the label of every handle x that has no hot label; K is a multiple of kFoldTile), ORed with
@@ -1829,29 +1854,60 @@ __device__ unsigned long long fold_tile(const FoldArgs& f, const unsigned long l
     return c;
 }
 
+// The count kernel's last block, every other block having arrived: the counters to the host (ListPub; V_inv
+// is the block's own sum `all`, the statistics totals were exchanged at agent scope), then, once the wave is
+// over, zeroed — nothing in the launch reads them any more. Out of line: one block in the grid runs it.
+__device__ __noinline__ void publish_count(ListPub pub, WaveCtr* ctr, unsigned long long all, bool over) {
+    if (threadIdx.x == 0) pub.dst[pub.words + 1] = wall_clock64();
+    unsigned long long* src = reinterpret_cast<unsigned long long*>(ctr);
+    constexpr uint32_t kInvWord = offsetof(WaveCtr, inv) / 8;
+    for (uint32_t i = threadIdx.x; i < pub.words; i += blockDim.x) pub.dst[i] = i == kInvWord ? all : coh_read(src + i);
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(pub.dst + pub.words, pub.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (over)
+        for (uint32_t i = threadIdx.x; i < (uint32_t)(sizeof(WaveCtr) / 8); i += blockDim.x) src[i] = 0ull;
+}
+
 constexpr uint32_t kFoldBlocks = 4096;   // k_final_count's grid with hot labels: one fold tile per block up to 2^28 handles
 
 // The final count: tickets 0..kStats-1 fold the per-block statistics into the wave counters; every
 // block counts the set bits of its 64-bit words [t * wpb, (t + 1) * wpb) into status[t]. With hot labels
 // (f.xbm), block t is fold tile t instead: it writes the tile's bitmap over boundary handles into xbm
 // and counts that.
+// With total and end.ctr (a count-only level group's end, run_wave): every block clears its share of the
+// swapped-out bitmaps (end.spare, end.inv_spare) whether the wave is over or not, and once the wave is
+// over (wave_over) each statistics block zeroes the column it has just summed, so the next wave needs no
+// init kernel; the invalidated bitmap itself stays. With pub the last block then publishes the counters
+// (the statistics totals reach it as agent-scope exchanges, V_inv is its own sum) and, once the wave is
+// over, zeroes them after the release. Idempotent while the wave goes on, as the list kernel.
 __global__ __launch_bounds__(kBlock) void k_final_count(const unsigned long long* __restrict__ inv64, uint64_t words,
                                                         uint64_t wpb, unsigned long long* status, WaveCtr* ctr,
-                                                        const unsigned long long* __restrict__ blk, int total,
-                                                        unsigned long long* done, FoldArgs f) {
+                                                        unsigned long long* blk, int total,
+                                                        unsigned long long* done, FoldArgs f, ListPub pub, WaveEnd end) {
     __shared__ unsigned long long s_red[kBlock / 64];
     const uint32_t t = blockIdx.x;
+    const bool over = total && end.ctr && wave_over(end);   // block-uniform; read before any block's arrival
     if (t < (uint32_t)kStats) {
         const int k = t;
         unsigned long long* dst[kStats] = {&ctr->e_match,   &ctr->n_flagged, &ctr->pull_surv, &ctr->pull_edges,
                                            &ctr->pull_live, &ctr->pull_win,  &ctr->pull_tail, &ctr->pull_scan};
-        const unsigned long long* col = blk + (uint64_t)k * kStatBlocks;
+        unsigned long long* col = blk + (uint64_t)k * kStatBlocks;
         unsigned long long x = 0;
 #pragma unroll
         for (uint32_t q = 0; q < kStatBlocks / kBlock; ++q) x += col[q * kBlock + threadIdx.x];
         x = block_sum(x, s_red);
-        if (threadIdx.x == 0) *dst[k] = x + (k == kStFlagged ? ctr->root_flagged : 0ull);
+        if (over) {   // the column's one reader: no other block touches it in this launch
+#pragma unroll 4
+            for (uint32_t q = 0; q < kStatBlocks / kBlock; ++q) col[q * kBlock + threadIdx.x] = 0ull;
+        }
+        if (threadIdx.x == 0) {
+            const unsigned long long v = x + (k == kStFlagged ? ctr->root_flagged : 0ull);
+            if (total && pub.dst) coh_xchg(dst[k], v);   // read by the publishing block in this launch
+            else *dst[k] = v;
+        }
     }
+    if (total && end.ctr) clear_spares(end);
     unsigned long long c = 0;
     if (f.xbm) {
         // fold tiles t, t + G, ...: one status word per tile (k_final_write's spb groups); one tile per
@@ -1881,27 +1937,21 @@ __global__ __launch_bounds__(kBlock) void k_final_count(const unsigned long long
     unsigned long long all = 0;
     for (uint32_t k = threadIdx.x; k < gridDim.x; k += blockDim.x) all += coh_read(status + k);
     all = block_sum(all, s_red);
-    if (threadIdx.x == 0) ctr->inv = all;
+    if (threadIdx.x == 0 && !(pub.dst && over)) ctr->inv = all;   // (the publishing block zeroes it below)
+    if (pub.dst) publish_count(pub, ctr, all, over);
 }
 
 // The list: block t writes the set bits of its words [t * wpb, + wpb) of inv64 (the boundary's bitmap:
 // the labels' own, or xbm) in ascending order, after the sum of the counts of the status entries
 // before its own (spb entries per block: 1, or its fold tiles).
 // With pub (a synchronous wave's list, run_wave): the last block to finish also publishes the wave's
-// counters to fine-grained host memory and then the sequence word (k_publish's protocol, one launch
-// fewer). The asynchronous waves keep k_publish: their ids are read by other streams after the wait, so
-// the word must follow the whole kernel.
-struct ListPub {
-    unsigned long long* dst;   // null: no publish
-    unsigned long long seq;
-    unsigned long long* done;
-    uint32_t words;
-};
+// counters (ListPub). The asynchronous waves keep k_publish: their ids are read by other streams after the
+// wait, so the word must follow the whole kernel.
 
 // With end.ctr (a level group's list, run_wave): once the wave is over (wave_over), every block also
 // zeroes its share of the invalidated bitmap (its own words, after reading them, when it lists that
-// bitmap; hot labels: k_final_count has read it) and of the statistics rows, and with end.spare its share
-// of the swapped-out visit bitmap, so that the next wave needs no init kernel.
+// bitmap; hot labels: k_final_count has read it) and of the statistics rows, and with end.spare /
+// end.inv_spare its share of the swapped-out bitmaps, so that the next wave needs no init kernel.
 __global__ __launch_bounds__(kBlock) void k_final_write(const unsigned long long* __restrict__ inv64, uint64_t words,
                                                         uint64_t wpb, const unsigned long long* __restrict__ status,
                                                         WaveCtr* ctr, uint32_t* out, int need_done, uint32_t spb,
@@ -1952,11 +2002,9 @@ __global__ __launch_bounds__(kBlock) void k_final_write(const unsigned long long
         const uint64_t P = (end.words + gridDim.x - 1) / gridDim.x;
         const uint64_t z0 = min(end.words, (uint64_t)t * P), z1 = min(end.words, z0 + P);
         unsigned long long* iw = reinterpret_cast<unsigned long long*>(end.inv_bm);
-        unsigned long long* sw = reinterpret_cast<unsigned long long*>(end.spare);
-        for (uint64_t x = z0 + threadIdx.x; x < z1; x += blockDim.x) {
-            if (over) iw[x] = 0ull;
-            if (sw) sw[x] = 0ull;
-        }
+        if (over)
+            for (uint64_t x = z0 + threadIdx.x; x < z1; x += blockDim.x) iw[x] = 0ull;
+        clear_spares(end);
         if (over) {
             constexpr uint64_t kBlk = (uint64_t)kStatBlocks * kStatCols;
             const uint64_t Q = (kBlk + gridDim.x - 1) / gridDim.x;
@@ -3041,8 +3089,10 @@ ExpandArgs expand_args(fgi_graph* g, int buf) {
 // the invalidated bitmap -> V_inv (ctr->inv) and, with ids, the invalidated list
 hipError_t launch_final(fgi_graph* g, uint32_t n_handles, bool ids = true, uint32_t* out = nullptr, ListPub pub = ListPub{},
                         WaveEnd end = WaveEnd{}) {
-    if (!ids) pub.dst = nullptr;   // no list kernel: the caller publishes
-    if (!end.ctr) g->wave_clean = false;   // the counters (inv, ...) are written and nothing clears them
+    // count only (!ids): the count kernel is the wave's end (pub, end); else the list kernel is
+    const ListPub cpub = ids ? ListPub{} : pub;
+    const WaveEnd cend = ids ? WaveEnd{} : end;
+    if (!end.ctr) g->wave_clean = g->wave_kept = false;   // the counters (inv, ...) are written and nothing clears them
     if (!out) out = g->inv;
     const auto* inv64 = reinterpret_cast<const unsigned long long*>(g->inv_bm);
     const FoldArgs f = fold_args(g);
@@ -3052,7 +3102,7 @@ hipError_t launch_final(fgi_graph* g, uint32_t n_handles, bool ids = true, uint3
         unsigned long long* st = g->fold_status;
         const uint32_t Gc = std::max<uint32_t>(std::min<uint32_t>(tiles, kFoldBlocks), kStats);
         hipLaunchKernelGGL(k_final_count, dim3(Gc), dim3(kBlock), 0, g->stream, inv64, words,
-                           (uint64_t)kFoldWords, st, g->ctr, (const unsigned long long*)g->blk_stats, ids ? 0 : 1, g->done, f);
+                           (uint64_t)kFoldWords, st, g->ctr, g->blk_stats, ids ? 0 : 1, g->done, f, cpub, cend);
         if (ids) {
             const uint32_t G = std::min<uint32_t>(kFinalBlocks, tiles), spb = (tiles + G - 1) / G;
             const uint32_t G2 = (tiles + spb - 1) / spb;
@@ -3067,7 +3117,7 @@ hipError_t launch_final(fgi_graph* g, uint32_t n_handles, bool ids = true, uint3
     // per-block counts apart from the pull prefixes a collect may still read
     unsigned long long* st = g->bsum + 6ull * kStatBlocks;
     hipLaunchKernelGGL(k_final_count, dim3(G), dim3(kBlock), 0, g->stream, inv64, words, wpb, st, g->ctr,
-                       (const unsigned long long*)g->blk_stats, ids ? 0 : 1, g->done, FoldArgs{});
+                       g->blk_stats, ids ? 0 : 1, g->done, FoldArgs{}, cpub, cend);
     if (ids)
         hipLaunchKernelGGL(k_final_write, dim3(G), dim3(kBlock), 0, g->stream, inv64, words, wpb,
                            (const unsigned long long*)st, g->ctr, out, 0, 1u, pub, end);
@@ -3131,7 +3181,7 @@ void launch_roots(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, con
 // clean start; a cooperative wave left it so; the fused head clears it itself). clear_vis = false: the
 // cooperative wave, which folds its own visits and never clears the bitmap.
 void wave_start(fgi_graph* g, bool launch, bool clear_vis) {
-    g->wave_clean = false;   // every path dirties the wave state; the ones that leave it clean say so at their end
+    g->wave_clean = g->wave_kept = false;   // every path dirties the wave state; the ones that leave it clean say so at their end
     if (launch)
         hipLaunchKernelGGL(k_wave_init, dim3(kInitBlocks), dim3(kBlock), 0, g->stream, g->ctr, g->blk_stats, g->inv_bm,
                            clear_vis && g->vis_stale ? g->vis_bm : nullptr, (uint64_t)g->bm_words);
@@ -3459,7 +3509,7 @@ uint32_t fused_grid(const fgi_graph* g) {
 // FGI_ENOTSUP (nothing launched) if the fused grid cannot be resident on this device.
 static fgi_status run_wave_fused(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, const uint8_t* imm_dev,
                                  fgi_wave_stats* stats, WaveParams wp, bool timing,
-                                 std::chrono::steady_clock::time_point t0) {
+                                 std::chrono::steady_clock::time_point t0, bool want_ids) {
     hipStream_t s = g->stream;
     const uint32_t G = fused_grid(g);
     if (g->fused_per_cu == 0) {
@@ -3544,7 +3594,7 @@ static fgi_status run_wave_fused(fgi_graph* g, uint32_t n_roots, const uint32_t*
         hipLaunchKernelGGL(k_wave_fused<true>, dim3(G), dim3(kBlock), 0, s, a);
         if (timing) FGI_HIP(g, hipEventRecord(ev[eh + 3], s));
         ++t.fused_launches;
-        if (g->want_ids) {
+        if (want_ids) {
             const auto* inv64 = reinterpret_cast<const unsigned long long*>(g->inv_bm);
             hipLaunchKernelGGL(k_final_write, dim3(a.fin_G), dim3(kBlock), 0, s, inv64, words, a.fin_wpb,
                                (const unsigned long long*)a.status, g->ctr, g->inv, 1, 1u, ListPub{}, WaveEnd{});
@@ -3589,7 +3639,7 @@ static fgi_status run_wave_fused(fgi_graph* g, uint32_t n_roots, const uint32_t*
     g->last_mid = (int)c.n_mid;
     if (imm_dev && n_roots) note_words(g);   // immediate roots changed node words
     g->last_wave_n = c.inv;
-    g->ids_valid = g->want_ids;
+    g->ids_valid = want_ids;
     g->stale_est += c.e_trav + c.e_match;
     if (n_roots) g->last_levels = (int)std::max<uint64_t>(c.n_levels, 1);
     static const bool trace = getenv("FGI_TRACE") != nullptr;
@@ -3887,8 +3937,9 @@ fgi_status read_flagged(fgi_graph* g, int k, bool blocking_copy, std::vector<uin
 }
 
 fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, const uint8_t* imm_dev,
-                    fgi_wave_stats* stats, bool ext_roots) {
+                    fgi_wave_stats* stats, bool ext_roots, WaveOut out) {
     const auto t0 = std::chrono::steady_clock::now();
+    const bool ids = out == WaveOut::kIds;   // the list kernel runs inside the wave (else on demand: ensure_ids)
     g->flg_last = -1;
     g->flg_drop.clear();
     forget_async_results(g, g->inv);   // the list goes to g->inv (now, or on demand: ensure_ids)
@@ -3913,18 +3964,46 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
     if ((g->opt_fused & kFusedOn) && !g->lbl_K && !g->flag_gate && !view_on(g) && (allow_pull || wp0.direction == 1)) {   // labels, flagged sets: level groups
         WaveParams wp = wp0;
         if (!allow_pull) wp.direction = 1;
-        const fgi_status r = run_wave_fused(g, n_roots, roots_dev, imm_dev, stats, wp, timing, t0);
+        const fgi_status r = run_wave_fused(g, n_roots, roots_dev, imm_dev, stats, wp, timing, t0, out != WaveOut::kBits);
         if (r != FGI_ENOTSUP) return r;
     }
 #endif
-    // the previous wave left the counters, statistics and invalidated bitmap zeroed (WaveEnd) and the visit
-    // bitmap is clean (fgi_restore swapped in the spare): no init kernel, the roots kernel stamps t0
-    const bool clean_start = g->wave_clean && !g->vis_stale && n_roots != 0;
     // a state view (view.hip) follows the wave: its update rides on every level group, queued between the
     // final collect and the publish the host waits for, so the view is exact when the wait returns
     const bool view = view_on(g) && n_roots != 0;
+    // The wave's end kernels — the list kernel and the publish, or the count kernel alone when the wave
+    // only counts — leave the state clean once the wave is over (WaveEnd).
+    // The list kernel may publish the counters itself (one launch fewer), but its last block's
+    // system-scope release then writes back the whole list first: 11.6 -> 33.7 us for configs[1]'s
+    // k_final_write, 0.231 -> 0.262 ms/step (profiles/r12c); measurement only (FGI_LIST_PUBLISH=1).
+    // The count kernel writes no list, so its last block publishes by default (FGI_COUNT_PUBLISH=0: the
+    // separate k_publish, for measurement; profiles/count_only_ab.txt).
+    static const bool list_pub = getenv("FGI_LIST_PUBLISH") && getenv("FGI_LIST_PUBLISH")[0] == '1';
+    static const bool count_pub = !(getenv("FGI_COUNT_PUBLISH") && getenv("FGI_COUNT_PUBLISH")[0] == '0');
+    const bool merged = FGI_SPIN_WAIT && (ids ? list_pub : count_pub) && !view;
+    // (a graph that can flag keeps the invalidated bitmap for the flagged-set post-pass: launch_flagged;
+    // one with a state view open keeps it for the view's update)
+    const bool leave_clean = !(ids && merged) && FGI_SPIN_WAIT && !g->flag_gate && !view_on(g);
+    // the previous wave left the counters, statistics and invalidated bitmap zeroed (WaveEnd) and the visit
+    // bitmap is clean (fgi_restore swapped in the spare): no init kernel, the roots kernel stamps t0.
+    // The same after a count-only wave, which kept its bitmap (wave_kept): the clean second bitmap takes its
+    // place and this wave's end kernel clears the kept one, so only a wave that has such an end swaps.
+    const bool kept_start = g->wave_kept && leave_clean && g->inv_spare && !g->inv_spare_dirty;
+    const bool clean_start = (g->wave_clean || kept_start) && !g->vis_stale && n_roots != 0;
+    // a count-only wave that leaves the state clean needs the second bitmap for the wave after it
+    // (single-device graphs only come here: partitions and their ranks never pay for it)
+    if (!ids && leave_clean && !g->inv_spare) {
+        FGI_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->inv_spare), (size_t)(g->bm_words + kHot / 32) * 4));
+        FGI_HIP(g, hipMemsetAsync(g->inv_spare, 0, g->bm_words * 4, g->stream));
+        g->inv_spare_dirty = false;
+    }
+    const bool swapped = clean_start && !g->wave_clean;
     if (view) view_begin(g);
     wave_start(g, !clean_start, true);
+    if (swapped) {   // every kernel argument below is built from g->inv_bm at launch time
+        std::swap(g->inv_bm, g->inv_spare);
+        g->inv_spare_dirty = true;
+    }
 #if FGI_PROBE
     {
         void* pp = nullptr;
@@ -3938,13 +4017,6 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
         g->v_dirty = true;
         launch_roots(g, n_roots, roots_dev, imm_dev, 0u, g->n_handles, 0, ext_roots, clean_start ? 1 : 0);
     }
-    // the list kernel and the publish of a group leave the state clean once the wave is over (WaveEnd):
-    // only when the list kernel runs (ids wanted, not the measurement-only merged publish)
-    static const bool list_pub = getenv("FGI_LIST_PUBLISH") && getenv("FGI_LIST_PUBLISH")[0] == '1';
-    const bool merged = FGI_SPIN_WAIT && g->want_ids && list_pub && !view;
-    // (a graph that can flag keeps the invalidated bitmap for the flagged-set post-pass: launch_flagged;
-    // one with a state view open keeps it for the view's update)
-    const bool leave_clean = g->want_ids && !merged && FGI_SPIN_WAIT && !g->flag_gate && !view_on(g);
     // Levels run in groups between host synchronisations (one ~30 us round trip each); the first
     // group is sized by the previous wave's depth, so a repeated workload syncs once per wave and an
     // overshoot costs only empty levels (two ~2 us launches each). Every group ends with the final
@@ -3976,18 +4048,15 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
         L += group;
         // the wave's small push levels after the group: one persistent launch
         if (use_tail) FGI_TRY(launch_tail(g, tail_args(g, L0, L, wp, tail_edges), L, timing));
-        // the list kernel may publish the counters itself (one launch fewer), but its last block's
-        // system-scope release then writes back the whole list first: 11.6 -> 33.7 us for configs[1]'s
-        // k_final_write, 0.231 -> 0.262 ms/step (profiles/r12c); measurement only (FGI_LIST_PUBLISH=1)
         ListPub lp{};
         if (merged) lp = ListPub{g->ctr_pub, ++g->pub_seq, g->done, (uint32_t)kPubWords};
         WaveEnd we{};
         if (leave_clean) {
             we = WaveEnd{g->ctr, L, use_tail ? 1 : 0, g->blk_stats, g->inv_bm, ((uint64_t)g->n_handles + 63) / 64,
-                         g->spare_dirty ? g->vis_spare : nullptr};
-            g->spare_dirty = false;   // the list kernel clears it whether the wave goes on or not
+                         g->spare_dirty ? g->vis_spare : nullptr, g->inv_spare_dirty ? g->inv_spare : nullptr};
+            g->spare_dirty = g->inv_spare_dirty = false;   // the end kernel clears them whether the wave goes on or not
         }
-        FGI_HIP(g, launch_final(g, g->n_handles, g->want_ids, nullptr, lp, we));   // idempotent: repeated if the wave goes on
+        FGI_HIP(g, launch_final(g, g->n_handles, ids, nullptr, lp, we));   // idempotent: repeated if the wave goes on
         final_done = true;
         FGI_HIP(g, hipGetLastError());
         if (view) {   // idempotent, as the final collect: repeated if the wave goes on
@@ -3996,6 +4065,8 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
         }
         // the wave's end marker rides on the group's synchronisation (re-recorded if the wave goes on):
         // recording it after the wait would cost the call a further device round trip
+        // (a list kernel that left the state clean is followed by the publish that zeroes the counters; the
+        // count kernel's last block does both)
         if (merged) FGI_TRY(counters_published(g, s, events, lp.seq));
         else FGI_TRY(counters_to_host(g, s, events, we));
         ++t.syncs;
@@ -4057,7 +4128,7 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
         }
     }
     if (!final_done) {   // no roots
-        FGI_HIP(g, launch_final(g, g->n_handles, g->want_ids));
+        FGI_HIP(g, launch_final(g, g->n_handles, ids));
         FGI_HIP(g, hipGetLastError());
         FGI_TRY(counters_to_host(g, s, events));
     }
@@ -4082,8 +4153,10 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
     if (view) view_end(g);
     if (imm_dev && n_roots) note_words(g);   // immediate roots changed node words
     // the last group's list kernel and publish saw the wave over (the host's loop ends on the same test)
-    g->wave_clean = leave_clean && final_done;
-    wave_finished(g, c, g->want_ids, g->inv, n_roots != 0, t, head, dirs_ok ? &dirs : nullptr);
+    // (a count-only wave kept its invalidated bitmap: wave_kept, which only run_wave honours)
+    g->wave_clean = leave_clean && final_done && ids;
+    g->wave_kept = leave_clean && final_done && !ids;
+    wave_finished(g, c, ids, g->inv, n_roots != 0, t, head, dirs_ok ? &dirs : nullptr);
     if (trace)
         fprintf(stderr,
                 "[fgi] wave: %llu invalidated; pull: live %llu, survivors %llu, queued %llu, dependencies "
