@@ -564,6 +564,11 @@ fgi_status fgi_stream(fgi_graph* g, void** stream);
  *                            how a wave's invalidated set reaches the planes: 0 by the wave's size (gather
  *                            from n_local / 16 invalidated handles on), 1 scatter, 2 gather. Results never
  *                            depend on it (tests pin both paths on small graphs).
+ *   FGI_OPT_PART_IDS_PATH  [0] partitions with codes: how fgi_part_last_wave_ids / _bits bring a wave's
+ *                            invalidated set into the host's numbering: 0 by the wave's size, 1 scatter
+ *                            from the wave's list, 2 gather per bitmap word. Results never
+ *                            depend on it (tests pin both paths); setting it makes the last wave's result
+ *                            again on the next call.
  *   FGI_OPT_RUN_OFFSET_BITS [28] tests only: a pull candidate's record names its tail run by an offset
  *                            below 2^bits words from its pull block's base; a candidate past that is
  *                            found through the per-slot list offsets instead (tests pin that path on
@@ -584,6 +589,7 @@ fgi_status fgi_stream(fgi_graph* g, void** stream);
 #define FGI_OPT_FAULT_INJECT_TAIL 16
 #define FGI_OPT_RUN_OFFSET_BITS 17
 #define FGI_OPT_PART_VIEW_PATH 18
+#define FGI_OPT_PART_IDS_PATH 19
 /* 12 and 15: the measurement variants' options (include/fgi_variants.h); FGI_ENOTSUP here */
 fgi_status fgi_set_option(fgi_graph* g, int option, int64_t value);
 
@@ -661,7 +667,43 @@ fgi_status fgi_part_local_load_shards(fgi_graph* const* gs, uint32_t p, const ui
  * invalidated slots it owns (global ids) and its own share of the statistics. */
 fgi_status fgi_part_invalidate(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev,
                                const uint8_t* immediately_dev, uint64_t* out_n, fgi_wave_stats* stats);
+/* (fgi_part_export_ids serves every call kind; after a wave, fgi_part_last_wave_ids / _bits below return
+ * the same set without the host-side mapping and sort) */
 fgi_status fgi_part_export_ids(fgi_graph* g, uint32_t* out_ids, uint64_t cap, uint64_t* out_n);
+/* The same collective wave from HOST roots (C-ABI 0.8): the scope-dispose flush of
+ * `using (Computed.Invalidate())` on a multi-GPU host — for each root, `existing.Invalidate(immediately[i])`
+ * (Computed.cs:162-230, as fgi_invalidate). Every rank passes the same root list (global slots); the roots
+ * are staged through a pinned buffer the graph owns, copied on its stream and, with partition codes, mapped
+ * on the device. A root >= n_global: FGI_EINVAL on every rank alike, before anything is launched or any
+ * collective joined.
+ * fgi_part_invalidate_host returns this rank's invalidated slots: the global slot ids it owns, in the
+ * host's numbering, strictly ascending; *out_n = the rank's V_inv. A short cap: FGI_ECAPACITY with *out_n
+ * set, the wave has completed (fgi_part_last_wave_ids then returns the ids). out_ids NULL: count only.
+ * fgi_part_invalidate_bits returns them as a bitmap addressed exactly like the planes of
+ * fgi_part_state_view_open: bit h % 64 of out_bits[h / 64] = global slot rank * block + h, h < cfg.n_slots;
+ * the bits past the rank's last owned slot and the detached handles' bits are 0, so a host applies it word
+ * for word against its view-indexed tables. `words` >= (n_slots + n_detached + 63) / 64, else FGI_ECAPACITY
+ * (nothing runs). out_bits NULL: count only.
+ * Both are made on the device from the wave's invalidated bitmap (no host loop, no sort), on demand. */
+fgi_status fgi_part_invalidate_host(fgi_graph* g, uint32_t n_roots, const uint32_t* roots,
+                                    const uint8_t* immediately /*nullable*/, uint32_t* out_ids /*nullable*/, uint64_t cap,
+                                    uint64_t* out_n, fgi_wave_stats* stats /*nullable*/);
+fgi_status fgi_part_invalidate_bits(fgi_graph* g, uint32_t n_roots, const uint32_t* roots,
+                                    const uint8_t* immediately /*nullable*/, uint64_t* out_bits /*nullable*/, uint64_t words,
+                                    uint64_t* out_n, fgi_wave_stats* stats /*nullable*/);
+/* This rank's share of its last wave (the set Computed.Invalidate(), Computed.cs:162-230, moved from
+ * Consistent to Invalidated; a partition's fgi_last_wave_ids / fgi_wave_ids_dev), made on demand, once per
+ * wave: ids and bitmap as described above, ids_dev the same ascending list in device memory. No collective
+ * runs: any rank may ask at any time, in any order. Valid after fgi_part_invalidate, fgi_part_invalidate_host,
+ * fgi_part_invalidate_bits, fgi_part_invalidate_all and each rank of fgi_part_local_invalidate, until the
+ * rank's next call that runs a cascade (ids_dev too). After any other call that ran cascades
+ * (fgi_part_begin_compute, fgi_part_set_output, fgi_part_run_batch, which return ids through their own
+ * out_ids): FGI_ENOTSUP. After fgi_restore, and before any wave: FGI_OK with 0 ids / a zero bitmap.
+ * FGI_ENOTSUP on a graph that is not partitioned, FGI_ESTATE on a poisoned one, and FGI_ESTATE naming the
+ * rank and both counts if the ids made from the bitmap are not as many as the wave counted. */
+fgi_status fgi_part_last_wave_ids(fgi_graph* g, uint32_t* out_ids /*nullable*/, uint64_t cap, uint64_t* out_n);
+fgi_status fgi_part_last_wave_bits(fgi_graph* g, uint64_t* out_bits /*nullable*/, uint64_t words, uint64_t* out_n);
+fgi_status fgi_part_wave_ids_dev(fgi_graph* g, const uint32_t** ids_dev, uint64_t* n /*nullable*/);
 /* In-process partition group: `p` graphs (created with rank = i, world = p) emulate p ranks in
  * one process — on one device or several. fgi_part_local_invalidate runs the RCCL path's own level
  * loop on every rank (one host thread per rank); only the collectives differ (device copies

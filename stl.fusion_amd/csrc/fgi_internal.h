@@ -405,6 +405,29 @@ struct View {
 // handles on and scatters below (FGI_OPT_PART_VIEW_PATH pins either)
 constexpr uint32_t kPartViewGatherDen = 16;
 
+// A partition rank's last wave in the host's numbering (part_out.hip): the bitmap over the
+// rank's boundary handles (bit h = global slot base + h, as the state view's planes) and the ascending
+// global ids made from it, both on the device, each made at most once per wave; and the staging of
+// fgi_part_invalidate_host's roots. Everything is allocated at first use and grown by need.
+struct PartOut {
+    unsigned long long* bits = nullptr;   // [bits_cap] device
+    uint64_t bits_cap = 0;
+    uint32_t* ids = nullptr;              // [ids_cap] device
+    uint64_t ids_cap = 0;
+    unsigned long long* bsum = nullptr;   // [bsum_cap] per-block popcounts, scanned in place; then the total
+    uint64_t bsum_cap = 0;
+    bool bits_valid = false, ids_valid = false;   // of the rank's last wave (part_out_mark clears them)
+    char* stage_h = nullptr;              // pinned: roots_cap roots, then roots_cap `immediately` bytes
+    uint32_t* roots_d = nullptr;
+    uint8_t* imm_d = nullptr;
+    uint64_t roots_cap = 0;
+};
+enum { kPoutNone = 0, kPoutWave = 1, kPoutOther = 2 };
+// With codes, a wave's host-order bitmap is gathered from n_local / kPartIdsGatherDen invalidated slots on
+// and scattered from the wave's list below (FGI_OPT_PART_IDS_PATH pins either). Measured at 524,288 slots per
+// rank (profiles/part_ids_ab.txt): the two tie at n_local / 256 and the gather wins above.
+constexpr uint32_t kPartIdsGatherDen = 256;
+
 }  // namespace fgi
 
 struct fgi_graph {
@@ -735,6 +758,14 @@ struct fgi_graph {
     uint32_t pflg_step = 0;
     fgi::View* view = nullptr;         // the host-memory state view (null until fgi_state_view_open)
     int opt_part_view_path = 0;        // FGI_OPT_PART_VIEW_PATH: 0 by the wave's count, 1 scatter, 2 gather
+    // A partition rank's last wave in the host's numbering (part_out.hip; fgi_part_last_wave_ids / _bits,
+    // fgi_part_wave_ids_dev). pout_kind: what the rank's last call that ran cascades was
+    // (kPoutNone: none since create or fgi_restore; kPoutWave: one wave, whose result the accessors make on
+    // demand; kPoutOther: a mutation or a batch, which report ids through their own out_ids). pout: the
+    // buffers, null until an accessor or fgi_part_invalidate_host first needs them.
+    fgi::PartOut* pout = nullptr;
+    int pout_kind = 0;
+    int opt_part_ids_path = 0;         // FGI_OPT_PART_IDS_PATH: 0 by the wave's count, 1 scatter, 2 gather
 };
 
 // ---- internal entry points shared between translation units ----------------------------------
@@ -978,6 +1009,24 @@ fgi_status run_part_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_d
 // and clears the cursor. run_part_wave opens a call of one cascade itself; fgi_part_run_batch opens its
 // own (pflg_batch) with its begin_compute entries as `extra`.
 fgi_status part_flagged_begin(fgi_graph* g, uint64_t cascades, uint64_t extra);
+// ---- a partitioned wave's result in the host's numbering (part_out.hip) ----
+// What this rank's call that runs a cascade is (kPout*), said before the cascade starts (kPoutOther) and
+// again once one wave's result stands (kPoutWave); the previous wave's bitmap and ids are forgotten.
+// Touches host fields only.
+inline void part_out_mark(fgi_graph* g, int kind) {
+    g->pout_kind = kind;
+    if (g->pout) g->pout->bits_valid = g->pout->ids_valid = false;
+}
+// n host roots (global slots) and their `immediately` bytes (nullable) through the graph's pinned buffer
+// into its device copies, on the graph's stream; nothing waits
+fgi_status part_out_stage_roots(fgi_graph* g, uint32_t n, const uint32_t* roots, const uint8_t* imm, uint32_t** roots_dev,
+                                uint8_t** imm_dev);
+// the last wave's bitmap over the rank's boundary handles / its ascending global ids, on the device
+// (queued on the graph's stream; part_out_ids waits for its count check, and for the copy of the list to
+// host_copy if that is given)
+fgi_status part_out_bits(fgi_graph* g, const unsigned long long** bits_dev, uint64_t* words);
+fgi_status part_out_ids(fgi_graph* g, const uint32_t** ids_dev, uint32_t* host_copy);
+void part_out_destroy(fgi_graph* g);
 // ---- sharded loads (shard.hip) ----
 // The collectives they add to a partition's transport (part.hip, PartComm): host words (at most kShardWords
 // per rank) all-gathered on the host; device byte ranges with per-peer counts, all-gathered (src[0,

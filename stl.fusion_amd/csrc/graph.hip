@@ -1914,7 +1914,9 @@ fgi_status fgi_version(uint32_t* major, uint32_t* minor) {
     // 0.5: fgi_part_register_shard, fgi_part_load_edges_shard and their in-process drivers
     // 0.6: the host-memory state view (fgi_state_view_open / _close / _stats, fgi_view_flags, fgi_view_is_consistent)
     // 0.7: the same view per rank of a partition (fgi_part_state_view_open, fgi_part_view_is_consistent)
-    if (minor) *minor = 7;
+    // 0.8: a partitioned wave from host roots, its ids or bitmap in the host's numbering made on the device
+    //      (fgi_part_invalidate_host, fgi_part_invalidate_bits, fgi_part_last_wave_ids / _bits, fgi_part_wave_ids_dev)
+    if (minor) *minor = 8;
     return FGI_OK;
 }
 
@@ -2001,6 +2003,7 @@ fgi_status fgi_destroy(fgi_graph* g) {
     if (!g) return FGI_OK;
     hipSetDevice(g->device);
     if (g->stream) hipStreamSynchronize(g->stream);
+    fgi::part_out_destroy(g);
     fgi::part_destroy(g);
     fgi::view_destroy(g);
     fgi::tmp_drain(g);
@@ -2463,6 +2466,7 @@ fgi_status fgi_restore(fgi_graph* g) {
     g->pflg_steps.clear();
     g->pflg_set.clear();
     g->pflg_read = false;
+    part_out_mark(g, kPoutNone);   // and its last wave's ids and bitmap (fgi_part_last_wave_ids: 0 ids)
     // the visit bits are forgotten: the clean spare bitmap takes the visit bitmap's place, and the next
     // wave's list kernel clears the old one; without a clean spare, the next wave's init kernel clears it
     // (or flush_vis before any other use)
@@ -2560,6 +2564,12 @@ fgi_status fgi_set_option(fgi_graph* g, int option, int64_t value) {
         g->opt_part_view_path = (int)value;
         return FGI_OK;
     case FGI_OPT_PART_BUCKET: return part_set_bucket(g, value);
+    case FGI_OPT_PART_IDS_PATH:
+        if (value < 0 || value > 2) return set_err(g, FGI_EINVAL, "partition ids path must be 0, 1 or 2");
+        g->opt_part_ids_path = (int)value;
+        // what the last wave's accessors made already is made again on the next call, by the path now set
+        if (g->pout) g->pout->bits_valid = g->pout->ids_valid = false;
+        return FGI_OK;
     case FGI_OPT_PROBE_SUMMARY:
         if (value < -1 || value > (int64_t)FGI_NONE) return set_err(g, FGI_EINVAL, "probe summary: -1 or a word count");
         if (!FGI_VARIANTS && value != -1)
@@ -3842,6 +3852,7 @@ fgi_status part_wave_host(fgi_graph* g, const PartView& pv, uint32_t n, const ui
         }
     }
     g->last_wave_n = 0;
+    part_out_mark(g, kPoutOther);   // a batch's step: its ids leave through the batch's out_ids
     FGI_TRY(run_part_wave(g, n, dr, di, stats));
     return part_take_ids(g, pv, ids);
 }
@@ -3919,6 +3930,7 @@ fgi_status part_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, co
     if (cnt[0]) hipLaunchKernelGGL(k_add_base, dim3(nblk(cnt[0])), dim3(256), 0, st, (uint32_t)cnt[0], droots, pv.base);
     g->last_wave_n = 0;
     g->flag_gate = true;   // Computing nodes from here on (flagged sets), on every rank alike
+    part_out_mark(g, kPoutOther);
     FGI_TRY(run_part_wave(g, (uint32_t)cnt[0], droots, nullptr, stats));
     // the call's slots hold new nodes when it returns: a node the displacement cascade flagged under one of
     // them is not in the cascade's set (fgi_begin_compute's rule); kept as the host numbers the slots
@@ -4105,6 +4117,7 @@ fgi_status part_set_output(fgi_graph* g, uint32_t n, const uint32_t* slot, uint8
     FGI_TRY(d2h(g, &nr, g->misc_dev, 1));
     if (nr) hipLaunchKernelGGL(k_add_base, dim3(nblk(nr)), dim3(256), 0, st, (uint32_t)nr, droots, pv.base);
     g->last_wave_n = 0;
+    part_out_mark(g, kPoutOther);
     FGI_TRY(run_part_wave(g, (uint32_t)nr, droots, nullptr, stats));   // Invalidate() (Computed.cs:153-156)
     FGI_TRY(part_take_ids(g, pv, ids));
     if (view_on(g) && m) {   // the owned items' new states (Consistent, or what the cascade left)
@@ -4145,7 +4158,9 @@ fgi_status part_invalidate_all(fgi_graph* g, fgi_wave_stats* stats, std::vector<
     FGI_TRY(d2h(g, &nr, g->misc_dev, 1));
     if (nr) hipLaunchKernelGGL(k_add_base, dim3(nblk(nr)), dim3(256), 0, st, (uint32_t)nr, roots, pv.base);
     g->last_wave_n = 0;
+    part_out_mark(g, kPoutOther);   // until the wave stands
     FGI_TRY(run_part_wave(g, (uint32_t)nr, roots, nullptr, stats));
+    part_out_mark(g, kPoutWave);    // one wave: fgi_part_last_wave_ids / _bits serve it too
     return part_take_ids(g, pv, ids);
 }
 

@@ -1810,7 +1810,9 @@ fgi_status fgi_part_local_invalidate(fgi_graph* const* gs, uint32_t P, uint32_t 
                     (immediately && hipMemcpy(id, immediately, n_roots, hipMemcpyHostToDevice) != hipSuccess))
                     s = set_err(g, FGI_EDEVICE, "root copy");
             }
+            part_out_mark(g, kPoutOther);   // until the rank's wave stands
             if (s == FGI_OK) s = run_part_wave(g, n_roots, rd, id, stats ? stats + r : nullptr);
+            if (s == FGI_OK) part_out_mark(g, kPoutWave);
             if (s != FGI_OK) c0->grp->fail();
             hipFree(rd);
             hipFree(id);
@@ -2175,9 +2177,55 @@ fgi_status fgi_part_invalidate(fgi_graph* g, uint32_t n_roots, const uint32_t* r
                            (uint64_t)n_roots, p->roots_codes, (const uint32_t*)g->pg_gc, p->v.n_global);
         roots_dev = p->roots_codes;
     }
+    part_out_mark(g, kPoutOther);   // until the wave stands
     FGI_TRY(run_part_wave(g, n_roots, roots_dev, imm_dev, stats));
+    part_out_mark(g, kPoutWave);
     if (out_n) *out_n = g->last_wave_n;
     return FGI_OK;
+}
+
+// What fgi_part_invalidate_host and fgi_part_invalidate_bits share: the roots checked on the host (every
+// rank holds the same list, so every rank refuses alike, before any launch or collective), staged through
+// the graph's pinned buffer, mapped to codes on the device, and the wave.
+static fgi_status part_wave_from_host(fgi_graph* g, const char* what, uint32_t n_roots, const uint32_t* roots,
+                                      const uint8_t* immediately, fgi_wave_stats* stats) {
+    if (!g->part) return set_err(g, FGI_ENOTSUP, "%s: not a partitioned graph (fgi_invalidate)", what);
+    if (g->failed) return set_err(g, FGI_ESTATE, "%s: the graph is poisoned; fgi_restore or fgi_destroy", what);
+    PartState* p = ps(g);
+    for (uint32_t i = 0; i < n_roots; ++i)
+        if (roots[i] >= p->v.n_global)
+            return set_err(g, FGI_EINVAL, "%s: root %u is slot %u of %u", what, i, roots[i], p->v.n_global);
+    hipSetDevice(g->device);
+    uint32_t* rd = nullptr;
+    uint8_t* id = nullptr;
+    FGI_TRY(part_out_stage_roots(g, n_roots, roots, immediately, &rd, &id));
+    if (g->lbl_perm && n_roots) {
+        hipLaunchKernelGGL(k_pc_global, dim3(std::min<uint32_t>(nblk(n_roots), 4096)), dim3(256), 0, g->stream,
+                           (uint64_t)n_roots, rd, (const uint32_t*)g->pg_gc, p->v.n_global);
+        FGI_HIP(g, hipGetLastError());
+    }
+    part_out_mark(g, kPoutOther);   // until the wave stands
+    FGI_TRY(run_part_wave(g, n_roots, rd, id, stats));
+    part_out_mark(g, kPoutWave);
+    return FGI_OK;
+}
+
+fgi_status fgi_part_invalidate_host(fgi_graph* g, uint32_t n_roots, const uint32_t* roots, const uint8_t* immediately,
+                                    uint32_t* out_ids, uint64_t cap, uint64_t* out_n, fgi_wave_stats* stats) {
+    if (!g || (n_roots && !roots)) return FGI_EINVAL;
+    FGI_TRY(part_wave_from_host(g, "fgi_part_invalidate_host", n_roots, roots, immediately, stats));
+    return fgi_part_last_wave_ids(g, out_ids, cap, out_n);   // a short cap: FGI_ECAPACITY, the wave has completed
+}
+
+fgi_status fgi_part_invalidate_bits(fgi_graph* g, uint32_t n_roots, const uint32_t* roots, const uint8_t* immediately,
+                                    uint64_t* out_bits, uint64_t words, uint64_t* out_n, fgi_wave_stats* stats) {
+    if (!g || (n_roots && !roots)) return FGI_EINVAL;
+    // a bitmap too short is refused before the wave, as fgi_invalidate_bits refuses it
+    if (g->part && out_bits && words < ((uint64_t)g->ext_handles + 63) / 64)
+        return set_err(g, FGI_ECAPACITY, "bitmap of %llu words needs %llu", (unsigned long long)words,
+                       (unsigned long long)(((uint64_t)g->ext_handles + 63) / 64));
+    FGI_TRY(part_wave_from_host(g, "fgi_part_invalidate_bits", n_roots, roots, immediately, stats));
+    return fgi_part_last_wave_bits(g, out_bits, words, out_n);
 }
 
 fgi_status fgi_part_front_stats(fgi_graph* g, uint64_t* full, uint64_t* delta, uint64_t* bytes) {
@@ -2185,6 +2233,7 @@ fgi_status fgi_part_front_stats(fgi_graph* g, uint64_t* full, uint64_t* delta, u
     return part_front_stats(g, full, delta, bytes);
 }
 
+// (a wave's ids without the host loop and sort: fgi_part_last_wave_ids / fgi_part_last_wave_bits, part_out.hip)
 fgi_status fgi_part_export_ids(fgi_graph* g, uint32_t* out_ids, uint64_t cap, uint64_t* out_n) {
     if (!g || !g->part) return FGI_EINVAL;
     const uint64_t n = g->last_wave_n;

@@ -3729,6 +3729,11 @@ static fgi_status wait_word(fgi_graph* g, hipStream_t s, const unsigned long lon
 
 fgi_status publish_wait(fgi_graph* g, hipStream_t s, const unsigned long long* src, uint32_t words, unsigned long long* dst) {
     const unsigned long long seq = ++g->pub_seq;
+    // Callers share dst across publishes of different lengths (a partition's all-reduces: 1 to kPartRedMax
+    // words), so dst[words] may still hold a DATA word of an earlier, longer publish, and a small count there
+    // (a level's F or T) can equal this sequence number: the wait would end before the kernel has run. The
+    // earlier publish on dst has been waited for, so the host clears the word first (seq is never 0).
+    __atomic_store_n(dst + words, 0ull, __ATOMIC_RELEASE);
     hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, s, src, words, dst, seq, WaveEnd{});
     FGI_HIP(g, hipGetLastError());
     FGI_TRY(wait_word(g, s, dst + words, seq));

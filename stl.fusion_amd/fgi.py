@@ -32,6 +32,7 @@ OPT_FAULT_INJECT_TAIL = 16
 OPT_PROBE_SUMMARY = 15
 OPT_RUN_OFFSET_BITS = 17
 OPT_PART_VIEW_PATH = 18   # partitions with codes and a state view: 0 by the wave's size, 1 scatter, 2 gather
+OPT_PART_IDS_PATH = 19    # partitions with codes, a wave's ids / bitmap in the host's numbering: the same choice
 DIR_AUTO, DIR_PUSH, DIR_PULL = 0, 1, 2
 NONE = 0xFFFFFFFF
 COMPUTING, CONSISTENT, INVALIDATED = 0, 1, 2
@@ -231,6 +232,11 @@ SIGNATURES = {
     "fgi_view_flags": [C.POINTER(StateViewStruct), C.c_uint32],
     "fgi_part_state_view_open": [_G, C.POINTER(StateViewStruct), _u32p],
     "fgi_part_view_is_consistent": [C.POINTER(StateViewStruct), C.c_uint32, C.c_uint32, C.c_uint32],
+    "fgi_part_invalidate_host": [_G, C.c_uint32, _u32p, _u8p, _u32p, C.c_uint64, _u64p, C.POINTER(WaveStats)],
+    "fgi_part_invalidate_bits": [_G, C.c_uint32, _u32p, _u8p, _u64p, C.c_uint64, _u64p, C.POINTER(WaveStats)],
+    "fgi_part_last_wave_ids": [_G, _u32p, C.c_uint64, _u64p],
+    "fgi_part_last_wave_bits": [_G, _u64p, C.c_uint64, _u64p],
+    "fgi_part_wave_ids_dev": [_G, C.POINTER(C.c_void_p), _u64p],
 }
 
 _lib = None
@@ -806,6 +812,62 @@ class Graph:
         out = np.zeros(n.value, np.uint32)
         self._check(self.lib.fgi_part_export_ids(self.h, _ptr(out, C.c_uint32), n.value, C.byref(n)), "part_export_ids")
         return out
+
+    def part_invalidate_host(self, roots, immediately=None, stats: Optional[WaveStats] = None, want="ids"):
+        """fgi_part_invalidate_host / fgi_part_invalidate_bits (collective): the wave from host roots (global
+        slots, the same list on every rank). want="ids": this rank's invalidated global slots, ascending;
+        want="bits": (bitmap over the rank's boundary handles, addressed like its state view, V_inv);
+        want=None: the rank's V_inv alone (the wave only counts; part_last_wave_ids / _bits serve later)."""
+        r = _u32(roots)
+        imm = None if immediately is None else _u8(immediately)
+        st = C.byref(stats) if stats is not None else None
+        n = C.c_uint64()
+        if want == "bits":
+            words = (self.n_handles + 63) // 64
+            bits = np.zeros(words, np.uint64)
+            self._check(self.lib.fgi_part_invalidate_bits(self.h, len(r), _ptr(r, C.c_uint32), _ptr(imm, C.c_uint8),
+                                                          _ptr(bits, C.c_uint64), words, C.byref(n), st),
+                        "part_invalidate_bits")
+            return bits, n.value
+        if want is None:
+            self._check(self.lib.fgi_part_invalidate_host(self.h, len(r), _ptr(r, C.c_uint32), _ptr(imm, C.c_uint8),
+                                                          None, 0, C.byref(n), st), "part_invalidate_host")
+            return n.value
+        if want != "ids":
+            raise ValueError(want)
+        ids = np.zeros(self.n_slots, np.uint32)   # a rank invalidates at most the slots it owns
+        self._check(self.lib.fgi_part_invalidate_host(self.h, len(r), _ptr(r, C.c_uint32), _ptr(imm, C.c_uint8),
+                                                      _ptr(ids, C.c_uint32), len(ids), C.byref(n), st),
+                    "part_invalidate_host")
+        return ids[:n.value].copy()
+
+    def part_last_wave_ids(self) -> np.ndarray:
+        """fgi_part_last_wave_ids: this rank's invalidated global slots of its last wave, ascending, made on
+        the device in the host's numbering. No collective."""
+        n = C.c_uint64()
+        self._check(self.lib.fgi_part_last_wave_ids(self.h, None, 0, C.byref(n)), "part_last_wave_ids")
+        ids = np.zeros(n.value, np.uint32)
+        self._check(self.lib.fgi_part_last_wave_ids(self.h, _ptr(ids, C.c_uint32), len(ids), C.byref(n)),
+                    "part_last_wave_ids")
+        return ids
+
+    def part_last_wave_bits(self) -> Tuple[np.ndarray, int]:
+        """fgi_part_last_wave_bits: (the same set as a bitmap over the rank's boundary handles, bit h = global
+        slot base + h, addressed like part_open_state_view's planes; V_inv)."""
+        words = (self.n_handles + 63) // 64
+        bits = np.zeros(words, np.uint64)
+        n = C.c_uint64()
+        self._check(self.lib.fgi_part_last_wave_bits(self.h, _ptr(bits, C.c_uint64), words, C.byref(n)),
+                    "part_last_wave_bits")
+        return bits, n.value
+
+    def part_wave_ids_dev(self) -> Tuple[int, int]:
+        """fgi_part_wave_ids_dev: (device pointer to the same ascending list, its length); valid until the
+        rank's next call that runs a cascade."""
+        p = C.c_void_p()
+        n = C.c_uint64()
+        self._check(self.lib.fgi_part_wave_ids_dev(self.h, C.byref(p), C.byref(n)), "part_wave_ids_dev")
+        return p.value or 0, n.value
 
 
 def bits_to_ids(bits: np.ndarray) -> np.ndarray:
