@@ -396,6 +396,71 @@ fgi_status fgi_wave_wait_flagged(fgi_graph* g, uint64_t ticket, uint32_t* out_id
 fgi_status fgi_invalidate_all(fgi_graph* g, uint32_t* out_ids, uint64_t cap, uint64_t* out_n,
                               fgi_wave_stats* stats);
 
+/* ---- replica fan-out (C-ABI 0.9) ----------------------------------------------- */
+/* The RPC server's side of a replica: RpcInboundComputeCall awaits WhenInvalidated on the computed it served
+ * and then sends one `$sys-c.Invalidate(callId)` to its peer (Client/Internal/RpcInboundComputeCall.cs:53-62,
+ * 102-106; ComputedExt.WhenInvalidated, ComputedExt.cs:99-125). The engine keeps those subscriptions in device
+ * memory and joins them with a wave's invalidated set there: {invalidated handles} x {handle -> (peer, call
+ * id)}, returned as call ids grouped by peer, ready to send. No per-node data crosses to the host.
+ * Entries and lifetime
+ *   - An entry is (boundary handle, peer < FGI_MAX_PEERS, 64-bit call id); detached handles are included.
+ *   - No set semantics: the same triple stored twice is delivered twice.
+ *   - One-shot: the fan-out that delivers an entry removes it (WhenInvalidated completes once).
+ * fgi_subscribe stores n entries. out_result[i] (nullable) is FGI_SUB_ADDED, or FGI_SUB_INVALIDATED when the
+ * node is already Invalidated or the handle is empty: WhenInvalidated completes at once (ComputedExt.cs:99-125),
+ * nothing is stored and the host sends the message now. The state is the node's as it stands after the last
+ * wave, read from its node word and visit bit: no fold, no pass over the graph, and the last wave's id list,
+ * bitmap and flagged set stay as they are. A handle >= n_slots + n_detached or a peer >= FGI_MAX_PEERS returns
+ * FGI_EINVAL and stores nothing.
+ * fgi_last_wave_fanout returns the entries of every handle in the last wave's invalidated set. It is valid
+ * exactly where fgi_last_wave_ids is (after fgi_invalidate, _dev, _bits, fgi_invalidate_all, fgi_begin_compute,
+ * fgi_set_output) until the next call that runs a cascade or a fan-out, or fgi_restore. The lists are made on
+ * demand, once per wave: a second call returns the same arrays again, and so does a retry after FGI_ECAPACITY
+ * (*out_n holds the count). The entries leave the table when the lists are made, not when they are copied.
+ * n_peers must exceed every stored peer id (and be at most FGI_MAX_PEERS), else FGI_EINVAL and nothing is
+ * removed. After fgi_restore, or before any wave: FGI_OK with 0 entries. After fgi_run_batch or an asynchronous
+ * ticket: FGI_ENOTSUP (use fgi_fanout_ids). On a partitioned graph every call of this section returns
+ * FGI_ENOTSUP; on a poisoned graph FGI_ESTATE.
+ * A host that subscribes takes the fan-out of every wave before it begins a new computation on an invalidated
+ * slot: an entry left on a slot whose node a wave invalidated would otherwise fire with the next node there.
+ * fgi_fanout_ids is the same join for any strictly ascending handle list the host already holds (a batch's
+ * out_ids cascade by cascade, fgi_wave_wait_ids): one upload, and a handle without entries costs one bit test.
+ * A list that is not strictly ascending or names a handle out of range returns FGI_EINVAL. If cap is short it
+ * returns FGI_ECAPACITY with *out_n set and removes nothing.
+ * Output: peer_off[p] .. peer_off[p + 1] is peer p's range of call_ids / handles, peer_off[n_peers] == *out_n,
+ * a peer without entries has an empty range. Within a peer the order is ascending handle (the order the C++
+ * mirror delivers in); entries of the same handle and peer come in unspecified order. handles[i] is the handle
+ * whose invalidation released call_ids[i] (the host drops its RpcInboundComputeCall by it).
+ * Entries follow the node, not the slot: when fgi_begin_compute displaces a node that survives
+ * (out_detached[i] != FGI_NONE) its entries move to the detached handle; fgi_run_batch applies the same moves
+ * for its BEGIN_COMPUTE steps behind the batch, in step order (nobody can subscribe mid-batch, so only the
+ * first such step on a slot can have entries to move). fgi_release of a handle that still has entries drops
+ * them, fgi_unsubscribe_peer drops a disconnected peer's; both count in fgi_sub_stats.dropped.
+ * fgi_snapshot / fgi_restore leave the table alone.
+ * A graph that never subscribes allocates and launches nothing for any of this. */
+#define FGI_MAX_PEERS 4096u
+#define FGI_SUB_ADDED 0u
+#define FGI_SUB_INVALIDATED 1u
+fgi_status fgi_subscribe(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint32_t* peer,
+                         const uint64_t* call_id, uint32_t* out_result /*nullable*/);
+fgi_status fgi_last_wave_fanout(fgi_graph* g, uint32_t n_peers, uint64_t* peer_off /*n_peers+1*/,
+                                uint64_t* call_ids /*nullable*/, uint32_t* handles /*nullable*/,
+                                uint64_t cap, uint64_t* out_n);
+fgi_status fgi_fanout_ids(fgi_graph* g, uint64_t n, const uint32_t* ids /*host, strictly ascending*/,
+                          uint32_t n_peers, uint64_t* peer_off, uint64_t* call_ids, uint32_t* handles,
+                          uint64_t cap, uint64_t* out_n);
+fgi_status fgi_unsubscribe_peer(fgi_graph* g, uint32_t peer, uint64_t* out_dropped /*nullable*/);
+/* live: entries stored now; pool: record capacity of the table; delivered / dropped: entries that left through
+ * a fan-out / through fgi_release and fgi_unsubscribe_peer (delivered + dropped + live = entries ever stored);
+ * fanouts: fan-outs that launched kernels, of which from_list read an id list and from_bits the invalidated
+ * bitmap; last_kernel_ms: device time of the last one's kernels (HIP events). All zero on a graph that never
+ * subscribed. */
+typedef struct fgi_sub_stats {
+    uint64_t live, pool, delivered, dropped, fanouts, from_list, from_bits;
+    double last_kernel_ms;
+} fgi_sub_stats;
+fgi_status fgi_sub_stats_get(fgi_graph* g, fgi_sub_stats* out);
+
 /* ---- streaming batches (BASELINE.json configs[4]) ------------------------------- */
 /* One step of a batch: the arguments of the matching single call. */
 #define FGI_STEP_INVALIDATE 1     /* fgi_invalidate: handles, flags = immediately (nullable) */
@@ -569,6 +634,10 @@ fgi_status fgi_stream(fgi_graph* g, void** stream);
  *                            from the wave's list, 2 gather per bitmap word. Results never
  *                            depend on it (tests pin both paths); setting it makes the last wave's result
  *                            again on the next call.
+ *   FGI_OPT_FANOUT_PATH [0]  which form of the invalidated set a fan-out joins with the subscriptions: 0 by what
+ *                            the wave left (its kept bitmap, else its id list), 1 the id list, 2 the bitmap
+ *                            (made from the list if the wave kept none). Results never depend on it (tests pin
+ *                            both paths).
  *   FGI_OPT_RUN_OFFSET_BITS [28] tests only: a pull candidate's record names its tail run by an offset
  *                            below 2^bits words from its pull block's base; a candidate past that is
  *                            found through the per-slot list offsets instead (tests pin that path on
@@ -590,6 +659,7 @@ fgi_status fgi_stream(fgi_graph* g, void** stream);
 #define FGI_OPT_RUN_OFFSET_BITS 17
 #define FGI_OPT_PART_VIEW_PATH 18
 #define FGI_OPT_PART_IDS_PATH 19
+#define FGI_OPT_FANOUT_PATH 20
 /* 12 and 15: the measurement variants' options (include/fgi_variants.h); FGI_ENOTSUP here */
 fgi_status fgi_set_option(fgi_graph* g, int option, int64_t value);
 

@@ -428,6 +428,44 @@ enum { kPoutNone = 0, kPoutWave = 1, kPoutOther = 2 };
 // rank (profiles/part_ids_ab.txt): the two tie at n_local / 256 and the gather wins above.
 constexpr uint32_t kPartIdsGatherDen = 256;
 
+// The subscription table of the replica fan-out (fanout.hip), over boundary handles.
+// rec: 16-byte records chained from head[h] (FGI_NONE ends a chain); has: bit h set = head[h] != FGI_NONE.
+// Free records: the stack fstack[0, free_n) and the never-used range [bump, cap). The host mirrors both
+// counts from numbers the calls read back anyway (stored, delivered, dropped), so no kernel keeps a cursor.
+// pcnt[p]: live entries of peer p. The last fan-out's lists stay on the device (out_*) for the repeat calls.
+struct SubRec {
+    unsigned long long call;
+    uint32_t peer, next;
+};
+enum { kCascNone = 0, kCascWave = 1, kCascAsync = 2, kCascBatch = 3 };
+struct Fanout {
+    uint32_t* head = nullptr;              // [ext_handles]
+    unsigned long long* has = nullptr;     // [words]
+    uint64_t words = 0;
+    SubRec* rec = nullptr;                 // [cap]
+    uint32_t* fstack = nullptr;            // [cap]
+    uint64_t cap = 0, bump = 0, free_n = 0;
+    unsigned long long* pcnt = nullptr;    // [FGI_MAX_PEERS]
+    unsigned long long* ctr = nullptr;     // [8] device counters of a call; ctr_h: pinned copy
+    unsigned long long* ctr_h = nullptr;
+    uint32_t* tcnt = nullptr;              // [tiles][n_peers] per-tile counts, scanned per peer in place
+    uint64_t tcnt_cap = 0;
+    unsigned long long* tot = nullptr;     // [FGI_MAX_PEERS] a fan-out's entries per peer
+    unsigned long long* off = nullptr;     // [FGI_MAX_PEERS + 1] the last fan-out's peer offsets
+    unsigned long long* out_call = nullptr;
+    uint32_t* out_hnd = nullptr;
+    uint64_t out_cap = 0;
+    uint32_t* ids = nullptr;               // fgi_fanout_ids' upload
+    uint64_t ids_cap = 0;
+    unsigned long long* bits = nullptr;    // [words] the invalidated set as a bitmap when the wave kept none
+    uint64_t made_serial = 0;              // casc_serial the lists were made for (0: none)
+    uint32_t made_peers = 0;
+    uint64_t made_n = 0;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint64_t live = 0, delivered = 0, dropped = 0, fanouts = 0, from_list = 0, from_bits = 0;
+    double last_ms = 0;
+};
+
 }  // namespace fgi
 
 struct fgi_graph {
@@ -766,6 +804,13 @@ struct fgi_graph {
     fgi::PartOut* pout = nullptr;
     int pout_kind = 0;
     int opt_part_ids_path = 0;         // FGI_OPT_PART_IDS_PATH: 0 by the wave's count, 1 scatter, 2 gather
+    // Replica fan-out (fanout.hip). fan: the subscription table, null until the first
+    // fgi_subscribe. casc_serial counts the calls that ran cascades (and fgi_restore), casc_kind says what
+    // the last one was (kCasc*): fgi_last_wave_fanout makes its lists once per serial, from a kCascWave only.
+    fgi::Fanout* fan = nullptr;
+    uint64_t casc_serial = 0;
+    int casc_kind = 0;
+    int opt_fanout_path = 0;           // FGI_OPT_FANOUT_PATH: 0 by what the wave left, 1 id list, 2 bitmap
 };
 
 // ---- internal entry points shared between translation units ----------------------------------
@@ -1027,6 +1072,20 @@ fgi_status part_out_stage_roots(fgi_graph* g, uint32_t n, const uint32_t* roots,
 fgi_status part_out_bits(fgi_graph* g, const unsigned long long** bits_dev, uint64_t* words);
 fgi_status part_out_ids(fgi_graph* g, const uint32_t** ids_dev, uint32_t* host_copy);
 void part_out_destroy(fgi_graph* g);
+// ---- replica fan-out (fanout.hip) ----
+// A call that runs cascades says so before it starts (fgi_restore: kCascNone): the previous wave's fan-out
+// lists are forgotten. Touches host fields only.
+inline void fanout_note(fgi_graph* g, int kind) {
+    ++g->casc_serial;
+    g->casc_kind = kind;
+}
+// whether the graph holds subscriptions (everything below is a no-op returning FGI_OK otherwise)
+inline bool fanout_live(const fgi_graph* g) { return g->fan && g->fan->live; }
+// the entries of from[i] move to to[i] (boundary handles, host arrays; to[i] == FGI_NONE: nothing moves)
+fgi_status fanout_move(fgi_graph* g, uint32_t n, const uint32_t* from, const uint32_t* to);
+// the entries of the listed boundary handles (host array) are dropped
+fgi_status fanout_drop_handles(fgi_graph* g, uint32_t n, const uint32_t* handles);
+void fanout_destroy(fgi_graph* g);
 // ---- sharded loads (shard.hip) ----
 // The collectives they add to a partition's transport (part.hip, PartComm): host words (at most kShardWords
 // per rank) all-gathered on the host; device byte ranges with per-peer counts, all-gathered (src[0,

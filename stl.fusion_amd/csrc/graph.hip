@@ -1916,7 +1916,9 @@ fgi_status fgi_version(uint32_t* major, uint32_t* minor) {
     // 0.7: the same view per rank of a partition (fgi_part_state_view_open, fgi_part_view_is_consistent)
     // 0.8: a partitioned wave from host roots, its ids or bitmap in the host's numbering made on the device
     //      (fgi_part_invalidate_host, fgi_part_invalidate_bits, fgi_part_last_wave_ids / _bits, fgi_part_wave_ids_dev)
-    if (minor) *minor = 8;
+    // 0.9: the replica fan-out on the device (fgi_subscribe, fgi_last_wave_fanout, fgi_fanout_ids,
+    //      fgi_unsubscribe_peer, fgi_sub_stats_get)
+    if (minor) *minor = 9;
     return FGI_OK;
 }
 
@@ -2003,6 +2005,7 @@ fgi_status fgi_destroy(fgi_graph* g) {
     if (!g) return FGI_OK;
     hipSetDevice(g->device);
     if (g->stream) hipStreamSynchronize(g->stream);
+    fgi::fanout_destroy(g);
     fgi::part_out_destroy(g);
     fgi::part_destroy(g);
     fgi::view_destroy(g);
@@ -2460,6 +2463,7 @@ fgi_status fgi_restore(fgi_graph* g) {
     // wave (only graphs that can flag have one); the gate is the snapshot's again
     g->flg_valid = false;
     g->flag_gate = g->snap_flag_gate;
+    fanout_note(g, kCascNone);   // no wave's fan-out is left to make (the subscriptions themselves stay)
     g->flg_last = -1;
     g->flg_drop.clear();
     g->pflg_runs.clear();   // a partition's records too (fgi_part_last_flagged: 0 records)
@@ -2569,6 +2573,10 @@ fgi_status fgi_set_option(fgi_graph* g, int option, int64_t value) {
         g->opt_part_ids_path = (int)value;
         // what the last wave's accessors made already is made again on the next call, by the path now set
         if (g->pout) g->pout->bits_valid = g->pout->ids_valid = false;
+        return FGI_OK;
+    case FGI_OPT_FANOUT_PATH:
+        if (value < 0 || value > 2) return set_err(g, FGI_EINVAL, "fan-out path must be 0, 1 or 2");
+        g->opt_fanout_path = (int)value;
         return FGI_OK;
     case FGI_OPT_PROBE_SUMMARY:
         if (value < -1 || value > (int64_t)FGI_NONE) return set_err(g, FGI_EINVAL, "probe summary: -1 or a word count");
@@ -2865,6 +2873,7 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
                        cnt[1]);
     // displacement cascade first (ComputedRegistry.cs:91-94), then detach + install
     g->last_wave_n = 0;
+    fanout_note(g, kCascWave);   // a call that displaces nothing ran an empty cascade
     if (cnt[0]) FGI_TRY(run_wave(g, (uint32_t)cnt[0], droots, nullptr, stats, false, WaveOut::kCount));
     view_begin(g);   // the cascade's share of the state view is in; the install's follows below
     // the call's slots hold new nodes when it returns: a displaced node the cascade flagged is not in the
@@ -2893,6 +2902,8 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
     view_end(g);   // the copy waited for the flush
     g->free_detached.resize(g->free_detached.size() - take.size());
     if (out_detached) std::memcpy(out_detached, od.data(), n * sizeof(uint32_t));
+    // subscriptions follow the node: a displaced node that lives on takes its entries to its detached handle
+    if (fanout_live(g)) FGI_TRY(fanout_move(g, n, slot, od.data()));
     return FGI_OK;
 }
 
@@ -2992,6 +3003,7 @@ fgi_status fgi_set_output(fgi_graph* g, uint32_t n, const uint32_t* handle, uint
     FGI_TRY(d2h(g, &nr, g->misc_dev, 1));
     if (out_set) FGI_TRY(d2h(g, out_set, dset, n));
     g->last_wave_n = 0;
+    fanout_note(g, kCascWave);   // a call without roots ran an empty cascade
     if (nr)   // Invalidate() (Computed.cs:153-156)
         FGI_TRY(run_wave(g, (uint32_t)nr, droots, nullptr, stats, false, out_ids ? WaveOut::kIds : WaveOut::kCount));
     if (view_on(g)) {   // the handles' new states (Consistent, or what the cascade left) from their words and visit bits
@@ -3159,6 +3171,7 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
     }
     FGI_TRY(single_only(g, "fgi_run_batch"));
     g->flg_last = -2;   // the batch's cascades report through fgi_last_batch_flagged (bflg_runs)
+    fanout_note(g, kCascBatch);
     g->flg_drop.clear();
     g->bflg_runs.clear();
     g->bflg_step.clear();
@@ -3407,6 +3420,27 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
         if (rec_on) FGI_TRY(view_refresh(g, kViewRecords, g->brec, std::min<uint64_t>(scr_h[rcur_word], g->brec_cap)));
         return view_commit(g);
     };
+    // Subscriptions follow the node (fanout.hip): behind the batch, the BEGIN_COMPUTE steps [0, end) move a
+    // displaced node's entries to its detached handle, in step order. Nobody subscribes mid-batch, so only the
+    // first such step on a slot can find entries there: the nodes later steps displace were made by the batch.
+    auto sub_moves = [&](uint32_t end) -> fgi_status {
+        if (!fanout_live(g) || !n_begin) return FGI_OK;
+        std::vector<uint32_t> from, to;
+        std::vector<uint8_t>& seen = g->seen_slots;   // sized by the staging checks above; cleared again below
+        for (uint32_t k = 0; k < end; ++k) {
+            const fgi_step& sp = steps[k];
+            if (sp.kind != FGI_STEP_BEGIN_COMPUTE) continue;
+            const uint32_t* o = reinterpret_cast<const uint32_t*>(H + res_off + bs[k].out_off);
+            for (uint32_t i = 0; i < sp.n; ++i) {
+                if (seen[sp.handles[i]]) continue;
+                seen[sp.handles[i]] = 1;
+                from.push_back(sp.handles[i]);
+                to.push_back(o[i] == FGI_NONE ? FGI_NONE : o[i] - g->lbl_K);
+            }
+        }
+        for (const uint32_t x : from) seen[x] = 0;
+        return fanout_move(g, (uint32_t)from.size(), from.data(), to.data());
+    };
     view_begin(g);
     while (true) {
         fgi_status s = batch_launch(g, from, n_steps, steps, bs, scr, take, n_take, timed, wave_ev, rec_on ? &sink : nullptr);
@@ -3460,12 +3494,14 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
         note_runs(k);
         g->free_detached.resize(g->free_detached.size() - (size_t)scr_h[2]);
         FGI_TRY(view_sync());   // the steps before k are applied
+        FGI_TRY(sub_moves(k));
         return set_err(g, FGI_ECAPACITY, "step %u: out of detached handles (%zu free)", k, g->free_detached.size());
     }
     // host bookkeeping: the cascades' record runs, the detached handles taken, the per-step outputs
     note_runs(n_steps);
     g->free_detached.resize(g->free_detached.size() - (size_t)scr_h[2]);
     FGI_TRY(view_sync());
+    FGI_TRY(sub_moves(n_steps));
     for (uint32_t k = 0; k < n_steps; ++k) {
         const fgi_step& sp = steps[k];
         if (!sp.out || !sp.n) continue;
@@ -3770,6 +3806,10 @@ fgi_status fgi_release(fgi_graph* g, uint32_t n, const uint32_t* handle) {
     view_begin(g);
     // the state view follows the handles released so far, also when a later one is refused
     auto leave = [&](uint32_t released, fgi_status st) {
+        if (fanout_live(g)) {   // a released handle's subscriptions go with it (fgi_sub_stats.dropped)
+            const fgi_status fs = fanout_drop_handles(g, released, handle);
+            if (st == FGI_OK) st = fs;
+        }
         if (!view_on(g)) return st;
         fgi_status vs = view_refresh_host(g, handle, released);
         if (vs == FGI_OK) vs = view_commit(g);

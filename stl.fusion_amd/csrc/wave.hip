@@ -3946,6 +3946,7 @@ fgi_status run_wave(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_dev, c
     const auto t0 = std::chrono::steady_clock::now();
     const bool ids = out == WaveOut::kIds;   // the list kernel runs inside the wave (else on demand: ensure_ids)
     g->flg_last = -1;
+    fanout_note(g, kCascWave);
     g->flg_drop.clear();
     forget_async_results(g, g->inv);   // the list goes to g->inv (now, or on demand: ensure_ids)
     hipStream_t s = g->stream;
@@ -4190,6 +4191,7 @@ fgi_status run_wave_async(fgi_graph* g, uint32_t n_roots, const uint32_t* roots_
     fgi_graph::AsyncWave& a = g->aw[t & 1];
     if (a.busy) FGI_TRY(wave_wait(g, a.ticket, nullptr, nullptr, nullptr));   // at most two in flight
     g->flg_last = -1;
+    fanout_note(g, kCascAsync);
     g->flg_drop.clear();
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t s = g->stream;

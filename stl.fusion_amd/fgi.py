@@ -33,6 +33,9 @@ OPT_PROBE_SUMMARY = 15
 OPT_RUN_OFFSET_BITS = 17
 OPT_PART_VIEW_PATH = 18   # partitions with codes and a state view: 0 by the wave's size, 1 scatter, 2 gather
 OPT_PART_IDS_PATH = 19    # partitions with codes, a wave's ids / bitmap in the host's numbering: the same choice
+OPT_FANOUT_PATH = 20      # the replica fan-out's source: 0 by what the wave left, 1 its id list, 2 its bitmap
+MAX_PEERS = 4096
+SUB_ADDED, SUB_INVALIDATED = 0, 1
 DIR_AUTO, DIR_PUSH, DIR_PULL = 0, 1, 2
 NONE = 0xFFFFFFFF
 COMPUTING, CONSISTENT, INVALIDATED = 0, 1, 2
@@ -106,6 +109,16 @@ class StateViewStruct(C.Structure):
 class ViewStats(C.Structure):
     _fields_ = [("updates", C.c_uint64), ("words_published", C.c_uint64), ("full_builds", C.c_uint64),
                 ("extra_waits", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SubStats(C.Structure):
+    """fgi_sub_stats: the replica fan-out's subscription table."""
+    _fields_ = [("live", C.c_uint64), ("pool", C.c_uint64), ("delivered", C.c_uint64), ("dropped", C.c_uint64),
+                ("fanouts", C.c_uint64), ("from_list", C.c_uint64), ("from_bits", C.c_uint64),
+                ("last_kernel_ms", C.c_double)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -237,6 +250,11 @@ SIGNATURES = {
     "fgi_part_last_wave_ids": [_G, _u32p, C.c_uint64, _u64p],
     "fgi_part_last_wave_bits": [_G, _u64p, C.c_uint64, _u64p],
     "fgi_part_wave_ids_dev": [_G, C.POINTER(C.c_void_p), _u64p],
+    "fgi_subscribe": [_G, C.c_uint32, _u32p, _u32p, _u64p, _u32p],
+    "fgi_last_wave_fanout": [_G, C.c_uint32, _u64p, _u64p, _u32p, C.c_uint64, _u64p],
+    "fgi_fanout_ids": [_G, C.c_uint64, _u32p, C.c_uint32, _u64p, _u64p, _u32p, C.c_uint64, _u64p],
+    "fgi_unsubscribe_peer": [_G, C.c_uint32, _u64p],
+    "fgi_sub_stats_get": [_G, C.POINTER(SubStats)],
 }
 
 _lib = None
@@ -568,6 +586,53 @@ class Graph:
         self._check(self.lib.fgi_last_wave_ids(self.h, _ptr(ids, C.c_uint32), len(ids), C.byref(n)),
                     "last_wave_ids")
         return ids
+
+    # ---- replica fan-out (C-ABI 0.9) ----
+    def subscribe(self, handles, peers, call_ids) -> np.ndarray:
+        """fgi_subscribe: store (handle, peer, call id) entries; returns SUB_ADDED / SUB_INVALIDATED per entry
+        (an entry on an Invalidated or empty handle is not stored: the host sends its message at once)."""
+        h, p, c = _u32(handles), _u32(peers), _u64(call_ids)
+        if not (len(h) == len(p) == len(c)):
+            raise ValueError("subscribe: handles, peers and call_ids differ in length")
+        res = np.zeros(len(h), np.uint32)
+        self._check(self.lib.fgi_subscribe(self.h, len(h), _ptr(h, C.c_uint32), _ptr(p, C.c_uint32),
+                                           _ptr(c, C.c_uint64), _ptr(res, C.c_uint32)), "subscribe")
+        return res
+
+    def last_wave_fanout(self, n_peers: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """fgi_last_wave_fanout: (peer_off, call_ids, handles) of the entries the last wave released:
+        peer p's are [peer_off[p], peer_off[p + 1]), by ascending handle. One-shot: they leave the table."""
+        off = np.zeros(n_peers + 1, np.uint64)
+        n = C.c_uint64()
+        self._check(self.lib.fgi_last_wave_fanout(self.h, n_peers, _ptr(off, C.c_uint64), None, None, 0, C.byref(n)),
+                    "last_wave_fanout")
+        calls, hnd = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint32)
+        self._check(self.lib.fgi_last_wave_fanout(self.h, n_peers, _ptr(off, C.c_uint64), _ptr(calls, C.c_uint64),
+                                                  _ptr(hnd, C.c_uint32), len(calls), C.byref(n)), "last_wave_fanout")
+        return off, calls, hnd
+
+    def fanout_ids(self, ids, n_peers: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """fgi_fanout_ids: the same join for a strictly ascending handle list the host holds."""
+        i = _u32(ids)
+        cap = int(self.sub_stats()["live"])
+        off = np.zeros(n_peers + 1, np.uint64)
+        calls, hnd = np.zeros(cap, np.uint64), np.zeros(cap, np.uint32)
+        n = C.c_uint64()
+        self._check(self.lib.fgi_fanout_ids(self.h, len(i), _ptr(i, C.c_uint32), n_peers, _ptr(off, C.c_uint64),
+                                            _ptr(calls, C.c_uint64), _ptr(hnd, C.c_uint32), cap, C.byref(n)),
+                    "fanout_ids")
+        return off, calls[:n.value].copy(), hnd[:n.value].copy()
+
+    def unsubscribe_peer(self, peer: int) -> int:
+        """fgi_unsubscribe_peer: drop a disconnected peer's entries; returns how many."""
+        n = C.c_uint64()
+        self._check(self.lib.fgi_unsubscribe_peer(self.h, peer, C.byref(n)), "unsubscribe_peer")
+        return int(n.value)
+
+    def sub_stats(self) -> dict:
+        st = SubStats()
+        self._check(self.lib.fgi_sub_stats_get(self.h, C.byref(st)), "sub_stats")
+        return st.as_dict()
 
     def last_wave_flagged(self) -> Tuple[np.ndarray, np.ndarray]:
         """fgi_last_wave_flagged: (handles, state_flags) of the nodes the last call's cascade flagged

@@ -80,7 +80,10 @@ ComputedRegistry::ComputedRegistry(uint32_t n_slots, uint32_t n_detached, int de
     has_obj_.assign(n_handles_, 0);
 }
 
-ComputedRegistry::~ComputedRegistry() { FGI_CALL(fgi_destroy, g_); }
+ComputedRegistry::~ComputedRegistry() {
+    if (dev_buf_) fgi_free_pinned(dev_buf_);
+    FGI_CALL(fgi_destroy, g_);
+}
 
 void ComputedRegistry::Check(fgi_status s, const char* what) const {
     if (s != FGI_OK) throw FgiError(s, std::string(what) + ": " + FGI_CALL(fgi_last_error, g_));
@@ -162,7 +165,7 @@ std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& inpu
                     StartTimer(detached, old->version_, old->delay_);
             }
         }
-        MoveSubs(s, detached);   // the replicas follow the old node
+        if (!DeviceFanout) MoveSubs(s, detached);   // the replicas follow the old node (the engine moves its own)
     } else if (old) {
         old->gone_ = true;   // the slot names the new node from here on (its handlers may still read its state)
     }
@@ -259,6 +262,8 @@ void ComputedRegistry::DispatchBits(const uint64_t* bits, uint64_t words, uint64
 
 void ComputedRegistry::DispatchImpl(const uint32_t* ids, const uint64_t* bits, uint64_t words, uint64_t n) {
     const auto t0 = std::chrono::steady_clock::now();
+    const bool from_ticket = from_ticket_;
+    from_ticket_ = false;   // read once: the callbacks below may run waves of their own
     DropTimers(ids, bits, words, n);
     std::unique_ptr<uint32_t[]> own;
     uint64_t own_cap = 0;
@@ -289,7 +294,65 @@ void ComputedRegistry::DispatchImpl(const uint32_t* ids, const uint64_t* bits, u
         std::vector<std::pair<uint32_t, std::shared_ptr<Computed>>> objs;
     };
     std::vector<Part> parts(T);
-    const bool any_subs = !subs_.empty() && !sub_head_.empty();
+    // DeviceFanout: the per-peer lists come from the engine's join (fgi_last_wave_fanout; a ticket's ids through
+    // fgi_fanout_ids), fetched before the gather releases detached handles (a release drops their entries);
+    // the gather then only resolves host objects and never touches sub_head_
+    // The call ids land in a page-locked buffer kept across waves (no zero-fill, a copy at the link's rate).
+    // This fan-out owns it while its callbacks run (a nested wave gets a fresh one), like the ids buffer.
+    std::vector<uint64_t> dev_off;
+    struct Lease {   // hands the (larger) buffer back when this fan-out ends, also by an exception
+        ComputedRegistry* r;
+        uint64_t* p;
+        uint64_t cap;
+        ~Lease() {
+            if (!p) return;
+            if (cap > r->dev_buf_cap_) {
+                if (r->dev_buf_) fgi_free_pinned(r->dev_buf_);
+                r->dev_buf_ = p;
+                r->dev_buf_cap_ = cap;
+            } else {
+                fgi_free_pinned(p);
+            }
+        }
+    } lease{this, dev_buf_, dev_buf_cap_};
+    uint64_t*& dev_calls = lease.p;
+    uint64_t& dev_cap = lease.cap;
+    dev_buf_ = nullptr;
+    dev_buf_cap_ = 0;
+    auto dev_room = [&](uint64_t entries) {   // 8 B of call id and 4 B of handle per entry
+        if (dev_cap >= entries && dev_calls) return;
+        if (dev_calls) fgi_free_pinned(dev_calls);
+        dev_calls = nullptr;
+        dev_cap = 0;
+        void* p = nullptr;
+        Check(fgi_alloc_pinned(std::max<uint64_t>(entries, 4096) * 12, &p), "fgi_alloc_pinned");
+        dev_calls = static_cast<uint64_t*>(p);
+        dev_cap = std::max<uint64_t>(entries, 4096);
+    };
+    if (DeviceFanout && dev_subs_ && P && n) {
+        dev_off.assign((size_t)P + 1, 0);
+        uint64_t tot = 0;
+        if (from_ticket && ids) {
+            fgi_sub_stats st{};
+            Check(FGI_CALL(fgi_sub_stats_get, g_, &st), "fgi_sub_stats_get");
+            dev_room(std::max<uint64_t>(st.live, 1));
+            Check(FGI_CALL(fgi_fanout_ids, g_, n, ids, P, dev_off.data(), dev_calls, reinterpret_cast<uint32_t*>(dev_calls + dev_cap),
+                           dev_cap, &tot),
+                  "fgi_fanout_ids");
+        } else {
+            Check(FGI_CALL(fgi_last_wave_fanout, g_, P, dev_off.data(), nullptr, nullptr, 0, &tot), "fgi_last_wave_fanout");
+            if (tot) {
+                dev_room(tot);
+                Check(FGI_CALL(fgi_last_wave_fanout, g_, P, dev_off.data(), dev_calls, nullptr, dev_cap, &tot),
+                      "fgi_last_wave_fanout");
+            }
+        }
+        fgi_sub_stats st{};
+        Check(FGI_CALL(fgi_sub_stats_get, g_, &st), "fgi_sub_stats_get");
+        fan.device = 1;
+        fan.device_kernel_ms = st.last_kernel_ms;
+    }
+    const bool any_subs = !DeviceFanout && !subs_.empty() && !sub_head_.empty();
     auto gather = [&](uint32_t t) {
         Part& pt = parts[t];
         pt.calls.resize(P);
@@ -353,9 +416,12 @@ void ComputedRegistry::DispatchImpl(const uint32_t* ids, const uint64_t* bits, u
     for (uint32_t q = 0; q < P; ++q) {
         uint64_t tot = 0;
         for (auto& pt : parts) tot += pt.calls[q].size();
+        if (!dev_off.empty()) tot = dev_off[q + 1] - dev_off[q];
         if (!tot) continue;
         const uint64_t* data;
-        if (T == 1) {
+        if (!dev_off.empty()) {
+            data = dev_calls + dev_off[q];
+        } else if (T == 1) {
             data = parts[0].calls[q].data();
         } else {
             buf.clear();
@@ -425,6 +491,26 @@ void ComputedRegistry::Subscribe(uint32_t handle, uint32_t peer, uint64_t call_i
 }
 
 void ComputedRegistry::Subscribe(size_t n, const uint32_t* handles, const uint32_t* peers, const uint64_t* call_ids) {
+    if (DeviceFanout) {
+        // the engine stores the entries (fgi_subscribe); a node that is Invalidated already completes its
+        // WhenInvalidated at once (ComputedExt.cs:99-125): its call id goes to the peer's sink now
+        for (size_t i = 0; i < n; ++i)
+            if (peers[i] >= peers_.size()) throw FgiError(FGI_EINVAL, "Subscribe: bad handle or peer");
+        std::vector<uint32_t> res(n);
+        Check(FGI_CALL(fgi_subscribe, g_, (uint32_t)n, handles, peers, call_ids, res.data()), "fgi_subscribe");
+        dev_subs_ = true;
+        std::vector<std::vector<uint64_t>> now;
+        for (size_t i = 0; i < n; ++i) {
+            if (res[i] != FGI_SUB_INVALIDATED) continue;
+            if (now.empty()) now.resize(peers_.size());
+            now[peers[i]].push_back(call_ids[i]);
+        }
+        const size_t B = std::max<size_t>(1, PeerBatch);
+        for (uint32_t q = 0; q < now.size(); ++q)
+            for (size_t o = 0; o < now[q].size(); o += B)
+                if (peers_[q]) peers_[q](q, now[q].data() + o, std::min(B, now[q].size() - o));
+        return;
+    }
     if (sub_head_.empty()) sub_head_.assign(n_handles_, kNone);   // once, on the first subscription
     for (size_t i = 0; i < n; ++i) {
         const uint32_t h = handles[i];
@@ -509,6 +595,7 @@ void ComputedRegistry::Complete(uint64_t ticket) {
         last_ = ws;
         pred_v_ = n;
         StartTimers(t);
+        from_ticket_ = true;   // the device fan-out of a ticket's ids goes through fgi_fanout_ids
         Dispatch(ids, n);
     }
 }

@@ -147,6 +147,8 @@ struct FanoutStats {
     uint32_t bitmap = 0;         // 1: dispatched from the wave's invalidated bitmap (fgi_invalidate_bits)
     double dispatch_ms = 0;      // whole Dispatch
     double gather_ms = 0;        // parallel phase (subscriptions -> per-peer lists)
+    uint32_t device = 0;         // 1: the per-peer lists came from the engine's join (DeviceFanout)
+    double device_kernel_ms = 0; // ... and the device time of its kernels (fgi_sub_stats.last_kernel_ms)
     std::vector<uint64_t> peer_calls, peer_batches;   // per peer id
 };
 
@@ -243,6 +245,12 @@ class ComputedRegistry {
     void Subscribe(uint32_t handle, uint32_t peer, uint64_t call_id);
     void Subscribe(size_t n, const uint32_t* handles, const uint32_t* peers, const uint64_t* call_ids);
     size_t PeerBatch = 4096;
+    // The subscriptions live in the engine (fgi_subscribe) and a wave's per-peer lists come from its join on
+    // the device (fgi_last_wave_fanout; fgi_fanout_ids for an asynchronous ticket's ids) instead of the gather
+    // over sub_head_. Set before the first Subscribe and left alone afterwards; at most FGI_MAX_PEERS peers.
+    // Subscribing to a node that is Invalidated already delivers its call id at once. Handler objects and
+    // delay timers keep their host path.
+    bool DeviceFanout = false;
     uint32_t FanoutThreads = 0;   // 0: hardware concurrency, capped at 16
 
     // how a wave's invalidated set comes back: 0 auto (the bitmap once the previous wave invalidated
@@ -325,6 +333,10 @@ class ComputedRegistry {
     std::vector<uint32_t> sub_head_;
     std::vector<Sub> subs_;
     std::vector<uint32_t> sub_free_;
+    bool dev_subs_ = false;     // DeviceFanout: the engine holds subscriptions
+    bool from_ticket_ = false;  // the Dispatch about to run fans out an asynchronous ticket's ids
+    uint64_t* dev_buf_ = nullptr;   // page-locked: a device fan-out's call ids (and a ticket's handles behind them)
+    uint64_t dev_buf_cap_ = 0;      // entries
 };
 
 }  // namespace fusion
