@@ -511,8 +511,7 @@ struct fgi_graph {
     uint32_t* used_cnt = nullptr;
     uint32_t* home = nullptr;          // [n_detached]: home slot of a detached handle
     std::vector<uint32_t> free_detached;  // host free list of detached handles
-    std::vector<uint64_t> seen_bits;      // host scratch bitmap over slots (batch duplicate checks)
-    std::vector<uint8_t> seen_slots;      // host scratch, a byte per slot (fgi_run_batch's duplicate checks)
+    std::vector<uint8_t> seen_slots;      // host scratch, a byte per slot, all-zero between uses (slot-repeat checks)
     // device temporaries of the mutation calls, kept for reuse (same stream, so reuse is ordered
     // after the previous user) instead of a hipMalloc + hipFree (an implicit device sync) per call
     std::vector<std::pair<size_t, void*>> tmp_cache;
@@ -1107,9 +1106,6 @@ fgi_status part_local_run(fgi_graph* const* gs, uint32_t P, const std::function<
 // load_rows from device arrays (left untouched)
 fgi_status load_rows_dev(fgi_graph* g, uint64_t m, const uint64_t* dev_keys, const uint64_t* dev_tags, uint32_t src_base,
                          uint32_t dst_base);
-// Append (used, dependant slot, tag) entries to rows (set semantics, no state checks).
-fgi_status append_edges(fgi_graph* g, uint64_t m, const uint32_t* used_dev, const uint32_t* dep_dev,
-                        const uint64_t* tag_dev, const uint32_t* dep_handle_dev);
 }  // namespace fgi
 
 #define FGI_HIP(g, call)                                                   \

@@ -2775,6 +2775,22 @@ static fgi_status copy_flagged(fgi_graph* g, const std::vector<uint64_t>& set, c
     return FGI_OK;
 }
 
+// the flagged sets of a call with several cascades (a batch's, a partitioned call's), each entry with its step
+static fgi_status copy_step_flagged(fgi_graph* g, const std::vector<uint64_t>& set, const std::vector<uint32_t>& step,
+                                    uint32_t* out_step, uint32_t* out_ids, uint32_t* out_flags, uint64_t cap, uint64_t* out_n) {
+    const uint64_t n = set.size();
+    if (out_n) *out_n = n;
+    if (!out_ids) return FGI_OK;
+    if (n > cap) return set_err(g, FGI_ECAPACITY, "the call's flagged sets hold %llu entries, the buffer %llu",
+                                (unsigned long long)n, (unsigned long long)cap);
+    for (uint64_t i = 0; i < n; ++i) {
+        out_ids[i] = (uint32_t)(set[i] >> 32);
+        if (out_step) out_step[i] = step[i];
+        if (out_flags) out_flags[i] = (uint32_t)set[i];
+    }
+    return FGI_OK;
+}
+
 fgi_status fgi_last_wave_flagged(fgi_graph* g, uint32_t* out_ids, uint32_t* out_flags, uint64_t cap, uint64_t* out_n) {
     if (!g) return FGI_EINVAL;
     FGI_TRY(usable(g));
@@ -2818,28 +2834,96 @@ fgi_status fgi_invalidate_all(fgi_graph* g, uint32_t* out_ids, uint64_t cap, uin
     return copy_ids(g, out_ids, cap, out_n);
 }
 
+// ---- what the mutation entry points share (single calls, batches, partitions) -------------------
+// The host scratch of the slot-repeat checks, a byte per slot below `limit`: all-zero between uses.
+static std::vector<uint8_t>& seen_scratch(fgi_graph* g, uint32_t limit) {
+    if (g->seen_slots.size() < limit) g->seen_slots.assign(limit, 0);
+    return g->seen_slots;
+}
+
+// The begin_compute argument check of every entry point: the first offender by index; within an item
+// the slot's range (value: the slot), then the version (0 or > kVMask; value: the index), then a slot
+// that an earlier item named (value: the slot). why == nullptr: the arguments are good.
+struct BadBegin { const char* why; uint32_t value; };
+static BadBegin check_begin_args(fgi_graph* g, uint32_t limit, uint32_t n, const uint32_t* slot, const uint64_t* version) {
+    std::vector<uint8_t>& seen = seen_scratch(g, limit);
+    BadBegin bad{nullptr, 0};
+    uint32_t i = 0;
+    for (; i < n && !bad.why; ++i) {
+        const uint32_t x = slot[i];
+        if (x >= limit) bad = {"slot out of range", x};
+        else if (version[i] == 0 || version[i] > kVMask) bad = {"bad version", i};
+        else if (seen[x]) bad = {"slot repeated in one step", x};
+        else seen[x] = 1;
+    }
+    for (uint32_t j = 0; j < i; ++j)   // every item looked at, the offender included (it may be out of range)
+        if (slot[j] < limit) seen[slot[j]] = 0;
+    return bad;
+}
+
+// The kernels' argument blocks: every graph-owned field from g, the per-call pointers as parameters. The
+// only places that spell out the structs' field order.
+static InstallArgs install_args(fgi_graph* g, const uint32_t* slot, const uint64_t* version, const uint8_t* has_delay,
+                                const uint8_t* cls, const uint32_t* free_h, unsigned long long* cursor, uint32_t* out_det) {
+    return InstallArgs{slot,       version,    has_delay,  cls,         free_h,  cursor,
+                       g->n_slots, reinterpret_cast<unsigned long long*>(g->node),
+                       g->row_off, g->row_len, g->row_cap, g->used_cnt, g->home, out_det};
+}
+// dep, used and result are null where only the append kernels run (a partition classifies with its own
+// kernel, k_pau_classify); it also clears used_cnt: the dependant's owner counts, in k_pau_apply
+static AuArgs au_args(fgi_graph* g, const uint32_t* dep, const uint32_t* used, uint32_t* result, unsigned long long* hset,
+                      uint64_t hcap, Cand* cand, uint32_t* pend_pos, uint32_t* ovf_rows, unsigned long long* cnt) {
+    return AuArgs{dep,        used,       g->n_slots, g->home,     reinterpret_cast<unsigned long long*>(g->node),
+                  g->row_off, g->row_len, g->row_cap, g->used_cnt, g->pool_col, g->pool_tag,
+                  hset,       hcap - 1,   result,     cand,        pend_pos,    ovf_rows,    cnt};
+}
+
+// The install half of begin_compute: the top n_take handles of the free list uploaded, the displacement
+// cascade's visits folded, and k_bc_install queued over the n classified items (detached handles into
+// out_det). The free list itself shrinks in the caller, once the install's results have reached the host.
+static fgi_status install_nodes(fgi_graph* g, uint32_t n, uint64_t n_take, const uint32_t* slot, const uint64_t* version,
+                                const uint8_t* has_delay, const uint8_t* cls, uint32_t* out_det, Tmp& tfree) {
+    hipStream_t st = g->stream;
+    uint32_t* dfree_h;
+    FGI_TRY(tmalloc(g, tfree, &dfree_h, n_take + 1));
+    FGI_TRY(h2d(g, dfree_h, g->free_detached.data() + (g->free_detached.size() - n_take), n_take));
+    FGI_TRY(fold(g));   // the displacement cascade's visits
+    FGI_HIP(g, hipMemsetAsync(g->misc_dev + 2, 0, sizeof(unsigned long long), st));
+    const InstallArgs ia = install_args(g, slot, version, has_delay, cls, dfree_h, g->misc_dev + 2, out_det);
+    hipLaunchKernelGGL(k_bc_install, dim3(nblk(n)), dim3(256), 0, st, n, ia);
+    FGI_HIP(g, hipGetLastError());
+    return FGI_OK;
+}
+
+// The append tail of add_used: the nc candidates a classify kernel left (aa.cand, counters in aa.cnt)
+// reserve their places; rows that outgrew their capacity move to the pool top, which grows first if it must.
+static fgi_status append_candidates(fgi_graph* g, uint64_t nc, const AuArgs& aa) {
+    if (nc == 0) return FGI_OK;
+    hipStream_t st = g->stream;
+    touch(g);
+    hipLaunchKernelGGL(k_au_reserve, dim3(nblk(nc)), dim3(256), 0, st, nc, aa);
+    unsigned long long c2[2];
+    FGI_TRY(d2h(g, c2, aa.cnt + 1, 2));
+    if (c2[1] == 0) return FGI_OK;
+    hipLaunchKernelGGL(k_au_size, dim3(nblk(c2[1])), dim3(256), 0, st, (uint64_t)c2[1], aa.ovf_rows, g->row_len, aa.cnt + 3);
+    unsigned long long need = 0;
+    FGI_TRY(d2h(g, &need, aa.cnt + 3, 1));
+    FGI_TRY(ensure_pool(g, g->pool_top + need));
+    FGI_HIP(g, hipMemcpyAsync(g->pool_top_dev, &g->pool_top, sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_au_relocate, dim3(nblk(c2[1] * 64)), dim3(256), 0, st, (uint64_t)c2[1], aa.ovf_rows, g->row_off,
+                       g->row_len, g->row_cap, g->pool_col, g->pool_tag, g->pool_top_dev);
+    hipLaunchKernelGGL(k_au_pending, dim3(nblk(nc)), dim3(256), 0, st, nc, aa.cand, aa.pend_pos, g->row_off, g->pool_col,
+                       g->pool_tag);
+    g->pool_top += need;
+    return ensure_cstart(g, g->pool_top);
+}
+
 fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, const uint64_t* version,
                              const uint8_t* has_delay, uint32_t* out_detached, fgi_wave_stats* stats) {
     if (!g || (n && (!slot || !version))) return FGI_EINVAL;
     if (n == 0) return FGI_OK;
-    {
-        // O(n) validation over a reusable slot bitmap (cleared again bit by bit)
-        std::vector<uint64_t>& seen = g->seen_bits;
-        if (seen.size() < ((size_t)g->ext_slots + 63) / 64) seen.assign(((size_t)g->ext_slots + 63) / 64, 0);
-        uint32_t bad = FGI_NONE;
-        const char* why = nullptr;
-        uint32_t i = 0;
-        for (; i < n; ++i) {
-            const uint32_t x = slot[i];
-            if (x >= g->ext_slots) { why = "slot out of range"; bad = x; break; }
-            if (version[i] == 0 || version[i] > kVMask) { why = "bad version"; bad = i; break; }
-            const uint64_t m = 1ull << (x & 63);
-            if (seen[x >> 6] & m) { why = "slot repeated in one batch"; bad = x; break; }
-            seen[x >> 6] |= m;
-        }
-        for (uint32_t j = 0; j < i; ++j) seen[slot[j] >> 6] = 0;
-        if (why) return set_err(g, FGI_EINVAL, "%s (%u)", why, bad);
-    }
+    const BadBegin bad = check_begin_args(g, g->ext_slots, n, slot, version);
+    if (bad.why) return set_err(g, FGI_EINVAL, "%s (%u)", bad.why, bad.value);
     FGI_TRY(single_only(g, "fgi_begin_compute"));
     g->flag_gate = true;   // Computing nodes from here on (flagged sets)
     g->flg_last = -1;
@@ -2847,7 +2931,7 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
     hipSetDevice(g->device);
     hipStream_t st = g->stream;
     Tmp ts, tv, td, tc, tr, tf, to;
-    uint32_t *ds, *droots, *dfree_h, *dout;
+    uint32_t *ds, *droots, *dout;
     uint64_t* dv;
     uint8_t *dd = nullptr, *dcls;
     FGI_TRY(tmalloc(g, ts, &ds, n));
@@ -2880,18 +2964,9 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
     // call's flagged set under its slot (it lives on as out_detached[i])
     g->flg_drop.assign(slot, slot + n);
     std::sort(g->flg_drop.begin(), g->flg_drop.end());
-    std::vector<uint32_t> take(g->free_detached.end() - (ptrdiff_t)cnt[1], g->free_detached.end());
-    FGI_TRY(tmalloc(g, tf, &dfree_h, take.size() + 1));
-    FGI_TRY(h2d(g, dfree_h, take.data(), take.size()));
-    FGI_TRY(fold(g));   // the displacement cascade's visits
-    FGI_HIP(g, hipMemsetAsync(g->misc_dev + 2, 0, sizeof(unsigned long long), st));
     touch(g);
     note_words(g);
-    const InstallArgs ia{ds,          dv,          dd,         dcls,       dfree_h, g->misc_dev + 2, g->n_slots,
-                         reinterpret_cast<unsigned long long*>(g->node), g->row_off, g->row_len, g->row_cap,
-                         g->used_cnt, g->home, dout};
-    hipLaunchKernelGGL(k_bc_install, dim3(nblk(n)), dim3(256), 0, st, n, ia);
-    FGI_HIP(g, hipGetLastError());
+    FGI_TRY(install_nodes(g, n, cnt[1], ds, dv, dd, dcls, dout, tf));
     FGI_TRY(labels_map_out(g, dout, n));   // detached handles as the boundary numbers them
     // the state view: the slots' new nodes and the detached handles handed out, from their words
     FGI_TRY(view_refresh(g, kViewLabels, ds, n));
@@ -2900,7 +2975,7 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
     std::vector<uint32_t> od(n);
     FGI_TRY(d2h(g, od.data(), dout, n));
     view_end(g);   // the copy waited for the flush
-    g->free_detached.resize(g->free_detached.size() - take.size());
+    g->free_detached.resize(g->free_detached.size() - (size_t)cnt[1]);
     if (out_detached) std::memcpy(out_detached, od.data(), n * sizeof(uint32_t));
     // subscriptions follow the node: a displaced node that lives on takes its entries to its detached handle
     if (fanout_live(g)) FGI_TRY(fanout_move(g, n, slot, od.data()));
@@ -2938,33 +3013,11 @@ fgi_status fgi_add_used(fgi_graph* g, uint32_t n, const uint32_t* dependant, con
     note_words(g);   // may set InvalidateOnSetOutput (Computed.cs:376-378)
     FGI_HIP(g, hipMemsetAsync(dhash, 0xFF, hcap * sizeof(unsigned long long), st));
     FGI_HIP(g, hipMemsetAsync(g->misc_dev, 0, 8 * sizeof(unsigned long long), st));
-    const AuArgs aa{ddep,        duse,       g->n_slots,   g->home,     reinterpret_cast<unsigned long long*>(g->node),
-                    g->row_off,  g->row_len, g->row_cap,   g->used_cnt, g->pool_col,
-                    g->pool_tag, dhash,      hcap - 1,     dres,        dcand,
-                    dpend,       dovf,       g->misc_dev};
+    const AuArgs aa = au_args(g, ddep, duse, dres, dhash, hcap, dcand, dpend, dovf, g->misc_dev);
     hipLaunchKernelGGL(k_au_classify, dim3(nblk(n)), dim3(256), 0, st, n, aa);
     unsigned long long nc = 0;
     FGI_TRY(d2h(g, &nc, g->misc_dev, 1));
-    if (nc) {
-        touch(g);
-        hipLaunchKernelGGL(k_au_reserve, dim3(nblk(nc)), dim3(256), 0, st, (uint64_t)nc, aa);
-        unsigned long long c2[2];
-        FGI_TRY(d2h(g, c2, g->misc_dev + 1, 2));
-        if (c2[1]) {   // some rows outgrew their capacity: relocate them to the pool top
-            hipLaunchKernelGGL(k_au_size, dim3(nblk(c2[1])), dim3(256), 0, st, (uint64_t)c2[1], dovf, g->row_len,
-                               g->misc_dev + 3);
-            unsigned long long need = 0;
-            FGI_TRY(d2h(g, &need, g->misc_dev + 3, 1));
-            FGI_TRY(ensure_pool(g, g->pool_top + need));
-            FGI_HIP(g, hipMemcpyAsync(g->pool_top_dev, &g->pool_top, sizeof(uint64_t), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_au_relocate, dim3(nblk(c2[1] * 64)), dim3(256), 0, st, (uint64_t)c2[1], dovf,
-                               g->row_off, g->row_len, g->row_cap, g->pool_col, g->pool_tag, g->pool_top_dev);
-            hipLaunchKernelGGL(k_au_pending, dim3(nblk(nc)), dim3(256), 0, st, (uint64_t)nc, dcand, dpend, g->row_off,
-                               g->pool_col, g->pool_tag);
-            g->pool_top += need;
-            FGI_TRY(ensure_cstart(g, g->pool_top));
-        }
-    }
+    FGI_TRY(append_candidates(g, nc, aa));
     FGI_HIP(g, hipGetLastError());
     // the state view: a dependant may have gained InvalidateOnSetOutput
     FGI_TRY(view_refresh(g, kViewLabels, ddep, n));
@@ -3019,6 +3072,8 @@ namespace {
 
 constexpr size_t kStageAlign = 256;
 inline size_t stage_round(size_t b) { return (b + kStageAlign - 1) / kStageAlign * kStageAlign; }
+// FGI_BATCH_TIMES=1: a batch call's host phases on stderr (staging, enqueue, wait, unpacking; us)
+const bool batch_times = getenv("FGI_BATCH_TIMES") != nullptr;
 
 // Per-step device state of a batch (kept until the call returns: a pool growth resumes a step).
 struct BatchStep {
@@ -3040,15 +3095,44 @@ struct BatchStep {
     std::vector<Tmp> tmp;
 };
 
+// One fgi_run_batch call: the staging layout and the per-step device state, and the call's stages as
+// functions on them, in the order fgi_run_batch runs them.
+struct Batch {
+    using clk = std::chrono::steady_clock;
+    fgi_graph* const g;
+    const uint32_t n_steps;
+    const fgi_step* const steps;
+    const hipStream_t st;
+    uint64_t n_waves = 0, n_begin = 0, n_add = 0;   // cascades, begin_compute items, add_used pairs (check_kinds)
+    bool rec_on = false;             // the cascades record the nodes they only flag (the graph can flag)
+    uint64_t n_take = 0;             // detached handles the begin_compute steps may take (top of the free list)
+    // staging (pinned H, its device mirror D): the detached-handle list | inputs | scratch words | outputs | ids
+    std::vector<size_t> in_off;      // per step: handles, used, versions, flags (0: none)
+    std::vector<BatchStep> bs;
+    size_t in_bytes = 0, out_bytes = 0, scr_words = 0, scr_bytes = 0, ptop_word = 0, rcur_word = 0, res_off = 0, ids_off = 0;
+    uint64_t spec = 0;               // ids copied back with the results, on speculation
+    char *H = nullptr, *D = nullptr;
+    unsigned long long *scr = nullptr, *scr_h = nullptr;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> wave_ev;   // per-cascade timing, when asked for
+    uint32_t syncs = 0, from = 0;    // waits so far; the step a resumed launch starts at
+    const clk::time_point t0 = clk::now();
+    clk::time_point t_check, t_cap, t_stage, t_pack, t_enq, t_wait;
+
+    Batch(fgi_graph* g_, uint32_t n, const fgi_step* s) : g(g_), n_steps(n), steps(s), st(g_->stream) {}
+    const unsigned long long* counters(uint32_t k) const { return scr_h + 3 + kAccCount + 4 * (size_t)k; }
+    fgi_status check_kinds(), ensure_capacities(), lay_out(const uint32_t* out_ids, uint64_t cap), stage(), alloc_temps();
+    fgi_status launch(bool timed, const RecSink* sink), run(bool timed, uint32_t* applied);
+    void note_runs(uint32_t end);
+    fgi_status view_sync(), sub_moves(uint32_t end), unpack(uint32_t* out_ids, uint64_t cap, uint64_t* out_n);
+    void report(fgi_batch_stats* stats);
+};
+
 }  // namespace
 
-// Launches steps [from, n) of a batch; returns with the work queued (no synchronisation).
-static fgi_status batch_launch(fgi_graph* g, uint32_t from, uint32_t n_steps, const fgi_step* steps,
-                               std::vector<BatchStep>& bs, unsigned long long* scr, const uint32_t* take,
-                               uint64_t n_take, bool timed, std::vector<std::pair<hipEvent_t, hipEvent_t>>& wave_ev,
-                               const RecSink* sink) {
+// Launches steps [from, n_steps) of the batch; returns with the work queued (no synchronisation).
+fgi_status Batch::launch(bool timed, const RecSink* sink) {
     FGI_TRY(flush_vis(g));
-    hipStream_t st = g->stream;
+    const uint32_t* take = reinterpret_cast<const uint32_t*>(D);
     unsigned long long* abort = scr;
     unsigned long long* out_n = scr + 1;
     unsigned long long* cursor = scr + 2;
@@ -3101,8 +3185,7 @@ static fgi_status batch_launch(fgi_graph* g, uint32_t from, uint32_t n_steps, co
                 FGI_TRY(wave(n, b.roots, nullptr, b.cnt, b.cnt));   // displacement cascade (ComputedRegistry.cs:91-94)
                 touch(g);
                 note_words(g);
-                const InstallArgs ia{b.h,        b.ver,      b.flags,    b.cls,       take, cursor, g->n_slots, node,
-                                     g->row_off, g->row_len, g->row_cap, g->used_cnt, g->home, b.out32};
+                const InstallArgs ia = install_args(g, b.h, b.ver, b.flags, b.cls, take, cursor, b.out32);
                 hipLaunchKernelGGL(kb_bc_install, dim3(nblk(n)), dim3(256), 0, st, abort, n, ia);
                 break;
             }
@@ -3110,9 +3193,7 @@ static fgi_status batch_launch(fgi_graph* g, uint32_t from, uint32_t n_steps, co
                 FGI_TRY(fold(g));
                 note_words(g);
                 touch(g);
-                const AuArgs aa{b.h,        b.used,     g->n_slots, g->home,     node,        g->row_off,
-                                g->row_len, g->row_cap, g->used_cnt, g->pool_col, g->pool_tag, b.hash,
-                                b.hcap - 1, b.out32,    b.cand,     b.pend,      b.ovf,       b.cnt};
+                const AuArgs aa = au_args(g, b.h, b.used, b.out32, b.hash, b.hcap, b.cand, b.pend, b.ovf, b.cnt);
                 if (from == k && b.hcap == 0) {   // resumed after a pool growth: relocate and finish
                     hipLaunchKernelGGL(kb_au_relocate, dim3(grid), dim3(256), 0, st, abort, aa, g->pool_top_dev);
                     hipLaunchKernelGGL(kb_au_pending, dim3(grid), dim3(256), 0, st, abort, aa);
@@ -3133,22 +3214,15 @@ static fgi_status batch_launch(fgi_graph* g, uint32_t from, uint32_t n_steps, co
                                    b.out8, b.roots, b.cnt);
                 FGI_TRY(wave(n, b.roots, nullptr, b.cnt, b.cnt));   // Invalidate() of InvalidateOnSetOutput nodes (153-156)
                 break;
-            default:
-                break;
         }
     }
     FGI_HIP(g, hipGetLastError());
     return FGI_OK;
 }
 
-fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, uint32_t* out_ids, uint64_t cap,
-                         uint64_t* out_n, fgi_batch_stats* stats) {
-    if (!g || (n_steps && !steps)) return FGI_EINVAL;
-    if (coop_launch_mode()) FGI_TRY(coop_warm(g));   // once per graph, before the call's timed span
-    const auto t0 = std::chrono::steady_clock::now();
-    if (out_n) *out_n = 0;
-    uint64_t n_waves = 0, n_begin = 0, n_add = 0;
-    for (uint32_t k = 0; k < n_steps; ++k) {   // step kinds and pointers (the elements: while staging)
+// step kinds and pointers (the elements: while staging)
+fgi_status Batch::check_kinds() {
+    for (uint32_t k = 0; k < n_steps; ++k) {
         const fgi_step& sp = steps[k];
         if (sp.n && !sp.handles) return set_err(g, FGI_EINVAL, "step %u: no handles", k);
         switch (sp.kind) {
@@ -3169,81 +3243,61 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
                 return set_err(g, FGI_EINVAL, "step %u: unknown kind %u", k, sp.kind);
         }
     }
-    FGI_TRY(single_only(g, "fgi_run_batch"));
-    g->flg_last = -2;   // the batch's cascades report through fgi_last_batch_flagged (bflg_runs)
-    fanout_note(g, kCascBatch);
-    g->flg_drop.clear();
-    g->bflg_runs.clear();
-    g->bflg_step.clear();
-    g->bflg_set.clear();
-    g->bflg_read = false;
-    if (n_begin) g->flag_gate = true;
-    const bool rec_on = g->flag_gate;   // off: nothing is allocated, queued or launched differently
-    const auto t_check = std::chrono::steady_clock::now();
-    hipSetDevice(g->device);
-    hipStream_t st = g->stream;
-    // capacities, before anything is queued: the ids of every cascade, pool headroom for the rows
-    // the add_used steps may relocate (an add_used step that needs more resumes after a growth)
-    const uint64_t need_out = std::max<uint64_t>(1, n_waves) * g->n_handles;
-    if (g->bout_cap < need_out) {
-        dfree(g->bout);
-        g->bout_cap = 0;
-        FGI_TRY(dmalloc(g, &g->bout, need_out));
-        g->bout_cap = need_out;
-    }
+    return FGI_OK;
+}
+
+// capacities, before anything is queued: the ids of every cascade, pool headroom for the rows
+// the add_used steps may relocate (an add_used step that needs more resumes after a growth)
+fgi_status Batch::ensure_capacities() {
+    auto grow = [this](auto*& buf, uint64_t& have, uint64_t need) -> fgi_status {
+        if (have >= need) return FGI_OK;
+        dfree(buf);
+        have = 0;
+        FGI_TRY(dmalloc(g, &buf, need));
+        have = need;
+        return FGI_OK;
+    };
+    FGI_TRY(grow(g->bout, g->bout_cap, std::max<uint64_t>(1, n_waves) * g->n_handles));
     // the cascades' flag-only records: each of a node's two flag bits goes 0 -> 1 at most
     // once in its life and every record reports at least one such change, so a batch writes at most two per
     // node it ever holds: those of its handles and one more per begin_compute entry
-    const uint64_t need_rec = rec_on ? 2 * ((uint64_t)g->n_handles + n_begin) : 0;
-    if (g->brec_cap < need_rec) {
-        dfree(g->brec);
-        g->brec_cap = 0;
-        FGI_TRY(dmalloc(g, &g->brec, need_rec));
-        g->brec_cap = need_rec;
-    }
+    FGI_TRY(grow(g->brec, g->brec_cap, rec_on ? 2 * ((uint64_t)g->n_handles + n_begin) : 0));
     if (n_add) FGI_TRY(ensure_pool(g, g->pool_top + std::max<uint64_t>(1ull << 20, 4 * n_add)));
-    FGI_TRY(ensure_cstart(g, std::max<uint64_t>(g->pool_top, g->pool_cap)));
-    const auto t_cap = std::chrono::steady_clock::now();
-    // detached handles the begin_compute steps may take (top of the free list)
-    const uint64_t n_take = std::min<uint64_t>(n_begin, g->free_detached.size());
-    // staging: inputs (uploaded once) | the detached-handle list | outputs (downloaded once)
-    size_t in_bytes = stage_round(n_take * 4), out_bytes = 0;
-    std::vector<size_t> in_off(n_steps * 4, 0);
+    return ensure_cstart(g, std::max<uint64_t>(g->pool_top, g->pool_cap));
+}
+
+// The staging layout, and the pinned buffer and its device mirror grown to hold it: the detached-handle list
+// and the inputs (uploaded once), the scratch words, the outputs (downloaded once), the speculative ids.
+fgi_status Batch::lay_out(const uint32_t* out_ids, uint64_t cap) {
+    n_take = std::min<uint64_t>(n_begin, g->free_detached.size());
+    in_bytes = stage_round(n_take * 4);
+    in_off.assign(n_steps * 4, 0);
+    bs.resize(n_steps);
     for (uint32_t k = 0; k < n_steps; ++k) {
         const fgi_step& sp = steps[k];
         const size_t n = sp.n;
-        in_off[4 * k] = in_bytes;
-        in_bytes += stage_round(n * 4);
-        if (sp.kind == FGI_STEP_ADD_USED) {
-            in_off[4 * k + 1] = in_bytes;
-            in_bytes += stage_round(n * 4);
-        }
-        if (sp.kind == FGI_STEP_BEGIN_COMPUTE) {
-            in_off[4 * k + 2] = in_bytes;
-            in_bytes += stage_round(n * 8);
-        }
-        if (sp.flags && (sp.kind == FGI_STEP_BEGIN_COMPUTE || sp.kind == FGI_STEP_INVALIDATE)) {
-            in_off[4 * k + 3] = in_bytes;
-            in_bytes += stage_round(n);
-        }
-    }
-    std::vector<BatchStep> bs(n_steps);
-    for (uint32_t k = 0; k < n_steps; ++k) {
-        const fgi_step& sp = steps[k];
         bs[k].out_off = out_bytes;
-        if (sp.kind == FGI_STEP_BEGIN_COMPUTE || sp.kind == FGI_STEP_ADD_USED) out_bytes += stage_round(sp.n * 4);
-        if (sp.kind == FGI_STEP_SET_OUTPUT) out_bytes += stage_round(sp.n);
+        if (sp.kind == FGI_STEP_BEGIN_COMPUTE || sp.kind == FGI_STEP_ADD_USED) out_bytes += stage_round(n * 4);
+        if (sp.kind == FGI_STEP_SET_OUTPUT) out_bytes += stage_round(n);
+        auto place = [&](uint32_t which, size_t bytes) {
+            in_off[4 * k + which] = in_bytes;
+            in_bytes += stage_round(bytes);
+        };
+        place(0, n * 4);
+        if (sp.kind == FGI_STEP_ADD_USED) place(1, n * 4);
+        if (sp.kind == FGI_STEP_BEGIN_COMPUTE) place(2, n * 8);
+        if (sp.flags && (sp.kind == FGI_STEP_BEGIN_COMPUTE || sp.kind == FGI_STEP_INVALIDATE)) place(3, n);
     }
     // scratch words: abort, ids, detached taken, accumulators, 4 counters per step (the last one of a step
     // with a cascade: the record cursor at the cascade's end), the pool top, the record cursor
-    const size_t scr_words = 3 + kAccCount + 4 * (size_t)n_steps + 2;
-    const size_t scr_bytes = stage_round(scr_words * 8);
-    const size_t ptop_word = scr_words - 2;
-    const size_t rcur_word = scr_words - 1;
+    scr_words = 3 + kAccCount + 4 * (size_t)n_steps + 2;
+    scr_bytes = stage_round(scr_words * 8);
+    ptop_word = scr_words - 2;
+    rcur_word = scr_words - 1;
     // the ids are copied back with the results when they fit the previous batch's count (+25%)
-    const uint64_t spec = out_ids ? std::min<uint64_t>(cap, g->batch_ids_hint + g->batch_ids_hint / 4 + 4096) : 0;
-    const size_t res_off = in_bytes + scr_bytes;   // outputs follow the scratch words
-    const size_t ids_off = res_off + out_bytes;
+    spec = out_ids ? std::min<uint64_t>(cap, g->batch_ids_hint + g->batch_ids_hint / 4 + 4096) : 0;
+    res_off = in_bytes + scr_bytes;   // outputs follow the scratch words
+    ids_off = res_off + out_bytes;
     const size_t total = ids_off + stage_round(spec * 4);
     if (g->bst_cap < total) {
         if (g->bst_h) hipHostFree(g->bst_h);
@@ -3255,13 +3309,19 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
         FGI_TRY(dmalloc(g, &g->bst_d, c));
         g->bst_cap = c;
     }
-    char* H = g->bst_h;
-    char* D = g->bst_d;
-    // The single calls' argument checks, made while the inputs are staged (one pass over the caller's
-    // arrays): range and version checks as branch-free reductions beside the copies (they vectorise),
-    // then a slot-repeat test over the staged copy with a byte per slot (independent stores, no
-    // read-modify-write chain through one bitmap word). The first offender is searched for only on
-    // failure. Nothing has been queued yet, so a bad step applies nothing.
+    H = g->bst_h;
+    D = g->bst_d;
+    scr = reinterpret_cast<unsigned long long*>(D + in_bytes);
+    scr_h = reinterpret_cast<unsigned long long*>(H + in_bytes);
+    return FGI_OK;
+}
+
+// The single calls' argument checks, made while the inputs are staged (one pass over the caller's
+// arrays): range and version checks as branch-free reductions beside the copies (they vectorise),
+// then a slot-repeat test over the staged copy with a byte per slot (independent stores, no
+// read-modify-write chain through one bitmap word). The first offender is searched for only on
+// failure (check_begin_args). Nothing has been queued yet, so a bad step applies nothing. Then the upload.
+fgi_status Batch::stage() {
     for (uint32_t k = 0; k < n_steps; ++k) {
         const fgi_step& sp = steps[k];
         const uint32_t n = sp.n;
@@ -3279,8 +3339,7 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
                 hmax = std::max(hmax, x);
                 vbad |= (uint64_t)(v - 1 >= kVMask);   // version 0 or > kVMask
             }
-            std::vector<uint8_t>& seen = g->seen_slots;
-            if (seen.size() < g->ext_slots) seen.assign(g->ext_slots, 0);
+            std::vector<uint8_t>& seen = seen_scratch(g, g->ext_slots);
             uint32_t dup = 0;
             if (hmax < g->ext_slots && !vbad) {
                 for (uint32_t i = 0; i < n; ++i) {
@@ -3290,17 +3349,8 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
                 for (uint32_t i = 0; i < n; ++i) seen[hh[i]] = 0;
             }
             if (hmax >= g->ext_slots || vbad || dup) {
-                const char* why = "bad step";
-                uint32_t i = 0, bad = 0;
-                for (; i < n; ++i) {
-                    const uint32_t x = sp.handles[i];
-                    if (x >= g->ext_slots) { why = "slot out of range"; bad = x; break; }
-                    if (sp.version[i] == 0 || sp.version[i] > kVMask) { why = "bad version"; bad = i; break; }
-                    if (seen[x]) { why = "slot repeated in one step"; bad = x; break; }
-                    seen[x] = 1;
-                }
-                for (uint32_t j = 0; j < i; ++j) seen[sp.handles[j]] = 0;
-                return set_err(g, FGI_EINVAL, "step %u: %s (%u)", k, why, bad);
+                const BadBegin bad = check_begin_args(g, g->ext_slots, n, sp.handles, sp.version);
+                return set_err(g, FGI_EINVAL, "step %u: %s (%u)", k, bad.why ? bad.why : "bad step", bad.value);
             }
             bs[k].ver = reinterpret_cast<const uint64_t*>(D + in_off[4 * k + 2]);
         } else if (sp.kind == FGI_STEP_ADD_USED) {
@@ -3326,24 +3376,23 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
         }
     }
     if (n_take) std::memcpy(H, g->free_detached.data() + (g->free_detached.size() - n_take), n_take * 4);
-    const auto t_stage = std::chrono::steady_clock::now();
-    unsigned long long* scr = reinterpret_cast<unsigned long long*>(D + in_bytes);
-    unsigned long long* scr_h = reinterpret_cast<unsigned long long*>(H + in_bytes);
+    t_stage = clk::now();
+    // the scratch words zeroed, then one upload of them and every input; the steps' handles as labels
     std::memset(scr_h, 0, scr_words * 8);
-    hipEvent_t b0 = g->ev_w0, b1 = g->ev_w1;
-    // FGI_BATCH_TIMES=1: the call's host phases on stderr (staging, enqueue, wait, unpacking; us)
-    static const bool times = getenv("FGI_BATCH_TIMES") != nullptr;
-    using clk = std::chrono::steady_clock;
-    const clk::time_point t_pack = times ? clk::now() : t0;
-    clk::time_point t_enq = t_pack, t_wait = t_pack;
-    FGI_HIP(g, hipEventRecord(b0, st));
-    FGI_HIP(g, hipMemcpyAsync(D, H, in_bytes + scr_words * 8, hipMemcpyHostToDevice, st));   // one upload
-    for (uint32_t k = 0; k < n_steps && g->lbl_K; ++k) {   // the steps' handles as labels
+    t_pack = batch_times ? clk::now() : t0;
+    t_enq = t_wait = t_pack;
+    FGI_HIP(g, hipEventRecord(g->ev_w0, st));   // the batch's span on the device: ev_w0 .. ev_w1 (report)
+    FGI_HIP(g, hipMemcpyAsync(D, H, in_bytes + scr_words * 8, hipMemcpyHostToDevice, st));
+    for (uint32_t k = 0; k < n_steps && g->lbl_K; ++k) {
         const fgi_step& sp = steps[k];
         FGI_TRY(labels_map_in(g, reinterpret_cast<uint32_t*>(D + in_off[4 * k]), sp.n));
         if (sp.kind == FGI_STEP_ADD_USED) FGI_TRY(labels_map_in(g, reinterpret_cast<uint32_t*>(D + in_off[4 * k + 1]), sp.n));
     }
-    // per-step device temporaries
+    return FGI_OK;
+}
+
+// per-step device temporaries; the outputs are written straight into the staging's device mirror
+fgi_status Batch::alloc_temps() {
     for (uint32_t k = 0; k < n_steps; ++k) {
         const fgi_step& sp = steps[k];
         BatchStep& b = bs[k];
@@ -3370,88 +3419,89 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
                 b.out8 = reinterpret_cast<uint8_t*>(D + res_off + b.out_off);
                 FGI_TRY(tmalloc(g, b.tmp[1], &b.roots, n));
                 break;
-            default:
-                break;
         }
     }
-    const uint32_t* take = reinterpret_cast<const uint32_t*>(D);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> wave_ev;
-    const bool timed = stats && g->opt_level_timing;
-    uint32_t syncs = 0, from = 0;
-    g->last_wave_n = 0;
+    return FGI_OK;
+}
+
+// The cascades of steps [0, end) ran to their end: their record runs, from the words each left in its
+// step's counters (RecSink; a resumed batch keeps the cursor and the words of the cascades that ran
+// before). A cascade that found no roots left no word and has no records. The records stay on the
+// device until fgi_last_batch_flagged asks for them.
+void Batch::note_runs(uint32_t end) {
+    for (uint32_t k = 0; rec_on && k < end; ++k) {
+        const fgi_step& sp = steps[k];
+        const unsigned long long* cnt = counters(k);
+        if (!sp.n || sp.kind == FGI_STEP_ADD_USED || cnt[3] == 0) continue;
+        fgi_graph::BatchRun r;
+        r.step = k;
+        r.lo = cnt[3] - 1 - cnt[2];
+        r.hi = scr_h[rcur_word];
+        if (!g->bflg_runs.empty()) g->bflg_runs.back().hi = r.lo;
+        if (sp.kind == FGI_STEP_BEGIN_COMPUTE) {
+            r.drop_off = in_off[4 * k];
+            r.n_drop = sp.n;
+        }
+        g->bflg_runs.push_back(r);
+    }
+}
+
+// The state view after a batch: every handle a step may have changed, refreshed once from the post-batch
+// words (a slot one step's cascade invalidated and a later step began again ends Computing): the steps'
+// own handles, the detached handles handed out, the cascades' invalidated ids and their flagged records.
+// Queued behind the batch's own wait, so one more wait (fgi_view_stats.extra_waits).
+fgi_status Batch::view_sync() {
+    if (!view_on(g)) return FGI_OK;
+    for (uint32_t k = 0; k < n_steps; ++k) {
+        FGI_TRY(view_refresh(g, kViewLabels, bs[k].h, steps[k].n));
+        if (steps[k].kind == FGI_STEP_BEGIN_COMPUTE) FGI_TRY(view_refresh(g, kViewLabels, bs[k].out32, steps[k].n));
+    }
+    FGI_TRY(view_refresh(g, kViewHandles, g->bout, std::min<uint64_t>(scr_h[1], g->bout_cap)));
+    if (rec_on) FGI_TRY(view_refresh(g, kViewRecords, g->brec, std::min<uint64_t>(scr_h[rcur_word], g->brec_cap)));
+    return view_commit(g);
+}
+
+// Subscriptions follow the node (fanout.hip): behind the batch, the BEGIN_COMPUTE steps [0, end) move a
+// displaced node's entries to its detached handle, in step order. Nobody subscribes mid-batch, so only the
+// first such step on a slot can find entries there: the nodes later steps displace were made by the batch.
+fgi_status Batch::sub_moves(uint32_t end) {
+    if (!fanout_live(g) || !n_begin) return FGI_OK;
+    std::vector<uint32_t> src, dst;
+    std::vector<uint8_t>& seen = seen_scratch(g, g->ext_slots);   // cleared again below
+    for (uint32_t k = 0; k < end; ++k) {
+        const fgi_step& sp = steps[k];
+        if (sp.kind != FGI_STEP_BEGIN_COMPUTE) continue;
+        const uint32_t* o = reinterpret_cast<const uint32_t*>(H + res_off + bs[k].out_off);
+        for (uint32_t i = 0; i < sp.n; ++i) {
+            if (seen[sp.handles[i]]) continue;
+            seen[sp.handles[i]] = 1;
+            src.push_back(sp.handles[i]);
+            dst.push_back(o[i] == FGI_NONE ? FGI_NONE : o[i] - g->lbl_K);
+        }
+    }
+    for (const uint32_t x : src) seen[x] = 0;
+    return fanout_move(g, (uint32_t)src.size(), src.data(), dst.data());
+}
+
+// Launch the steps and wait, once: the counters, the pool top and every step's output come back in one copy,
+// the ids (as many as the previous batch had, +25%) in a second. An add_used step that outgrew the pool grows
+// it and resumes. *applied < n_steps: that step found no detached handle left, the steps before it are applied.
+fgi_status Batch::run(bool timed, uint32_t* applied) {
     RecSink sink;
     sink.rec = g->brec;
     sink.cur = scr + rcur_word;
     sink.cap = g->brec_cap;
     sink.l2s = g->l2s;
     sink.K = g->lbl_K;
-    // The cascades of steps [0, end) ran to their end: their record runs, from the words each left in its
-    // step's counters (RecSink; a resumed batch keeps the cursor and the words of the cascades that ran
-    // before). A cascade that found no roots left no word and has no records. The records stay on the
-    // device until fgi_last_batch_flagged asks for them.
-    auto note_runs = [&](uint32_t end) {
-        for (uint32_t k = 0; rec_on && k < end; ++k) {
-            const fgi_step& sp = steps[k];
-            const unsigned long long* cnt = scr_h + 3 + kAccCount + 4 * (size_t)k;
-            if (!sp.n || sp.kind == FGI_STEP_ADD_USED || cnt[3] == 0) continue;
-            fgi_graph::BatchRun r;
-            r.step = k;
-            r.lo = cnt[3] - 1 - cnt[2];
-            r.hi = scr_h[rcur_word];
-            if (!g->bflg_runs.empty()) g->bflg_runs.back().hi = r.lo;
-            if (sp.kind == FGI_STEP_BEGIN_COMPUTE) {
-                r.drop_off = in_off[4 * k];
-                r.n_drop = sp.n;
-            }
-            g->bflg_runs.push_back(r);
-        }
-    };
-    // The state view after a batch: every handle a step may have changed, refreshed once from the post-batch
-    // words (a slot one step's cascade invalidated and a later step began again ends Computing): the steps'
-    // own handles, the detached handles handed out, the cascades' invalidated ids and their flagged records.
-    // Queued behind the batch's own wait, so one more wait (fgi_view_stats.extra_waits).
-    auto view_sync = [&]() -> fgi_status {
-        if (!view_on(g)) return FGI_OK;
-        for (uint32_t k = 0; k < n_steps; ++k) {
-            FGI_TRY(view_refresh(g, kViewLabels, bs[k].h, steps[k].n));
-            if (steps[k].kind == FGI_STEP_BEGIN_COMPUTE) FGI_TRY(view_refresh(g, kViewLabels, bs[k].out32, steps[k].n));
-        }
-        FGI_TRY(view_refresh(g, kViewHandles, g->bout, std::min<uint64_t>(scr_h[1], g->bout_cap)));
-        if (rec_on) FGI_TRY(view_refresh(g, kViewRecords, g->brec, std::min<uint64_t>(scr_h[rcur_word], g->brec_cap)));
-        return view_commit(g);
-    };
-    // Subscriptions follow the node (fanout.hip): behind the batch, the BEGIN_COMPUTE steps [0, end) move a
-    // displaced node's entries to its detached handle, in step order. Nobody subscribes mid-batch, so only the
-    // first such step on a slot can find entries there: the nodes later steps displace were made by the batch.
-    auto sub_moves = [&](uint32_t end) -> fgi_status {
-        if (!fanout_live(g) || !n_begin) return FGI_OK;
-        std::vector<uint32_t> from, to;
-        std::vector<uint8_t>& seen = g->seen_slots;   // sized by the staging checks above; cleared again below
-        for (uint32_t k = 0; k < end; ++k) {
-            const fgi_step& sp = steps[k];
-            if (sp.kind != FGI_STEP_BEGIN_COMPUTE) continue;
-            const uint32_t* o = reinterpret_cast<const uint32_t*>(H + res_off + bs[k].out_off);
-            for (uint32_t i = 0; i < sp.n; ++i) {
-                if (seen[sp.handles[i]]) continue;
-                seen[sp.handles[i]] = 1;
-                from.push_back(sp.handles[i]);
-                to.push_back(o[i] == FGI_NONE ? FGI_NONE : o[i] - g->lbl_K);
-            }
-        }
-        for (const uint32_t x : from) seen[x] = 0;
-        return fanout_move(g, (uint32_t)from.size(), from.data(), to.data());
-    };
-    view_begin(g);
+    const hipEvent_t b1 = g->ev_w1;
+    *applied = n_steps;
     while (true) {
-        fgi_status s = batch_launch(g, from, n_steps, steps, bs, scr, take, n_take, timed, wave_ev, rec_on ? &sink : nullptr);
-        if (s != FGI_OK) return s;
-        // results: the counters, the pool top and every step's output in one copy, the ids (as
-        // many as the previous batch had, +25%) in a second, then one wait
+        FGI_TRY(launch(timed, rec_on ? &sink : nullptr));
         hipLaunchKernelGGL(kb_finish, dim3(1), dim3(64), 0, st, g->pool_top_dev, scr + ptop_word);
         FGI_HIP(g, hipMemcpyAsync(H + in_bytes, D + in_bytes, scr_bytes + out_bytes, hipMemcpyDeviceToHost, st));
         if (spec) FGI_HIP(g, hipMemcpyAsync(H + ids_off, g->bout, spec * 4, hipMemcpyDeviceToHost, st));
         FGI_HIP(g, hipEventRecord(b1, st));
-        if (times) t_enq = clk::now();
+        if (batch_times) t_enq = clk::now();
 #if FGI_SPIN_WAIT
         // the host spins on a published sequence word behind the copies (wave.hip publish_wait) instead
         // of a stream synchronisation; b1 is complete by then, so its wait returns at once
@@ -3460,7 +3510,7 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
 #else
         FGI_HIP(g, hipStreamSynchronize(st));
 #endif
-        if (times) t_wait = clk::now();
+        if (batch_times) t_wait = clk::now();
         ++syncs;
         g->pool_top = scr_h[ptop_word];
         const unsigned long long ab = scr_h[0];
@@ -3482,7 +3532,7 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
         if (!ab) break;
         const uint32_t k = (uint32_t)(ab & 0xFFFFFFFFull) - 1;
         if ((ab >> 32) == kAbortPool) {   // grow the pool, then finish step k and run the rest
-            const unsigned long long need = bs[k].cnt ? scr_h[3 + kAccCount + 4 * k + 3] : 0;
+            const unsigned long long need = bs[k].cnt ? counters(k)[3] : 0;
             FGI_TRY(ensure_pool(g, g->pool_top + need + std::max<uint64_t>(1ull << 20, 4 * n_add)));
             scr_h[0] = 0;
             FGI_HIP(g, hipMemcpyAsync(scr, scr_h, 8, hipMemcpyHostToDevice, st));
@@ -3490,18 +3540,15 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
             from = k;
             continue;
         }
-        // out of detached handles at step k: steps before it are applied
-        note_runs(k);
-        g->free_detached.resize(g->free_detached.size() - (size_t)scr_h[2]);
-        FGI_TRY(view_sync());   // the steps before k are applied
-        FGI_TRY(sub_moves(k));
-        return set_err(g, FGI_ECAPACITY, "step %u: out of detached handles (%zu free)", k, g->free_detached.size());
+        *applied = k;   // out of detached handles at step k
+        break;
     }
-    // host bookkeeping: the cascades' record runs, the detached handles taken, the per-step outputs
-    note_runs(n_steps);
-    g->free_detached.resize(g->free_detached.size() - (size_t)scr_h[2]);
-    FGI_TRY(view_sync());
-    FGI_TRY(sub_moves(n_steps));
+    return FGI_OK;
+}
+
+// The per-step outputs from the staging into the caller's arrays, then the cascades' ids: from the staging when
+// the speculative copy held them all (and the batch did not resume), else a second copy and wait.
+fgi_status Batch::unpack(uint32_t* out_ids, uint64_t cap, uint64_t* out_n) {
     for (uint32_t k = 0; k < n_steps; ++k) {
         const fgi_step& sp = steps[k];
         if (!sp.out || !sp.n) continue;
@@ -3515,25 +3562,24 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
         }
     }
     g->stale_est += scr_h[3 + 3] + scr_h[3 + 4];   // the cascades' E_trav + E_match (fgi_prune_step)
-#if FGI_PROBE
-    if (getenv("FGI_TRACE")) print_coop_probe();
-#endif
     const uint64_t n_ids = scr_h[1];
     if (out_n) *out_n = n_ids;
     g->batch_ids_hint = n_ids;
-    fgi_status ret = FGI_OK;
-    if (out_ids) {
-        if (n_ids > cap) {
-            ret = FGI_ECAPACITY;
-        } else if (n_ids <= spec && from == 0) {
-            std::memcpy(out_ids, H + ids_off, n_ids * 4);
-        } else if (n_ids) {
-            FGI_HIP(g, hipMemcpyAsync(out_ids, g->bout, n_ids * 4, hipMemcpyDeviceToHost, st));
-            FGI_HIP(g, hipStreamSynchronize(st));
-            ++syncs;
-        }
+    if (!out_ids) return FGI_OK;
+    if (n_ids > cap) return FGI_ECAPACITY;   // the batch is applied
+    if (n_ids <= spec && from == 0) {
+        std::memcpy(out_ids, H + ids_off, n_ids * 4);
+    } else if (n_ids) {
+        FGI_HIP(g, hipMemcpyAsync(out_ids, g->bout, n_ids * 4, hipMemcpyDeviceToHost, st));
+        FGI_HIP(g, hipStreamSynchronize(st));
+        ++syncs;
     }
-    if (times) {
+    return FGI_OK;
+}
+
+// the FGI_BATCH_TIMES line and the caller's statistics
+void Batch::report(fgi_batch_stats* stats) {
+    if (batch_times) {
         const clk::time_point t_end = clk::now();
         auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
         fprintf(stderr, "[fgi] batch check %.1f cap %.1f stage %.1f pack %.1f enqueue %.1f wait %.1f unpack %.1f total %.1f us (%u steps)\n",
@@ -3549,12 +3595,56 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
         stats->e_match += acc[4];
         stats->n_flagged += acc[5];
         float ms = 0;
-        if (hipEventElapsedTime(&ms, b0, b1) == hipSuccess) stats->kernel_ms += ms;
+        if (hipEventElapsedTime(&ms, g->ev_w0, g->ev_w1) == hipSuccess) stats->kernel_ms += ms;
         for (auto& e : wave_ev)
             if (hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) stats->wave_ms += ms;
         stats->host_syncs += syncs;
-        stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->total_ms += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
     }
+}
+
+fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, uint32_t* out_ids, uint64_t cap,
+                         uint64_t* out_n, fgi_batch_stats* stats) {
+    if (!g || (n_steps && !steps)) return FGI_EINVAL;
+    if (coop_launch_mode()) FGI_TRY(coop_warm(g));   // once per graph, before the call's timed span
+    Batch b(g, n_steps, steps);
+    if (out_n) *out_n = 0;
+    FGI_TRY(b.check_kinds());
+    FGI_TRY(single_only(g, "fgi_run_batch"));
+    g->flg_last = -2;   // the batch's cascades report through fgi_last_batch_flagged (bflg_runs)
+    fanout_note(g, kCascBatch);
+    g->flg_drop.clear();
+    g->bflg_runs.clear();
+    g->bflg_step.clear();
+    g->bflg_set.clear();
+    g->bflg_read = false;
+    if (b.n_begin) g->flag_gate = true;
+    b.rec_on = g->flag_gate;   // off: nothing is allocated, queued or launched differently
+    b.t_check = Batch::clk::now();
+    hipSetDevice(g->device);
+    FGI_TRY(b.ensure_capacities());
+    b.t_cap = Batch::clk::now();
+    FGI_TRY(b.lay_out(out_ids, cap));
+    FGI_TRY(b.stage());
+    FGI_TRY(b.alloc_temps());
+    g->last_wave_n = 0;
+    view_begin(g);
+    uint32_t applied = 0;
+    FGI_TRY(b.run(stats && g->opt_level_timing, &applied));
+    // host bookkeeping for the steps that ran: the cascades' record runs, the detached handles taken, the
+    // state view, the subscriptions of displaced nodes
+    b.note_runs(applied);
+    g->free_detached.resize(g->free_detached.size() - (size_t)b.scr_h[2]);
+    FGI_TRY(b.view_sync());
+    FGI_TRY(b.sub_moves(applied));
+    if (applied < n_steps)
+        return set_err(g, FGI_ECAPACITY, "step %u: out of detached handles (%zu free)", applied, g->free_detached.size());
+#if FGI_PROBE
+    if (getenv("FGI_TRACE")) print_coop_probe();
+#endif
+    const fgi_status ret = b.unpack(out_ids, cap, out_n);
+    if (ret != FGI_OK && ret != FGI_ECAPACITY) return ret;
+    b.report(stats);
     return ret;
 }
 
@@ -3590,17 +3680,7 @@ fgi_status fgi_last_batch_flagged(fgi_graph* g, uint32_t* out_step, uint32_t* ou
         }
         g->bflg_read = true;
     }
-    const uint64_t n = g->bflg_set.size();
-    if (out_n) *out_n = n;
-    if (!out_ids) return FGI_OK;
-    if (n > cap) return set_err(g, FGI_ECAPACITY, "the batch's flagged sets hold %llu handles, the buffer %llu",
-                                (unsigned long long)n, (unsigned long long)cap);
-    for (uint64_t i = 0; i < n; ++i) {
-        out_ids[i] = (uint32_t)(g->bflg_set[i] >> 32);
-        if (out_step) out_step[i] = g->bflg_step[i];
-        if (out_flags) out_flags[i] = (uint32_t)g->bflg_set[i];
-    }
-    return FGI_OK;
+    return copy_step_flagged(g, g->bflg_set, g->bflg_step, out_step, out_ids, out_flags, cap, out_n);
 }
 
 // PruneUsedBy over the rows of handles [lo, hi) in place (queued, no synchronisation): the
@@ -3864,22 +3944,32 @@ fgi_status part_take_ids(fgi_graph* g, const PartView& pv, std::vector<uint32_t>
     return FGI_OK;
 }
 
-fgi_status part_check_slots(fgi_graph* g, const PartView& pv, uint32_t n, const uint32_t* slot, bool distinct) {
+fgi_status part_check_slots(fgi_graph* g, const PartView& pv, uint32_t n, const uint32_t* slot) {
     for (uint32_t i = 0; i < n; ++i)
         if (slot[i] >= pv.n_global) return set_err(g, FGI_EINVAL, "slot %u out of range", slot[i]);
-    if (distinct && n > 1) {
-        std::vector<uint32_t> c(slot, slot + n);
-        std::sort(c.begin(), c.end());
-        for (uint32_t i = 1; i < n; ++i)
-            if (c[i] == c[i - 1]) return set_err(g, FGI_EINVAL, "slot repeated in one batch (%u)", c[i]);
-    }
     return FGI_OK;
 }
 
-// a cascade from host root slots (global ids; each rank starts the ones it owns), on every rank
+// One cascade of a partitioned mutation from device roots (global ids), on every rank; its ids into *ids.
+fgi_status part_cascade_global(fgi_graph* g, const PartView& pv, uint32_t n_roots, const uint32_t* roots_dev,
+                               const uint8_t* imm_dev, fgi_wave_stats* stats, std::vector<uint32_t>* ids) {
+    g->last_wave_n = 0;
+    part_out_mark(g, kPoutOther);
+    FGI_TRY(run_part_wave(g, n_roots, roots_dev, imm_dev, stats));
+    return part_take_ids(g, pv, ids);
+}
+
+// the same from this rank's own roots, local handles on the device (made global in place)
+fgi_status part_cascade(fgi_graph* g, const PartView& pv, uint32_t n_roots, uint32_t* roots_local_dev, fgi_wave_stats* stats,
+                        std::vector<uint32_t>* ids) {
+    if (n_roots)
+        hipLaunchKernelGGL(k_add_base, dim3(nblk(n_roots)), dim3(256), 0, g->stream, n_roots, roots_local_dev, pv.base);
+    return part_cascade_global(g, pv, n_roots, roots_local_dev, nullptr, stats, ids);
+}
+
+// a cascade from host root slots (global ids), on every rank
 fgi_status part_wave_host(fgi_graph* g, const PartView& pv, uint32_t n, const uint32_t* slots, const uint8_t* imm,
                           fgi_wave_stats* stats, std::vector<uint32_t>* ids) {
-    (void)pv;
     Tmp tr, ti;
     uint32_t* dr = nullptr;
     uint8_t* di = nullptr;
@@ -3891,10 +3981,7 @@ fgi_status part_wave_host(fgi_graph* g, const PartView& pv, uint32_t n, const ui
             FGI_TRY(h2d(g, di, imm, n));
         }
     }
-    g->last_wave_n = 0;
-    part_out_mark(g, kPoutOther);   // a batch's step: its ids leave through the batch's out_ids
-    FGI_TRY(run_part_wave(g, n, dr, di, stats));
-    return part_take_ids(g, pv, ids);
+    return part_cascade_global(g, pv, n, dr, di, stats, ids);   // a batch's step: its ids leave through the batch's out_ids
 }
 
 // ComputeMethodFunctionBase.Compute + ComputedRegistry.Register with displacement (as
@@ -3906,9 +3993,8 @@ fgi_status part_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, co
     PartView pv;
     FGI_TRY(part_check(g, &pv, "fgi_part_begin_compute"));
     if (n && (!slot || !version)) return FGI_EINVAL;
-    FGI_TRY(part_check_slots(g, pv, n, slot, true));
-    for (uint32_t i = 0; i < n; ++i)
-        if (version[i] == 0 || version[i] > kVMask) return set_err(g, FGI_EINVAL, "bad version (%u)", i);
+    const BadBegin bad = check_begin_args(g, pv.n_global, n, slot, version);
+    if (bad.why) return set_err(g, FGI_EINVAL, "%s (%u)", bad.why, bad.value);
     hipSetDevice(g->device);
     hipStream_t st = g->stream;
     std::vector<uint32_t> li, ls;
@@ -3923,7 +4009,7 @@ fgi_status part_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, co
         }
     const uint32_t m = (uint32_t)li.size();
     Tmp ts, tv, td, tc, tr, to, tf, tflag, tall, tallv;
-    uint32_t *ds = nullptr, *droots = nullptr, *dout = nullptr, *dfree_h = nullptr, *dflag = nullptr;
+    uint32_t *ds = nullptr, *droots = nullptr, *dout = nullptr, *dflag = nullptr;
     uint64_t* dv = nullptr;
     uint8_t *dd = nullptr, *dcls = nullptr;
     FGI_TRY(fold(g));
@@ -3967,11 +4053,8 @@ fgi_status part_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, co
         FGI_TRY(part_kill_used(g, std::move(det)));
     }
     // the displacement cascade (ComputedRegistry.cs:91-94) on every rank, then versions and installs
-    if (cnt[0]) hipLaunchKernelGGL(k_add_base, dim3(nblk(cnt[0])), dim3(256), 0, st, (uint32_t)cnt[0], droots, pv.base);
-    g->last_wave_n = 0;
     g->flag_gate = true;   // Computing nodes from here on (flagged sets), on every rank alike
-    part_out_mark(g, kPoutOther);
-    FGI_TRY(run_part_wave(g, (uint32_t)cnt[0], droots, nullptr, stats));
+    FGI_TRY(part_cascade(g, pv, (uint32_t)cnt[0], droots, stats, ids));
     // the call's slots hold new nodes when it returns: a node the displacement cascade flagged under one of
     // them is not in the cascade's set (fgi_begin_compute's rule); kept as the host numbers the slots
     if (!g->pflg_runs.empty()) {
@@ -3979,7 +4062,6 @@ fgi_status part_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, co
         for (uint32_t j = 0; j < m; ++j) drop.push_back(part_slot_of(g, ls[j] + pv.base));
         std::sort(drop.begin(), drop.end());
     }
-    FGI_TRY(part_take_ids(g, pv, ids));
     if (n) {
         uint32_t* as = nullptr;
         uint64_t* av = nullptr;
@@ -3991,18 +4073,9 @@ fgi_status part_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, co
     }
     std::vector<uint32_t> od(m, FGI_NONE);
     if (m) {
-        std::vector<uint32_t> take(g->free_detached.end() - (ptrdiff_t)cnt[1], g->free_detached.end());
-        FGI_TRY(tmalloc(g, tf, &dfree_h, take.size() + 1));
-        FGI_TRY(h2d(g, dfree_h, take.data(), take.size()));
-        FGI_TRY(fold(g));   // the displacement cascade's visits
-        FGI_HIP(g, hipMemsetAsync(g->misc_dev + 2, 0, sizeof(unsigned long long), st));
-        const InstallArgs ia{ds,         dv,          dd,        dcls,      dfree_h, g->misc_dev + 2, g->n_slots,
-                             reinterpret_cast<unsigned long long*>(g->node), g->row_off, g->row_len, g->row_cap,
-                             g->used_cnt, g->home, dout};
-        hipLaunchKernelGGL(k_bc_install, dim3(nblk(m)), dim3(256), 0, st, m, ia);
-        FGI_HIP(g, hipGetLastError());
+        FGI_TRY(install_nodes(g, m, cnt[1], ds, dv, dd, dcls, dout, tf));
         FGI_TRY(d2h(g, od.data(), dout, m));
-        g->free_detached.resize(g->free_detached.size() - take.size());
+        g->free_detached.resize(g->free_detached.size() - (size_t)cnt[1]);
         if (view_on(g)) {   // the owned slots' new nodes and the detached handles handed out (the cascade's share is in)
             view_begin(g);
             FGI_TRY(view_refresh(g, kViewLabels, ds, m));
@@ -4035,8 +4108,8 @@ fgi_status part_add_used(fgi_graph* g, uint32_t n, const uint32_t* dep, const ui
     PartView pv;
     FGI_TRY(part_check(g, &pv, "fgi_part_add_used"));
     if (n && (!dep || !used)) return FGI_EINVAL;
-    FGI_TRY(part_check_slots(g, pv, n, dep, false));
-    FGI_TRY(part_check_slots(g, pv, n, used, false));
+    FGI_TRY(part_check_slots(g, pv, n, dep));
+    FGI_TRY(part_check_slots(g, pv, n, used));
     if (n == 0) return FGI_OK;
     hipSetDevice(g->device);
     hipStream_t st = g->stream;
@@ -4071,29 +4144,10 @@ fgi_status part_add_used(fgi_graph* g, uint32_t n, const uint32_t* dep, const ui
     hipLaunchKernelGGL(k_pau_classify, dim3(nblk(n)), dim3(256), 0, st, n, pa);
     unsigned long long nc = 0;
     FGI_TRY(d2h(g, &nc, g->misc_dev, 1));
-    if (nc) {
-        touch(g);
-        const AuArgs aa{nullptr,     nullptr,    g->n_slots,  g->home,     node,        g->row_off,
-                        g->row_len,  g->row_cap, nullptr,     g->pool_col, g->pool_tag, dhash,
-                        hcap - 1,    nullptr,    dcand,       dpend,       dovf,        g->misc_dev};
-        hipLaunchKernelGGL(k_au_reserve, dim3(nblk(nc)), dim3(256), 0, st, (uint64_t)nc, aa);
-        unsigned long long c2[2];
-        FGI_TRY(d2h(g, c2, g->misc_dev + 1, 2));
-        if (c2[1]) {   // rows that outgrew their capacity: relocated to the pool top
-            hipLaunchKernelGGL(k_au_size, dim3(nblk(c2[1])), dim3(256), 0, st, (uint64_t)c2[1], dovf, g->row_len,
-                               g->misc_dev + 3);
-            unsigned long long need = 0;
-            FGI_TRY(d2h(g, &need, g->misc_dev + 3, 1));
-            FGI_TRY(ensure_pool(g, g->pool_top + need));
-            FGI_HIP(g, hipMemcpyAsync(g->pool_top_dev, &g->pool_top, sizeof(uint64_t), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_au_relocate, dim3(nblk(c2[1] * 64)), dim3(256), 0, st, (uint64_t)c2[1], dovf,
-                               g->row_off, g->row_len, g->row_cap, g->pool_col, g->pool_tag, g->pool_top_dev);
-            hipLaunchKernelGGL(k_au_pending, dim3(nblk(nc)), dim3(256), 0, st, (uint64_t)nc, dcand, dpend, g->row_off,
-                               g->pool_col, g->pool_tag);
-            g->pool_top += need;
-            FGI_TRY(ensure_cstart(g, g->pool_top));
-        }
-    }
+    // the rows' owner appends; the dependant's owner counts the new dependency (k_pau_apply), so no used_cnt
+    AuArgs aa = au_args(g, nullptr, nullptr, nullptr, dhash, hcap, dcand, dpend, dovf, g->misc_dev);
+    aa.used_cnt = nullptr;
+    FGI_TRY(append_candidates(g, nc, aa));
     FGI_TRY(part_allreduce_u32(g, dres, n));
     FGI_HIP(g, hipMemsetAsync(g->misc_dev + 5, 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_pau_apply, dim3(nblk(n)), dim3(256), 0, st, n, ddep, duse, pv.base, pv.n_local, dres, node,
@@ -4127,7 +4181,7 @@ fgi_status part_set_output(fgi_graph* g, uint32_t n, const uint32_t* slot, uint8
     PartView pv;
     FGI_TRY(part_check(g, &pv, "fgi_part_set_output"));
     if (n && !slot) return FGI_EINVAL;
-    FGI_TRY(part_check_slots(g, pv, n, slot, false));
+    FGI_TRY(part_check_slots(g, pv, n, slot));
     hipSetDevice(g->device);
     hipStream_t st = g->stream;
     std::vector<uint32_t> li, lh;
@@ -4155,11 +4209,7 @@ fgi_status part_set_output(fgi_graph* g, uint32_t n, const uint32_t* slot, uint8
     }
     unsigned long long nr = 0;
     FGI_TRY(d2h(g, &nr, g->misc_dev, 1));
-    if (nr) hipLaunchKernelGGL(k_add_base, dim3(nblk(nr)), dim3(256), 0, st, (uint32_t)nr, droots, pv.base);
-    g->last_wave_n = 0;
-    part_out_mark(g, kPoutOther);
-    FGI_TRY(run_part_wave(g, (uint32_t)nr, droots, nullptr, stats));   // Invalidate() (Computed.cs:153-156)
-    FGI_TRY(part_take_ids(g, pv, ids));
+    FGI_TRY(part_cascade(g, pv, (uint32_t)nr, droots, stats, ids));   // Invalidate() (Computed.cs:153-156)
     if (view_on(g) && m) {   // the owned items' new states (Consistent, or what the cascade left)
         view_begin(g);
         FGI_TRY(view_refresh(g, kViewLabels, dh, m));
@@ -4196,20 +4246,16 @@ fgi_status part_invalidate_all(fgi_graph* g, fgi_wave_stats* stats, std::vector<
                        reinterpret_cast<const unsigned long long*>(g->node), roots, g->misc_dev);
     unsigned long long nr = 0;
     FGI_TRY(d2h(g, &nr, g->misc_dev, 1));
-    if (nr) hipLaunchKernelGGL(k_add_base, dim3(nblk(nr)), dim3(256), 0, st, (uint32_t)nr, roots, pv.base);
-    g->last_wave_n = 0;
-    part_out_mark(g, kPoutOther);   // until the wave stands
-    FGI_TRY(run_part_wave(g, (uint32_t)nr, roots, nullptr, stats));
-    part_out_mark(g, kPoutWave);    // one wave: fgi_part_last_wave_ids / _bits serve it too
-    return part_take_ids(g, pv, ids);
+    FGI_TRY(part_cascade(g, pv, (uint32_t)nr, roots, stats, ids));
+    part_out_mark(g, kPoutWave);   // one wave: fgi_part_last_wave_ids / _bits serve it too
+    return FGI_OK;
 }
 
-fgi_status part_copy_ids(fgi_graph* g, const std::vector<uint32_t>& ids, uint32_t* out_ids, uint64_t cap, uint64_t* out_n) {
+fgi_status part_copy_ids(const std::vector<uint32_t>& ids, uint32_t* out_ids, uint64_t cap, uint64_t* out_n) {
     if (out_n) *out_n = ids.size();
     if (!out_ids) return FGI_OK;
     if (ids.size() > cap) return FGI_ECAPACITY;
     std::memcpy(out_ids, ids.data(), ids.size() * 4);
-    (void)g;
     return FGI_OK;
 }
 
@@ -4222,7 +4268,7 @@ fgi_status fgi_part_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot
     std::vector<uint32_t> ids, ms;
     slot = part_codes_in(g, n, slot, ms);   // partition codes; outputs are slots again
     FGI_TRY(part_begin_compute(g, n, slot, version, has_delay, out_detached, stats, &ids));
-    return part_copy_ids(g, ids, out_ids, cap, out_n);
+    return part_copy_ids(ids, out_ids, cap, out_n);
 }
 
 fgi_status fgi_part_add_used(fgi_graph* g, uint32_t n, const uint32_t* dependant, const uint32_t* used,
@@ -4238,7 +4284,7 @@ fgi_status fgi_part_set_output(fgi_graph* g, uint32_t n, const uint32_t* slot, u
     std::vector<uint32_t> ids, ms;
     slot = part_codes_in(g, n, slot, ms);
     FGI_TRY(part_set_output(g, n, slot, out_set, stats, &ids));
-    return part_copy_ids(g, ids, out_ids, cap, out_n);
+    return part_copy_ids(ids, out_ids, cap, out_n);
 }
 
 fgi_status fgi_part_invalidate_all(fgi_graph* g, uint32_t* out_ids, uint64_t cap, uint64_t* out_n,
@@ -4246,7 +4292,7 @@ fgi_status fgi_part_invalidate_all(fgi_graph* g, uint32_t* out_ids, uint64_t cap
     if (!g) return FGI_EINVAL;
     std::vector<uint32_t> ids;
     FGI_TRY(part_invalidate_all(g, stats, &ids));
-    return part_copy_ids(g, ids, out_ids, cap, out_n);
+    return part_copy_ids(ids, out_ids, cap, out_n);
 }
 
 fgi_status fgi_part_prune(fgi_graph* g, fgi_prune_stats* stats) {
@@ -4272,12 +4318,13 @@ fgi_status fgi_part_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* st
         if (sp.n && (!sp.handles || (sp.kind == FGI_STEP_ADD_USED && !sp.used) ||
                      (sp.kind == FGI_STEP_BEGIN_COMPUTE && !sp.version)))
             return set_err(g, FGI_EINVAL, "step %u: missing arrays", k);
-        FGI_TRY(part_check_slots(g, pv, sp.n, sp.handles, sp.kind == FGI_STEP_BEGIN_COMPUTE));
-        if (sp.kind == FGI_STEP_ADD_USED) FGI_TRY(part_check_slots(g, pv, sp.n, sp.used, false));
-        if (sp.kind == FGI_STEP_BEGIN_COMPUTE)
-            for (uint32_t i = 0; i < sp.n; ++i)
-                if (sp.version[i] == 0 || sp.version[i] > kVMask)
-                    return set_err(g, FGI_EINVAL, "step %u: bad version (%u)", k, i);
+        if (sp.kind == FGI_STEP_BEGIN_COMPUTE) {
+            const BadBegin bad = check_begin_args(g, pv.n_global, sp.n, sp.handles, sp.version);
+            if (bad.why) return set_err(g, FGI_EINVAL, "step %u: %s (%u)", k, bad.why, bad.value);
+        } else {
+            FGI_TRY(part_check_slots(g, pv, sp.n, sp.handles));
+            if (sp.kind == FGI_STEP_ADD_USED) FGI_TRY(part_check_slots(g, pv, sp.n, sp.used));
+        }
     }
     // The batch's flagged records (fgi_part_last_flagged): one buffer and one cursor for all its cascades,
     // sized before anything is queued. begin_compute steps open the gate up front, so the cascades of the
@@ -4336,14 +4383,10 @@ fgi_status fgi_part_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* st
         std::vector<uint32_t> mh, mu;
         sp.handles = part_codes_in(g, sp.n, sp.handles, mh);
         if (sp.kind == FGI_STEP_ADD_USED) sp.used = part_codes_in(g, sp.n, sp.used, mu);
-        if (sp.n && !sp.handles) return set_err(g, FGI_EINVAL, "step %u: no handles", k);
-        const uint64_t before = ws.v_inv;
-        switch (sp.kind) {
-            case FGI_STEP_INVALIDATE: {
-                FGI_TRY(part_check_slots(g, pv, sp.n, sp.handles, false));
+        switch (sp.kind) {   // the kinds and every step's slots were checked above, before anything was applied
+            case FGI_STEP_INVALIDATE:
                 FGI_TRY(part_wave_host(g, pv, sp.n, sp.handles, sp.flags, &ws, &ids));
                 break;
-            }
             case FGI_STEP_BEGIN_COMPUTE:
                 FGI_TRY(part_begin_compute(g, sp.n, sp.handles, sp.version, sp.flags, static_cast<uint32_t*>(sp.out), &ws,
                                            &ids));
@@ -4354,11 +4397,8 @@ fgi_status fgi_part_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* st
             case FGI_STEP_SET_OUTPUT:
                 FGI_TRY(part_set_output(g, sp.n, sp.handles, static_cast<uint8_t*>(sp.out), &ws, &ids));
                 break;
-            default:
-                return set_err(g, FGI_EINVAL, "step %u: unknown kind %u", k, sp.kind);
         }
         if (stats && sp.kind != FGI_STEP_ADD_USED) stats->waves += 1;
-        (void)before;
     }
     FGI_TRY(vscope.sync());
     if (stats) {
@@ -4372,7 +4412,7 @@ fgi_status fgi_part_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* st
         stats->host_syncs += (uint32_t)ws.host_syncs;
         stats->total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    return part_copy_ids(g, ids, out_ids, cap, out_n);
+    return part_copy_ids(ids, out_ids, cap, out_n);
 }
 
 // The call's cascades left their records on the device (pflg_runs): the first call waits for the post-passes,
@@ -4413,17 +4453,7 @@ fgi_status fgi_part_last_flagged(fgi_graph* g, uint32_t* out_step, uint32_t* out
         }
         g->pflg_read = true;
     }
-    const uint64_t n = g->pflg_set.size();
-    if (out_n) *out_n = n;
-    if (!out_ids) return FGI_OK;
-    if (n > cap) return set_err(g, FGI_ECAPACITY, "the call's flagged sets hold %llu slots, the buffer %llu",
-                                (unsigned long long)n, (unsigned long long)cap);
-    for (uint64_t i = 0; i < n; ++i) {
-        out_ids[i] = (uint32_t)(g->pflg_set[i] >> 32);
-        if (out_step) out_step[i] = g->pflg_steps[i];
-        if (out_flags) out_flags[i] = (uint32_t)g->pflg_set[i];
-    }
-    return FGI_OK;
+    return copy_step_flagged(g, g->pflg_set, g->pflg_steps, out_step, out_ids, out_flags, cap, out_n);
 }
 
 }  // extern "C"

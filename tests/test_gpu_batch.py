@@ -7,9 +7,11 @@
 (b) Every behaviour scenario of tests/test_oracle_scenarios.py with each engine call made as a
     one-step batch (displacement and InvalidateOnSetOutput cascades included).
 (c) A batch whose add_used step outgrows the pool headroom (the call grows the pool and resumes).
-(d) A batch that runs out of detached handles: FGI_ECAPACITY, the steps before it applied.
+(d) A batch that runs out of detached handles: FGI_ECAPACITY, the steps before it applied; the single
+    call refuses whole and keeps the free list.
 (e) A batch with a bad argument in any step (a slot repeated in one begin_compute step, a slot or a
-    handle out of range, a bad version): FGI_EINVAL, nothing applied.
+    handle out of range, a bad version): FGI_EINVAL, nothing applied; the same steps as single calls
+    refuse at the call that carries it.
 """
 import functools
 
@@ -143,17 +145,35 @@ def test_batch_out_of_detached_handles(pkg, gpu_available):
     assert (f[0] & 3) == 1                  # step 0 applied
     assert (f[1] & 3) == 0 and v[1] == 1    # step 1 not
     g.close()
+    # the single call: refused whole, and the free list is not consumed by the refused call
+    g = pkg.Graph(8, n_detached=1)
+    g.register_nodes(np.arange(8, dtype=np.uint32), np.arange(8, dtype=np.uint64) * 2 + 1, np.zeros(8, np.uint32))
+    before = g.get_state([0, 1])
+    with pytest.raises(pkg.fgi.FgiError) as e:
+        g.begin_compute([0, 1], [101, 103])
+    assert e.value.status == 3
+    assert all(np.array_equal(a, b) for a, b in zip(before, g.get_state([0, 1])))
+    det = g.begin_compute([0], [101])
+    assert det[0] != pkg.fgi.NONE
+    g.close()
 
 
-@pytest.mark.parametrize("bad", ["repeat", "slot_range", "version0", "version_big", "used_range", "dep_range"])
-def test_batch_bad_argument_applies_nothing(pkg, gpu_available, bad):
+_BAD = ["repeat", "slot_range", "version0", "version_big", "used_range", "dep_range"]
+
+
+@pytest.mark.parametrize("form,bad", [(f, b) for f in ("batch", "calls") for b in _BAD],
+                         ids=_BAD + [b + "-calls" for b in _BAD])
+def test_batch_bad_argument_applies_nothing(pkg, gpu_available, form, bad):
+    """form "batch": the steps as one fgi_run_batch. form "calls": the same steps as single calls; the one
+    that carries the bad argument must be the one refused, and it must apply nothing."""
     rng = np.random.default_rng(61)
     n = 2000
     from harness import random_states
     from test_gpu_parity import _edges_from_live
     versions, flags = random_states(n, rng, p_delay=0.0)
     src, dst, tags = _edges_from_live(versions, flags, rng, 8000, n, stale_p=0.2)
-    g, o = build_pair(pkg, n, versions, flags, src, dst, tags)
+    # single calls displace more: the good begin_compute at the end meets the nodes an earlier call began
+    g, o = build_pair(pkg, n, versions, flags, src, dst, tags, n_detached=64 if form == "batch" else 1024)
     before = g.dump_states()
     edges = g.export_edges()
     slots = rng.choice(n, 500, replace=False).astype(np.uint32)
@@ -176,14 +196,28 @@ def test_batch_bad_argument_applies_nothing(pkg, gpu_available, bad):
              ("begin_compute", slots, ver),
              ("add_used", dep, use),
              ("set_output", slots[:100])]
-    with pytest.raises(pkg.FgiError) as e:
-        g.run_batch(steps)
+    if form == "batch":
+        with pytest.raises(pkg.FgiError) as e:
+            g.run_batch(steps)
+    else:
+        calls = [lambda: g.invalidate(steps[0][1]), lambda: g.begin_compute(slots, ver),
+                 lambda: g.add_used(dep, use), lambda: g.set_output(slots[:100])]
+        at = 2 if bad in ("used_range", "dep_range") else 1
+        for call in calls[:at]:
+            call()
+        # applied-nothing is judged against the graph as the good calls before the bad one left it
+        before = g.dump_states()
+        edges = g.export_edges()
+        with pytest.raises(pkg.FgiError) as e:
+            calls[at]()
     assert e.value.status == pkg.fgi.EINVAL
     after = g.dump_states()
     assert all(np.array_equal(a, b) for a, b in zip(before, after))
     assert all(np.array_equal(a, b) for a, b in zip(edges, g.export_edges()))
     # the graph still takes a good batch (the scratch the checks used is clean again)
     slots2 = np.unique(slots[slots < n])[:200].astype(np.uint32)
+    if form == "calls":
+        g.begin_compute(slots2, (versions[slots2] + np.uint64(7)).astype(np.uint64))
     g.run_batch([("begin_compute", slots2, (versions[slots2] + np.uint64(9)).astype(np.uint64))])
     g.close()
     o.close()
