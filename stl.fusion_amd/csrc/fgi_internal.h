@@ -1000,18 +1000,21 @@ struct PartView {
     unsigned long long* scratch_u64;
 };
 bool part_view(fgi_graph* g, PartView* v);
-// Exchange this level's messages: counts by all-gather, payload by grouped send/recv over RCCL.
-// Returns the number of target ids received (concatenated at recv_buf) and sent.
+// Exchange this level's messages over the partition's transport (RCCL, host collectives or an in-process
+// group): the per-owner counts and the rank's next-level {F, T} by an all-gather of words, which the host
+// waits for (glob = {sum F, sum T, sum sent}), the payload by the transport's variable-size exchange,
+// stream-ordered. Returns the number of target ids received (concatenated at recv_buf) and sent.
 fgi_status part_exchange(fgi_graph* g, uint64_t* n_recv, uint64_t* n_sent, uint64_t* glob);
-// Sum of count (1..kPartRedMax) device u64 over all ranks, returned on the host.
 // src[0, words) of device memory into the fine-grained host buffer dst (words + 2 long), the host
 // spinning on the sequence word dst[words]; dst[words + 1] = the publish's device wall-clock stamp
 // (wave.hip). wall_ms: milliseconds between two such stamps (WaveCtr::t0 is one).
 fgi_status publish_wait(fgi_graph* g, hipStream_t s, const unsigned long long* src, uint32_t words, unsigned long long* dst);
 float wall_ms(fgi_graph* g, uint64_t t0, uint64_t t1);
+// Sum of count (1..kPartRedMax) device u64 over all ranks, returned on the host.
 fgi_status part_allreduce_sum(fgi_graph* g, const unsigned long long* dev_val, uint64_t* out,
                               uint32_t count = 1);
-// all-gather every rank's local invalidated-bitmap words into front_global (part.hip)
+// The invalidated bitmap of all ranks' slots into front_global before a pull level, stream-ordered: every
+// rank's words all-gathered, or only the changed ones (FGI_OPT_FRONT_EXCHANGE; the host waits for their count)
 fgi_status part_allgather_front(fgi_graph* g);
 // zero front_global at a wave's start (the delta exchange's baseline)
 fgi_status part_front_reset(fgi_graph* g);
@@ -1025,7 +1028,7 @@ struct PartBuckets {
     unsigned long long* cur;           // [world] the next send_buf id to pack per owner
     unsigned long long* red;           // [kPartRedMax] device all-reduce source
 };
-fgi_status part_allgather_front_async(fgi_graph* g);
+fgi_status part_allgather_front_full(fgi_graph* g);
 uint64_t part_plan_key(const fgi_graph* g);
 fgi_status part_alltoall_async(fgi_graph* g);
 PartBuckets part_buckets(fgi_graph* g);
@@ -1086,10 +1089,10 @@ fgi_status fanout_move(fgi_graph* g, uint32_t n, const uint32_t* from, const uin
 fgi_status fanout_drop_handles(fgi_graph* g, uint32_t n, const uint32_t* handles);
 void fanout_destroy(fgi_graph* g);
 // ---- sharded loads (shard.hip) ----
-// The collectives they add to a partition's transport (part.hip, PartComm): host words (at most kShardWords
+// Their collectives, over the partition's transport (part.hip, PartComm): host words (at most kShardWords
 // per rank) all-gathered on the host; device byte ranges with per-peer counts, all-gathered (src[0,
 // bytes[rank]) of every rank in rank order at dst) or exchanged (src + soff[q], sbytes[q] bytes, to rank q;
-// rbytes[q] bytes from rank q at dst + roff[q]). Each returns with the data in place.
+// rbytes[q] bytes from rank q at dst + roff[q]; a range may be empty). Each returns with the data in place.
 constexpr uint32_t kShardWords = 24;
 fgi_status part_allgather_words(fgi_graph* g, const uint64_t* mine, uint32_t words, uint64_t* all);
 fgi_status part_allgatherv(fgi_graph* g, const void* src, const uint64_t* bytes, void* dst);

@@ -14,10 +14,15 @@
 // counts, moves the targets by grouped send/recv and the owners apply them (k_apply_recv); a pull
 // level all-gathers the frontier bitmap and every rank pulls its own slots.
 //
-// The collectives sit behind PartComm: RcclComm (one process per GPU, RCCL over xGMI) or
+// The bytes move behind PartComm, which has three transports: RcclComm (one process per GPU, RCCL over
+// xGMI), HostComm (one process per rank, every collective an all-gather the host supplies) and
 // LocalComm (an in-process group of P graphs driven by P host threads, device copies between their
-// buffers). Both run the same run_part_wave, so the in-process tests execute exactly the level
-// sequence a multi-GPU run does.
+// buffers). A transport knows five things: a few words of every rank on every host (gather_words), the
+// per-level sum of device words (allreduce_sum), the in-place sum of a device u32 array (allreduce_u32),
+// fixed-size stream-ordered moves (allgather_dev, alltoall_dev) and device byte ranges with per-peer
+// counts (alltoallv). The wave's and the loads' protocols (part_exchange, part_allgather_front,
+// part_allgatherv, ...) are written once above them, so all three transports run the same
+// run_part_wave and the in-process tests execute exactly the level sequence a multi-GPU run does.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <dlfcn.h>
@@ -41,59 +46,70 @@
 
 namespace fgi {
 
-// Collectives of a partitioned wave (every rank calls them in the same order).
+// What a transport must know (every rank calls these in the same order). Ranges of length 0 are legal
+// everywhere and move nothing.
+constexpr uint64_t kPairUnknown = ~0ull;   // alltoallv: the caller does not know the other ranks' pair sizes
 struct PartComm {
     virtual ~PartComm() {}
-    // sum of `count` device u64 over all ranks, returned on the host (synchronises the stream)
-    virtual fgi_status allreduce_sum(fgi_graph* g, const unsigned long long* dev_val, uint64_t* out, uint32_t count) = 0;
-    // this level's forwarded targets: send_buf[q] (send_cnt[q] entries) to owner q; the targets
-    // received from every other rank are concatenated at recv_buf. send_cnt[world, world + 1] carry
-    // the rank's local {F, T} of the next level, summed with the targets sent by all ranks into
-    // glob = {sum F, sum T, sum sent} on the way (the count all-gather doubles as the level's
-    // all-reduce, so a push level synchronises the host once)
-    virtual fgi_status exchange(fgi_graph* g, uint64_t* n_recv, uint64_t* n_sent, uint64_t* glob) = 0;
-    // every rank's local invalidated-bitmap words inv_bm[0, block/32) into front_global
-    virtual fgi_status allgather_front(fgi_graph* g) = 0;
-    // every rank's u64 `mine` into all[0, world) (host), synchronising the stream
-    virtual fgi_status allgather_count(fgi_graph* g, uint64_t mine, uint64_t* all) = 0;
-    // every rank's delta entries dbuf[0, cnt[rank]) (global word << 32 | word) to every other rank:
-    // concatenated at rbuf, returns the number received
-    virtual fgi_status exchange_delta(fgi_graph* g, const uint64_t* cnt, uint64_t* n_recv) = 0;
-    // Planned waves (no host synchronisation): stream-ordered collectives of fixed size.
-    // allgather_front without waiting for the host (the next kernels on the stream see front_global)
-    virtual fgi_status allgather_front_async(fgi_graph* g) = 0;
-    // a2a_send[q * C, + C) to rank q, into a2a_recv[r * C, + C) from every rank r
-    virtual fgi_status alltoall_async(fgi_graph* g) = 0;
-    // Partitioned mutations: the element-wise sum of a device u32 array over all ranks, in place
-    // (synchronises); every rank's cur_local (W64 words) into cur_all[q * W64, + W64) (stream-ordered)
-    virtual fgi_status allreduce_u32(fgi_graph* g, uint32_t* dev, uint64_t n) = 0;
-    virtual fgi_status allgather_cur_async(fgi_graph* g) = 0;
-    // Sharded loads (shard.hip). Each returns with the data in place (the stream is synchronised).
-    // every rank's `words` host u64 (<= kShardWords) into all[world][words] on the host
-    virtual fgi_status allgather_words(fgi_graph* g, const uint64_t* mine, uint32_t words, uint64_t* all) = 0;
-    // device byte ranges with per-peer counts: src + soff[q] (sbytes[q] bytes) goes to rank q, which finds it
-    // at its dst + roff[this rank]; rbytes[q] bytes arrive from rank q. src and dst do not overlap.
-    virtual fgi_status alltoallv(fgi_graph* g, const void* src, const uint64_t* soff, const uint64_t* sbytes, void* dst,
-                                 const uint64_t* roff, const uint64_t* rbytes) = 0;
-    // src[0, bytes[rank]) of every rank, concatenated in rank order at dst (bytes: [world], known to all)
-    virtual fgi_status allgatherv(fgi_graph* g, const void* src, const uint64_t* bytes, void* dst) {
-        uint64_t soff[8], sb[8], roff[8], at = 0;
-        for (uint32_t q = 0; q < (uint32_t)g->world; ++q) {
-            soff[q] = 0;
-            sb[q] = bytes[g->rank];
-            roff[q] = at;
-            at += bytes[q];
+    // words (<= kPartRedMax) u64 of every rank into all[world][words] on every host; src is device memory
+    // (final once the stream has run this far) or host memory. Returns with `all` filled: the stream has
+    // run up to here if src is on the device. `what` names the collective in a timeout's message.
+    virtual fgi_status gather_words(fgi_graph* g, const unsigned long long* src, bool src_dev, uint32_t words, uint64_t* all,
+                                    const char* what) = 0;
+    // sum of `count` device u64 over all ranks, returned on the host (the stream has run up to here):
+    // the words of every rank gathered on the host and summed there, unless the transport sums on the device
+    virtual fgi_status allreduce_sum(fgi_graph* g, const unsigned long long* dev_val, uint64_t* out, uint32_t count) {
+        uint64_t all[8 * kPartRedMax];
+        FGI_TRY(gather_words(g, dev_val, true, count, all, "all-reduce (wave counters)"));
+        for (uint32_t i = 0; i < count; ++i) {
+            out[i] = 0;
+            for (uint32_t q = 0; q < (uint32_t)g->world; ++q) out[i] += all[(size_t)q * count + i];
         }
-        return alltoallv(g, src, soff, sb, dst, roff, bytes);
+        return FGI_OK;
     }
+    // the element-wise sum of a device u32 array over all ranks, in place (synchronises)
+    virtual fgi_status allreduce_u32(fgi_graph* g, uint32_t* dev, uint64_t n) = 0;
+    // Fixed size, stream-ordered (the next kernels on the stream see dst; the host need not wait):
+    // every rank's src[0, bytes) into dst[q * bytes, + bytes) / src[q * bytes, + bytes) to rank q, which
+    // finds it at its dst[this rank * bytes, + bytes)
+    virtual fgi_status allgather_dev(fgi_graph* g, const void* src, void* dst, uint64_t bytes) = 0;
+    virtual fgi_status alltoall_dev(fgi_graph* g, const void* src, void* dst, uint64_t bytes) = 0;
+    // Device byte ranges with per-peer counts: src + soff[q] (sbytes[q] bytes) goes to rank q, which finds it
+    // at its dst + roff[this rank]; rbytes[q] bytes arrive from rank q. src and dst do not overlap.
+    // max_pair_bytes: the largest range of any pair of ranks if the caller knows it (from all-gathered
+    // counts), kPairUnknown if not. wait: return with the data in place and src free to reuse; otherwise
+    // the result is stream-ordered (and src is reused only by later work on the stream).
+    virtual fgi_status alltoallv(fgi_graph* g, const void* src, const uint64_t* soff, const uint64_t* sbytes, void* dst,
+                                 const uint64_t* roff, const uint64_t* rbytes, uint64_t max_pair_bytes, bool wait,
+                                 const char* what) = 0;
+    // src[0, bytes[rank]) of every rank, concatenated in rank order at dst (bytes: [world], known to all);
+    // returns with the data in place. Through alltoallv (allgatherv_pairs) unless the transport has a shorter way.
+    virtual fgi_status allgatherv(fgi_graph* g, const void* src, const uint64_t* bytes, void* dst);
 };
+
+static fgi_status allgatherv_pairs(fgi_graph* g, PartComm& c, const void* src, const uint64_t* bytes, void* dst) {
+    uint64_t soff[8], sb[8], roff[8], at = 0, mx = 0;
+    for (uint32_t q = 0; q < (uint32_t)g->world; ++q) {
+        soff[q] = 0;
+        sb[q] = bytes[g->rank];
+        roff[q] = at;
+        at += bytes[q];
+        mx = std::max(mx, bytes[q]);
+    }
+    return c.alltoallv(g, src, soff, sb, dst, roff, bytes, mx, true, "variable-size all-gather of a sharded load");
+}
+fgi_status PartComm::allgatherv(fgi_graph* g, const void* src, const uint64_t* bytes, void* dst) {
+    return allgatherv_pairs(g, *this, src, bytes, dst);
+}
 
 struct PartState {
     PartView v{};
     ncclComm_t comm = nullptr;
     std::unique_ptr<PartComm> ops;
-    unsigned long long* all_cnt = nullptr;     // [world * (world + 2)] device
-    unsigned long long* all_cnt_host = nullptr;
+    // gather_words over RCCL: [1 + world][kPartRedMax], this rank's words (when they come from the host)
+    // and everyone's; on the device and pinned on the host
+    unsigned long long* gw = nullptr;
+    unsigned long long* gw_host = nullptr;
     unsigned long long* scalar = nullptr;      // device scratch for all-reduce
     unsigned long long* scalar_host = nullptr;
     // In-store: the dependency entries of the owned slots, as loaded (dependant local << 32 | used
@@ -126,7 +142,7 @@ struct PartState {
     uint64_t cur_w64 = 0;
     unsigned long long* cur_local = nullptr;
     unsigned long long* cur_all = nullptr;
-    std::vector<uint32_t> u32_host;            // allreduce_u32's host copy (in-process groups)
+    std::vector<uint32_t> u32_host[2];         // allreduce_u32's host copies (in-process groups: LocalComm::meet)
     uint32_t* roots_codes = nullptr;           // fgi_part_invalidate's roots as codes (partition codes)
     uint32_t roots_cap = 0;
 };
@@ -206,8 +222,7 @@ static const RcclApi& rccl() {
 static bool rccl_ok() { return rccl().lib != nullptr; }
 
 // c: [W][W + 2] all-gathered counts (targets sent by q to r, then q's next-level F, T)
-template <typename C>
-static void sum_counts(const C* c, uint32_t W, uint64_t* glob) {
+static void sum_counts(const uint64_t* c, uint32_t W, uint64_t* glob) {
     const uint32_t S = W + 2;
     glob[0] = glob[1] = glob[2] = 0;
     for (uint32_t q = 0; q < W; ++q) {
@@ -228,7 +243,7 @@ fgi_status part_destroy(fgi_graph* g) {
     hipFree(p->v.send_buf);
     hipFree(p->v.recv_buf);
     hipFree(p->v.send_cnt);
-    hipFree(p->all_cnt);
+    hipFree(p->gw);
     hipFree(p->scalar);
     hipFree(p->v.front_global);
     hipFree(p->v.scratch_u64);
@@ -246,7 +261,7 @@ fgi_status part_destroy(fgi_graph* g) {
     hipFree(p->cur_all);
     hipFree(p->roots_codes);
     if (p->red_host) hipHostFree(p->red_host);
-    if (p->all_cnt_host) hipHostFree(p->all_cnt_host);
+    if (p->gw_host) hipHostFree(p->gw_host);
     if (p->scalar_host) hipHostFree(p->scalar_host);
     delete p;
     g->part = nullptr;
@@ -279,6 +294,7 @@ static double wait_limit_s(const char* var, double dflt) {
     const char* e = getenv(var);
     return e && *e ? atof(e) : dflt;
 }
+static double comm_limit_s() { return wait_limit_s("FGI_WAIT_TIMEOUT_S", 300.0); }
 
 static fgi_status comm_fail(fgi_graph* g, const char* what, double limit_s) {
     PartState* p = ps(g);
@@ -311,13 +327,12 @@ static fgi_status nccl_settle(fgi_graph* g, ncclComm_t comm, ncclResult_t r, con
     do {                                                                                                   \
         ncclResult_t _r = (call);                                                                          \
         if (_r != ncclSuccess)                                                                             \
-            FGI_TRY(nccl_settle((g), ps(g) ? ps(g)->comm : nullptr, _r, #call,                             \
-                                wait_limit_s("FGI_WAIT_TIMEOUT_S", 300.0)));                                \
+            FGI_TRY(nccl_settle((g), ps(g) ? ps(g)->comm : nullptr, _r, #call, comm_limit_s()));           \
     } while (0)
 
 // the host's wait behind this rank's collectives: the stream polled, bounded
 static fgi_status comm_sync(fgi_graph* g, hipStream_t s, const char* what) {
-    const double limit_s = wait_limit_s("FGI_WAIT_TIMEOUT_S", 300.0);
+    const double limit_s = comm_limit_s();
     const auto t0 = std::chrono::steady_clock::now();
     for (uint64_t k = 0;; ++k) {
         const hipError_t e = hipStreamQuery(s);
@@ -332,7 +347,36 @@ static fgi_status comm_sync(fgi_graph* g, hipStream_t s, const char* what) {
 }
 
 // ---- RCCL (one process per GPU) ----------------------------------------------------------------
+// At world size 1 nothing moves through RCCL (device copies instead) unless FGI_OPT_PART_COLLECTIVES
+// forces it. Only gather_words, allreduce_sum, allreduce_u32 and alltoallv(wait) make the host wait.
 struct RcclComm final : PartComm {
+    static bool through_rccl(fgi_graph* g) { return ps(g)->v.world > 1 || g->opt_part_coll; }
+
+    fgi_status gather_words(fgi_graph* g, const unsigned long long* src, bool src_dev, uint32_t words, uint64_t* all,
+                            const char* what) override {
+        PartState* p = ps(g);
+        const uint32_t W = p->v.world;
+        hipStream_t s = g->stream;
+        if (!src_dev && !through_rccl(g)) {   // one rank, host words: nothing to move
+            std::memcpy(all, src, 8ull * words);
+            return FGI_OK;
+        }
+        unsigned long long* every = p->gw_host + kPartRedMax;   // [W][words]
+        if (!src_dev) {
+            std::memcpy(p->gw_host, src, 8ull * words);
+            FGI_HIP(g, hipMemcpyAsync(p->gw, p->gw_host, 8ull * words, hipMemcpyHostToDevice, s));
+            src = p->gw;
+        }
+        if (through_rccl(g)) {
+            FGI_NCCL(g, rccl().AllGather(src, p->gw + kPartRedMax, words, ncclUint64, p->comm, s));
+            src = p->gw + kPartRedMax;
+        }
+        FGI_HIP(g, hipMemcpyAsync(every, src, (size_t)W * words * 8, hipMemcpyDeviceToHost, s));
+        FGI_TRY(comm_sync(g, s, what));
+        for (size_t i = 0; i < (size_t)W * words; ++i) all[i] = every[i];
+        return FGI_OK;
+    }
+    // summed on the device, into the words the host spins on
     fgi_status allreduce_sum(fgi_graph* g, const unsigned long long* dev_val, uint64_t* out, uint32_t count) override {
         PartState* p = ps(g);
         hipStream_t s = g->stream;
@@ -340,7 +384,7 @@ struct RcclComm final : PartComm {
         unsigned long long* dst = big ? p->red : p->scalar;
         unsigned long long* host = big ? p->red_host : p->scalar_host;
         const unsigned long long* src = dev_val;   // one rank: the sum is the value
-        if (p->v.world > 1 || g->opt_part_coll) {
+        if (through_rccl(g)) {
             FGI_NCCL(g, rccl().AllReduce(dev_val, dst, count, ncclUint64, ncclSum, p->comm, s));
             src = dst;
         }
@@ -348,7 +392,7 @@ struct RcclComm final : PartComm {
         (void)host;
         // the host spins instead of a stream sync (publish_wait is bounded by FGI_WAIT_TIMEOUT_S too)
         if (publish_wait(g, s, src, count, g->red_pub) != FGI_OK)
-            return comm_fail(g, "all-reduce (wave counters)", wait_limit_s("FGI_WAIT_TIMEOUT_S", 300.0));
+            return comm_fail(g, "all-reduce (wave counters)", comm_limit_s());
         for (uint32_t i = 0; i < count; ++i) out[i] = g->red_pub[i];
 #else
         FGI_HIP(g, hipMemcpyAsync(host, src, 8 * count, hipMemcpyDeviceToHost, s));
@@ -357,120 +401,45 @@ struct RcclComm final : PartComm {
 #endif
         return FGI_OK;
     }
-    fgi_status allgather_front_async(fgi_graph* g) override { return allgather_front(g); }   // stream-ordered
-    fgi_status alltoall_async(fgi_graph* g) override {
-        PartState* p = ps(g);
-        FGI_NCCL(g, rccl().AllToAll(p->a2a_send, p->a2a_recv, p->a2a_C, ncclUint32, p->comm, g->stream));
-        return FGI_OK;
-    }
     fgi_status allreduce_u32(fgi_graph* g, uint32_t* dev, uint64_t n) override {
-        PartState* p = ps(g);
-        if (n && (p->v.world > 1 || g->opt_part_coll))
-            FGI_NCCL(g, rccl().AllReduce(dev, dev, n, ncclUint32, ncclSum, p->comm, g->stream));
+        if (n && through_rccl(g))
+            FGI_NCCL(g, rccl().AllReduce(dev, dev, n, ncclUint32, ncclSum, ps(g)->comm, g->stream));
         return comm_sync(g, g->stream, "all-reduce (u32)");
     }
-    fgi_status allgather_cur_async(fgi_graph* g) override {
-        PartState* p = ps(g);
-        if (p->v.world > 1 || g->opt_part_coll)
-            FGI_NCCL(g, rccl().AllGather(p->cur_local, p->cur_all, p->cur_w64, ncclUint64, p->comm, g->stream));
-        else
-            FGI_HIP(g, hipMemcpyAsync(p->cur_all, p->cur_local, p->cur_w64 * 8, hipMemcpyDeviceToDevice, g->stream));
+    fgi_status allgather_dev(fgi_graph* g, const void* src, void* dst, uint64_t bytes) override {
+        if (through_rccl(g))
+            FGI_NCCL(g, rccl().AllGather(src, dst, bytes, ncclUint8, ps(g)->comm, g->stream));
+        else if (bytes)
+            FGI_HIP(g, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, g->stream));
         return FGI_OK;
     }
-    fgi_status exchange(fgi_graph* g, uint64_t* n_recv, uint64_t* n_sent, uint64_t* glob) override {
-        PartState* p = ps(g);
-        const uint32_t W = p->v.world, R = p->v.rank, S = W + 2;
-        hipStream_t s = g->stream;
-        FGI_NCCL(g, rccl().AllGather(p->v.send_cnt, p->all_cnt, S, ncclUint64, p->comm, s));
-        FGI_HIP(g, hipMemcpyAsync(p->all_cnt_host, p->all_cnt, (size_t)W * S * 8, hipMemcpyDeviceToHost, s));
-        FGI_TRY(comm_sync(g, s, "all-gather of the push level's counts"));
-        const unsigned long long* c = p->all_cnt_host;   // c[q * S + r]: sent by q to r; c[q * S + W + i]: q's F, T
-        sum_counts(c, W, glob);
-        uint64_t recv = 0, sent = 0;
-        FGI_NCCL(g, rccl().GroupStart());
-        for (uint32_t q = 0; q < W; ++q) {
-            if (q == R) continue;
-            const uint64_t to_q = c[R * S + q], from_q = c[q * S + R];
-            if (to_q)
-                FGI_NCCL(g, rccl().Send(p->v.send_buf + (uint64_t)q * p->v.block, to_q, ncclUint32, (int)q, p->comm, s));
-            if (from_q) FGI_NCCL(g, rccl().Recv(p->v.recv_buf + recv, from_q, ncclUint32, (int)q, p->comm, s));
-            recv += from_q;
-            sent += to_q;
-        }
-        FGI_NCCL(g, rccl().GroupEnd());
-        *n_recv = recv;
-        *n_sent = sent;
+    fgi_status alltoall_dev(fgi_graph* g, const void* src, void* dst, uint64_t bytes) override {
+        if (through_rccl(g))
+            FGI_NCCL(g, rccl().AllToAll(src, dst, bytes, ncclUint8, ps(g)->comm, g->stream));
+        else if (bytes)
+            FGI_HIP(g, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, g->stream));
         return FGI_OK;
     }
-    fgi_status allgather_front(fgi_graph* g) override {
-        PartState* p = ps(g);
-        FGI_NCCL(g, rccl().AllGather(g->inv_bm, p->v.front_global, p->v.block / 32, ncclUint32, p->comm, g->stream));
-        return FGI_OK;
-    }
-    fgi_status allgather_count(fgi_graph* g, uint64_t mine, uint64_t* all) override {
-        PartState* p = ps(g);
-        const uint32_t W = p->v.world;
-        p->scalar_host[0] = mine;
-        FGI_HIP(g, hipMemcpyAsync(p->scalar, p->scalar_host, 8, hipMemcpyHostToDevice, g->stream));
-        FGI_NCCL(g, rccl().AllGather(p->scalar, p->all_cnt, 1, ncclUint64, p->comm, g->stream));
-        FGI_HIP(g, hipMemcpyAsync(p->all_cnt_host, p->all_cnt, (size_t)W * 8, hipMemcpyDeviceToHost, g->stream));
-        FGI_TRY(comm_sync(g, g->stream, "all-gather of a count"));
-        for (uint32_t q = 0; q < W; ++q) all[q] = p->all_cnt_host[q];
-        return FGI_OK;
-    }
-    fgi_status exchange_delta(fgi_graph* g, const uint64_t* cnt, uint64_t* n_recv) override {
-        PartState* p = ps(g);
-        const uint32_t W = p->v.world, R = p->v.rank;
-        uint64_t recv = 0;
-        FGI_NCCL(g, rccl().GroupStart());
-        for (uint32_t q = 0; q < W; ++q) {
-            if (q == R) continue;
-            if (cnt[R]) FGI_NCCL(g, rccl().Send(p->dbuf, cnt[R], ncclUint64, (int)q, p->comm, g->stream));
-            if (cnt[q]) FGI_NCCL(g, rccl().Recv(p->rbuf + recv, cnt[q], ncclUint64, (int)q, p->comm, g->stream));
-            recv += cnt[q];
-        }
-        FGI_NCCL(g, rccl().GroupEnd());
-        *n_recv = recv;
-        return FGI_OK;
-    }
-    fgi_status allgather_words(fgi_graph* g, const uint64_t* mine, uint32_t words, uint64_t* all) override {
-        PartState* p = ps(g);
-        const uint32_t W = p->v.world;
-        if (W == 1 && !g->opt_part_coll) {
-            std::memcpy(all, mine, 8ull * words);
-            return FGI_OK;
-        }
-        unsigned long long* d = nullptr;   // [1 + W][words]: mine, then everyone's
-        FGI_HIP(g, hipMalloc(&d, (size_t)(W + 1) * words * 8));
-        fgi_status st = FGI_OK;
-        auto run = [&]() -> fgi_status {
-            FGI_HIP(g, hipMemcpyAsync(d, mine, 8ull * words, hipMemcpyHostToDevice, g->stream));
-            FGI_NCCL(g, rccl().AllGather(d, d + words, words, ncclUint64, p->comm, g->stream));
-            FGI_HIP(g, hipMemcpyAsync(all, d + words, (size_t)W * words * 8, hipMemcpyDeviceToHost, g->stream));
-            return comm_sync(g, g->stream, "all-gather of a sharded load's counts");
-        };
-        st = run();
-        hipFree(d);
-        return st;
-    }
+    // the engine's one grouped send/recv: every variable-size exchange (a push level's targets, the delta
+    // frontier lists, the sharded loads) comes through here
     fgi_status alltoallv(fgi_graph* g, const void* src, const uint64_t* soff, const uint64_t* sbytes, void* dst,
-                         const uint64_t* roff, const uint64_t* rbytes) override {
+                         const uint64_t* roff, const uint64_t* rbytes, uint64_t, bool wait, const char* what) override {
         PartState* p = ps(g);
         const uint32_t W = p->v.world;
         const char* s8 = static_cast<const char*>(src);
         char* d8 = static_cast<char*>(dst);
-        if (W == 1 && !g->opt_part_coll) {
+        if (!through_rccl(g)) {
             if (rbytes[0])
                 FGI_HIP(g, hipMemcpyAsync(d8 + roff[0], s8 + soff[0], rbytes[0], hipMemcpyDeviceToDevice, g->stream));
-            return comm_sync(g, g->stream, "sharded load (copy)");
+        } else {
+            FGI_NCCL(g, rccl().GroupStart());
+            for (uint32_t q = 0; q < W; ++q) {
+                if (sbytes[q]) FGI_NCCL(g, rccl().Send(s8 + soff[q], sbytes[q], ncclUint8, (int)q, p->comm, g->stream));
+                if (rbytes[q]) FGI_NCCL(g, rccl().Recv(d8 + roff[q], rbytes[q], ncclUint8, (int)q, p->comm, g->stream));
+            }
+            FGI_NCCL(g, rccl().GroupEnd());
         }
-        FGI_NCCL(g, rccl().GroupStart());
-        for (uint32_t q = 0; q < W; ++q) {
-            if (sbytes[q]) FGI_NCCL(g, rccl().Send(s8 + soff[q], sbytes[q], ncclUint8, (int)q, p->comm, g->stream));
-            if (rbytes[q]) FGI_NCCL(g, rccl().Recv(d8 + roff[q], rbytes[q], ncclUint8, (int)q, p->comm, g->stream));
-        }
-        FGI_NCCL(g, rccl().GroupEnd());
-        return comm_sync(g, g->stream, "variable-size exchange of a sharded load");
+        return wait ? comm_sync(g, g->stream, what) : FGI_OK;
     }
 };
 
@@ -480,7 +449,7 @@ struct RcclComm final : PartComm {
 // GPUs (RCCL refuses two ranks on one device), so the planned and host-driven waves, the mutations and
 // the prune of run_part_wave execute across real process boundaries on any box. Each collective
 // synchronises the rank's stream, moves its part through host memory and copies the result back:
-// correct, not fast (the async variants are synchronous here).
+// correct, not fast (the stream-ordered primitives are synchronous here).
 struct HostComm final : PartComm {
     fgi_allgather_fn fn;
     void* ctx;
@@ -510,100 +479,18 @@ struct HostComm final : PartComm {
         FGI_HIP(g, hipStreamSynchronize(g->stream));   // the host buffer is reused by the next collective
         return FGI_OK;
     }
-    const uint64_t* u64(uint32_t q, uint64_t words) const { return reinterpret_cast<const uint64_t*>(rbuf.data()) + q * words; }
 
-    fgi_status allreduce_sum(fgi_graph* g, const unsigned long long* dev_val, uint64_t* out, uint32_t count) override {
-        FGI_TRY(stage(g, dev_val, 8ull * count));
-        FGI_TRY(gather(g, 8ull * count));
-        for (uint32_t i = 0; i < count; ++i) {
-            uint64_t t = 0;
-            for (uint32_t q = 0; q < ps(g)->v.world; ++q) t += u64(q, count)[i];
-            out[i] = t;
+    fgi_status gather_words(fgi_graph* g, const unsigned long long* src, bool src_dev, uint32_t words, uint64_t* all,
+                            const char*) override {
+        if (src_dev) {
+            FGI_TRY(stage(g, src, 8ull * words));
+        } else {
+            if (sbuf.size() < 8ull * words) sbuf.resize(8ull * words);
+            std::memcpy(sbuf.data(), src, 8ull * words);
         }
+        FGI_TRY(gather(g, 8ull * words));
+        std::memcpy(all, rbuf.data(), (size_t)ps(g)->v.world * words * 8);
         return FGI_OK;
-    }
-    fgi_status exchange(fgi_graph* g, uint64_t* n_recv, uint64_t* n_sent, uint64_t* glob) override {
-        PartState* p = ps(g);
-        const uint32_t W = p->v.world, R = p->v.rank, S = W + 2;
-        FGI_TRY(stage(g, p->v.send_cnt, 8ull * S));
-        FGI_TRY(gather(g, 8ull * S));
-        std::vector<uint64_t> c(reinterpret_cast<const uint64_t*>(rbuf.data()),
-                                reinterpret_cast<const uint64_t*>(rbuf.data()) + (size_t)W * S);
-        sum_counts(c.data(), W, glob);
-        uint64_t mx = 0;   // the payload moves as one all-gather of [W][mx] ids per rank
-        for (uint32_t q = 0; q < W; ++q)
-            for (uint32_t r = 0; r < W; ++r)
-                if (r != q) mx = std::max<uint64_t>(mx, c[(size_t)q * S + r]);
-        uint64_t sent = 0, recv = 0;
-        if (mx) {
-            sbuf.assign((size_t)W * mx * 4, 0);
-            for (uint32_t q = 0; q < W; ++q) {
-                const uint64_t to_q = q == R ? 0 : c[(size_t)R * S + q];
-                if (to_q)
-                    FGI_HIP(g, hipMemcpyAsync(sbuf.data() + (size_t)q * mx * 4, p->v.send_buf + (uint64_t)q * p->v.block,
-                                              to_q * 4, hipMemcpyDeviceToHost, g->stream));
-                sent += to_q;
-            }
-            FGI_HIP(g, hipStreamSynchronize(g->stream));
-            FGI_TRY(gather(g, (uint64_t)W * mx * 4));
-            std::vector<uint32_t> in;
-            for (uint32_t q = 0; q < W; ++q) {
-                if (q == R) continue;
-                const uint64_t from_q = c[(size_t)q * S + R];
-                const uint32_t* src = reinterpret_cast<const uint32_t*>(rbuf.data() + ((size_t)q * W + R) * mx * 4);
-                in.insert(in.end(), src, src + from_q);
-            }
-            recv = in.size();
-            FGI_TRY(upload(g, p->v.recv_buf, in.data(), recv * 4));
-        }
-        *n_recv = recv;
-        *n_sent = sent;
-        return FGI_OK;
-    }
-    fgi_status allgather_front(fgi_graph* g) override {
-        PartState* p = ps(g);
-        const uint64_t bytes = (uint64_t)(p->v.block / 32) * 4;
-        FGI_TRY(stage(g, g->inv_bm, bytes));
-        FGI_TRY(gather(g, bytes));
-        return upload(g, p->v.front_global, rbuf.data(), (uint64_t)p->v.world * bytes);
-    }
-    fgi_status allgather_count(fgi_graph* g, uint64_t mine, uint64_t* all) override {
-        sbuf.resize(std::max<size_t>(sbuf.size(), 8));
-        std::memcpy(sbuf.data(), &mine, 8);
-        FGI_TRY(gather(g, 8));
-        for (uint32_t q = 0; q < ps(g)->v.world; ++q) all[q] = u64(q, 1)[0];
-        return FGI_OK;
-    }
-    fgi_status exchange_delta(fgi_graph* g, const uint64_t* cnt, uint64_t* n_recv) override {
-        PartState* p = ps(g);
-        const uint32_t W = p->v.world, R = p->v.rank;
-        uint64_t mx = 0;
-        for (uint32_t q = 0; q < W; ++q) mx = std::max<uint64_t>(mx, cnt[q]);
-        uint64_t recv = 0;
-        if (mx) {
-            sbuf.assign(mx * 8, 0);
-            FGI_TRY(stage(g, p->dbuf, cnt[R] * 8));
-            FGI_TRY(gather(g, mx * 8));
-            std::vector<uint64_t> in;
-            for (uint32_t q = 0; q < W; ++q)
-                if (q != R) in.insert(in.end(), u64(q, mx), u64(q, mx) + cnt[q]);
-            recv = in.size();
-            FGI_TRY(upload(g, p->rbuf, in.data(), recv * 8));
-        }
-        *n_recv = recv;
-        return FGI_OK;
-    }
-    fgi_status allgather_front_async(fgi_graph* g) override { return allgather_front(g); }
-    fgi_status alltoall_async(fgi_graph* g) override {
-        PartState* p = ps(g);
-        const uint32_t W = p->v.world, R = p->v.rank;
-        const uint64_t C = p->a2a_C;
-        FGI_TRY(stage(g, p->a2a_send, (uint64_t)W * C * 4));
-        FGI_TRY(gather(g, (uint64_t)W * C * 4));
-        std::vector<uint32_t> in((size_t)W * C);
-        for (uint32_t q = 0; q < W; ++q)
-            std::memcpy(in.data() + (size_t)q * C, rbuf.data() + ((size_t)q * W + R) * C * 4, C * 4);
-        return upload(g, p->a2a_recv, in.data(), (uint64_t)W * C * 4);
     }
     fgi_status allreduce_u32(fgi_graph* g, uint32_t* dev, uint64_t n) override {
         const uint32_t W = ps(g)->v.world;
@@ -616,20 +503,21 @@ struct HostComm final : PartComm {
         }
         return upload(g, dev, sum.data(), n * 4);
     }
-    fgi_status allgather_cur_async(fgi_graph* g) override {
-        PartState* p = ps(g);
-        FGI_TRY(stage(g, p->cur_local, p->cur_w64 * 8));
-        FGI_TRY(gather(g, p->cur_w64 * 8));
-        return upload(g, p->cur_all, rbuf.data(), (uint64_t)p->v.world * p->cur_w64 * 8);
+    fgi_status allgather_dev(fgi_graph* g, const void* src, void* dst, uint64_t bytes) override {
+        FGI_TRY(stage(g, src, bytes));
+        FGI_TRY(gather(g, bytes));
+        return upload(g, dst, rbuf.data(), (uint64_t)ps(g)->v.world * bytes);
     }
-    fgi_status allgather_words(fgi_graph* g, const uint64_t* mine, uint32_t words, uint64_t* all) override {
-        sbuf.resize(std::max<size_t>(sbuf.size(), 8ull * words));
-        std::memcpy(sbuf.data(), mine, 8ull * words);
-        FGI_TRY(gather(g, 8ull * words));
-        std::memcpy(all, rbuf.data(), (size_t)ps(g)->v.world * words * 8);
-        return FGI_OK;
+    fgi_status alltoall_dev(fgi_graph* g, const void* src, void* dst, uint64_t bytes) override {
+        const uint32_t W = ps(g)->v.world, R = ps(g)->v.rank;
+        FGI_TRY(stage(g, src, (uint64_t)W * bytes));
+        FGI_TRY(gather(g, (uint64_t)W * bytes));
+        std::vector<uint8_t> in((size_t)W * bytes);
+        for (uint32_t q = 0; q < W; ++q)
+            std::memcpy(in.data() + (size_t)q * bytes, rbuf.data() + ((size_t)q * W + R) * bytes, bytes);
+        return upload(g, dst, in.data(), (uint64_t)W * bytes);
     }
-    // one all-gather of [max] padded bytes per rank
+    // one all-gather of [max] padded bytes per rank: a world-th of what alltoallv would move
     fgi_status allgatherv(fgi_graph* g, const void* src, const uint64_t* bytes, void* dst) override {
         const uint32_t W = ps(g)->v.world, R = ps(g)->v.rank;
         uint64_t mx = 0;
@@ -649,14 +537,21 @@ struct HostComm final : PartComm {
         FGI_HIP(g, hipStreamSynchronize(g->stream));
         return FGI_OK;
     }
-    // the largest range of any pair first (one word per rank), then one all-gather of [world][max] padded bytes
+    // one all-gather of [world][max] padded bytes; the largest range of any pair first (one word per rank)
+    // where the caller does not know it. Always waits.
     fgi_status alltoallv(fgi_graph* g, const void* src, const uint64_t* soff, const uint64_t* sbytes, void* dst,
-                         const uint64_t* roff, const uint64_t* rbytes) override {
+                         const uint64_t* roff, const uint64_t* rbytes, uint64_t max_pair_bytes, bool,
+                         const char* what) override {
         const uint32_t W = ps(g)->v.world, R = ps(g)->v.rank;
-        uint64_t mine = 0, mx = 0, all[8];
-        for (uint32_t q = 0; q < W; ++q) mine = std::max(mine, sbytes[q]);
-        FGI_TRY(allgather_words(g, &mine, 1, all));
-        for (uint32_t q = 0; q < W; ++q) mx = std::max(mx, all[q]);
+        uint64_t mx = max_pair_bytes;
+        if (mx == kPairUnknown) {
+            unsigned long long mine = 0;
+            uint64_t all[8];
+            for (uint32_t q = 0; q < W; ++q) mine = std::max<unsigned long long>(mine, sbytes[q]);
+            FGI_TRY(gather_words(g, &mine, false, 1, all, what));
+            mx = 0;
+            for (uint32_t q = 0; q < W; ++q) mx = std::max(mx, all[q]);
+        }
         FGI_HIP(g, hipStreamSynchronize(g->stream));
         if (!mx) return FGI_OK;
         sbuf.assign((size_t)W * mx, 0);
@@ -685,20 +580,18 @@ struct LocalGroup {
     uint32_t arrived = 0;
     uint64_t gen = 0;
     bool failed = false;
-    std::vector<uint64_t> vals;   // [P][kPartRedMax] all-reduce contributions
-    std::vector<uint64_t> cnt;    // [P][P + 2] targets rank r forwards to owner q, then r's F, T
-    // stream-ordered exchanges (planned waves): rank r records ready[r] when its source is final and
-    // done[r] when its copies from the others are queued; the others' streams wait on them
+    std::vector<uint64_t> vals;   // [2][P][kPartRedMax] gather_words' contributions (LocalComm::meet)
+    // device exchanges (LocalComm::exchange_dev): rank r records ready[r] when its source is final and
+    // done[r] when its copies from the others are queued; the others' streams wait on them. xsrc, xoff:
+    // rank r's source and its [P] byte offsets per destination
     std::vector<hipEvent_t> ready, done;
-    // variable-size exchanges (sharded loads): rank r's source and its [P] byte offsets per destination
     std::vector<const char*> xsrc;
     std::vector<uint64_t> xoff;
 
     explicit LocalGroup(std::vector<fgi_graph*> g) : gs(std::move(g)) {
         xsrc.assign(gs.size(), nullptr);
         xoff.assign(gs.size() * gs.size(), 0);
-        vals.assign(gs.size() * kPartRedMax, 0);
-        cnt.assign(gs.size() * (gs.size() + 2), 0);
+        vals.assign(2 * gs.size() * kPartRedMax, 0);
         ready.assign(gs.size(), nullptr);
         done.assign(gs.size(), nullptr);
         for (size_t r = 0; r < gs.size(); ++r) {
@@ -733,13 +626,15 @@ struct LocalGroup {
         failed = true;
         cv.notify_all();
     }
-    void reset() {
+    void reset() {   // gen stays: LocalComm::meet takes its slots from it
         std::lock_guard<std::mutex> lk(mu);
         failed = false;
         arrived = 0;
     }
 };
 
+// Every collective is one of the two exchanges below; they alone meet the group's barrier. A rank that
+// leaves one with an error of its own fails the group in its driver (local_run), which releases the rest.
 struct LocalComm final : PartComm {
     std::shared_ptr<LocalGroup> grp;
     uint32_t rank;
@@ -747,208 +642,179 @@ struct LocalComm final : PartComm {
 
     fgi_status peer_failed(fgi_graph* g) { return set_err(g, FGI_EDEVICE, "another rank of the in-process group failed"); }
 
-    fgi_status allreduce_sum(fgi_graph* g, const unsigned long long* dev_val, uint64_t* out, uint32_t count) override {
-        PartState* p = ps(g);
-#if FGI_SPIN_WAIT
-        (void)p;
-        FGI_TRY(publish_wait(g, g->stream, dev_val, count, g->red_pub));
-        const unsigned long long* host = g->red_pub;
-#else
-        unsigned long long* host = count > 4 ? p->red_host : p->scalar_host;
-        FGI_HIP(g, hipMemcpyAsync(host, dev_val, 8 * count, hipMemcpyDeviceToHost, g->stream));
-        FGI_HIP(g, hipStreamSynchronize(g->stream));
-#endif
+    // Host memory, synchronous: publish(slot) leaves this rank's data in its slot, read(slot) finds every
+    // rank's there. One barrier: slot is the parity of the group's generation, the same on every rank
+    // between two barriers, so the next exchange writes the other slot, and a rank comes to write this one
+    // again only behind that exchange's barrier, which every rank reaches after its reads here.
+    // This rests on two things. Every rank meets every barrier of the group, the same number of times and in
+    // the same order (the collectives' contract; exchange_dev's two barriers leave the parity as it was, for
+    // every rank alike). And LocalGroup::gen only ever counts completed barriers: reset() after a failed call
+    // must leave it alone, since the ranks of a failed call may have left at different barriers and gen is
+    // the one count they still share.
+    template <class P, class R>
+    fgi_status meet(fgi_graph* g, P publish, R read) {
+        uint32_t slot = 0;
         {
             std::lock_guard<std::mutex> lk(grp->mu);
-            for (uint32_t i = 0; i < count; ++i) grp->vals[(size_t)rank * kPartRedMax + i] = host[i];
+            slot = (uint32_t)(grp->gen & 1);
         }
+        FGI_TRY(publish(slot));
         if (!grp->arrive()) return peer_failed(g);
-        for (uint32_t i = 0; i < count; ++i) {
-            uint64_t t = 0;
-            for (size_t r = 0; r < grp->gs.size(); ++r) t += grp->vals[r * kPartRedMax + i];
-            out[i] = t;
-        }
-        if (!grp->arrive()) return peer_failed(g);   // nobody overwrites vals before all have read them
+        read(slot);
         return FGI_OK;
     }
-    fgi_status exchange(fgi_graph* g, uint64_t* n_recv, uint64_t* n_sent, uint64_t* glob) override {
-        PartState* p = ps(g);
-        const uint32_t W = p->v.world, R = rank, S = W + 2;
-        FGI_HIP(g, hipMemcpyAsync(p->all_cnt_host, p->v.send_cnt, (size_t)S * 8, hipMemcpyDeviceToHost, g->stream));
-        FGI_HIP(g, hipStreamSynchronize(g->stream));   // also: this rank's send buffers are complete
-        {
-            std::lock_guard<std::mutex> lk(grp->mu);
-            for (uint32_t q = 0; q < S; ++q) grp->cnt[(size_t)R * S + q] = p->all_cnt_host[q];
-        }
-        if (!grp->arrive()) return peer_failed(g);
-        sum_counts(grp->cnt.data(), W, glob);
-        uint64_t recv = 0, sent = 0;
-        for (uint32_t q = 0; q < W; ++q) {
-            if (q == R) continue;
-            const uint64_t from_q = grp->cnt[(size_t)q * S + R];
-            if (from_q) {
-                PartState* pq = ps(grp->gs[q]);
-                FGI_HIP(g, hipMemcpyAsync(p->v.recv_buf + recv, pq->v.send_buf + (uint64_t)R * pq->v.block, from_q * 4,
-                                          hipMemcpyDefault, g->stream));
-            }
-            recv += from_q;
-            sent += grp->cnt[(size_t)R * S + q];
-        }
-        // the senders refill their buffers (and counts) only after every rank's copies are done
-        FGI_HIP(g, hipStreamSynchronize(g->stream));
-        if (!grp->arrive()) return peer_failed(g);
-        *n_recv = recv;
-        *n_sent = sent;
-        return FGI_OK;
-    }
-    fgi_status allgather_front(fgi_graph* g) override {
-        PartState* p = ps(g);
-        FGI_HIP(g, hipStreamSynchronize(g->stream));   // this rank's invalidated words are final
-        if (!grp->arrive()) return peer_failed(g);
-        const uint64_t words = p->v.block / 32;
-        for (size_t q = 0; q < grp->gs.size(); ++q)
-            FGI_HIP(g, hipMemcpyAsync(p->v.front_global + q * words, grp->gs[q]->inv_bm, words * 4, hipMemcpyDefault,
-                                      g->stream));
-        FGI_HIP(g, hipStreamSynchronize(g->stream));
-        if (!grp->arrive()) return peer_failed(g);     // the sources stay untouched until all copies are done
-        return FGI_OK;
-    }
-    fgi_status allgather_count(fgi_graph* g, uint64_t mine, uint64_t* all) override {
-        const size_t W = grp->gs.size();
-        {
-            std::lock_guard<std::mutex> lk(grp->mu);
-            grp->vals[(size_t)rank * kPartRedMax] = mine;
-        }
-        if (!grp->arrive()) return peer_failed(g);
-        for (size_t q = 0; q < W; ++q) all[q] = grp->vals[q * kPartRedMax];
-        if (!grp->arrive()) return peer_failed(g);
-        return FGI_OK;
-    }
-    fgi_status exchange_delta(fgi_graph* g, const uint64_t* cnt, uint64_t* n_recv) override {
-        PartState* p = ps(g);
-        FGI_HIP(g, hipStreamSynchronize(g->stream));   // this rank's delta list is complete
-        if (!grp->arrive()) return peer_failed(g);
-        uint64_t recv = 0;
-        for (uint32_t q = 0; q < (uint32_t)grp->gs.size(); ++q) {
-            if (q == rank) continue;
-            if (cnt[q])
-                FGI_HIP(g, hipMemcpyAsync(p->rbuf + recv, ps(grp->gs[q])->dbuf, cnt[q] * 8, hipMemcpyDefault, g->stream));
-            recv += cnt[q];
-        }
-        FGI_HIP(g, hipStreamSynchronize(g->stream));
-        if (!grp->arrive()) return peer_failed(g);     // the senders keep their lists until every copy is done
-        *n_recv = recv;
-        return FGI_OK;
-    }
-    // Stream-ordered copies between the group's graphs, no host wait: this rank's source is marked
-    // ready on its stream; once every rank has queued its mark (a host-thread barrier, no device
-    // synchronisation), each stream waits for the others' marks and copies; then each stream waits
-    // until every rank's copies are queued behind its own marks, so no source is overwritten early.
+    // Device memory: this rank publishes its source (and offsets into it, nullable); behind the first
+    // barrier every source is final and `copies` runs; behind the second every rank's copies out of it are
+    // done, so no source is overwritten early (and the host publishes its next source only then).
+    // Stream-ordered, no host wait: the rank marks its source ready on its stream before the first barrier
+    // (a host-thread barrier, no device synchronisation) and its copies done before the second; each stream
+    // waits for the others' marks. host_waits: the host waits for its stream before each barrier instead,
+    // and returns with the data in place.
     template <class F>
-    fgi_status exchange_async(fgi_graph* g, F copies) {
-        FGI_HIP(g, hipEventRecord(grp->ready[rank], g->stream));
-        if (!grp->arrive()) return peer_failed(g);
-        for (size_t q = 0; q < grp->gs.size(); ++q)
-            if (q != rank) FGI_HIP(g, hipStreamWaitEvent(g->stream, grp->ready[q], 0));
+    fgi_status exchange_dev(fgi_graph* g, const void* src, const uint64_t* soff, bool host_waits, F copies) {
+        const size_t W = grp->gs.size();
+        grp->xsrc[rank] = static_cast<const char*>(src);
+        for (size_t q = 0; q < W; ++q) grp->xoff[rank * W + q] = soff ? soff[q] : 0;
+        // what this rank's stream holds so far is final for the others behind the barrier: the host has
+        // waited for it, or it is marked and the others' streams wait for the mark
+        auto settle = [&](std::vector<hipEvent_t>& marks) -> fgi_status {
+            if (host_waits) {
+                FGI_HIP(g, hipStreamSynchronize(g->stream));
+                return grp->arrive() ? FGI_OK : peer_failed(g);
+            }
+            FGI_HIP(g, hipEventRecord(marks[rank], g->stream));
+            if (!grp->arrive()) return peer_failed(g);
+            for (size_t q = 0; q < W; ++q)
+                if (q != rank) FGI_HIP(g, hipStreamWaitEvent(g->stream, marks[q], 0));
+            return FGI_OK;
+        };
+        FGI_TRY(settle(grp->ready));   // every source is final
         FGI_TRY(copies());
-        FGI_HIP(g, hipEventRecord(grp->done[rank], g->stream));
-        if (!grp->arrive()) return peer_failed(g);
-        for (size_t q = 0; q < grp->gs.size(); ++q)
-            if (q != rank) FGI_HIP(g, hipStreamWaitEvent(g->stream, grp->done[q], 0));
-        return FGI_OK;
+        return settle(grp->done);      // every rank's copies out of this rank's source are done
     }
-    fgi_status allgather_front_async(fgi_graph* g) override {
-        PartState* p = ps(g);
-        const uint64_t words = p->v.block / 32;
-        return exchange_async(g, [&]() -> fgi_status {
-            for (size_t q = 0; q < grp->gs.size(); ++q)
-                FGI_HIP(g, hipMemcpyAsync(p->v.front_global + q * words, grp->gs[q]->inv_bm, words * 4, hipMemcpyDefault,
-                                          g->stream));
-            return FGI_OK;
-        });
-    }
-    fgi_status alltoall_async(fgi_graph* g) override {
-        PartState* p = ps(g);
-        const uint64_t C = p->a2a_C;
-        return exchange_async(g, [&]() -> fgi_status {
-            for (size_t q = 0; q < grp->gs.size(); ++q)
-                FGI_HIP(g, hipMemcpyAsync(p->a2a_recv + q * C, ps(grp->gs[q])->a2a_send + (uint64_t)rank * C, C * 4,
-                                          hipMemcpyDefault, g->stream));
-            return FGI_OK;
-        });
-    }
-    fgi_status allgather_cur_async(fgi_graph* g) override {
-        PartState* p = ps(g);
-        const uint64_t W = p->cur_w64;
-        return exchange_async(g, [&]() -> fgi_status {
-            for (size_t q = 0; q < grp->gs.size(); ++q)
-                FGI_HIP(g, hipMemcpyAsync(p->cur_all + q * W, ps(grp->gs[q])->cur_local, W * 8, hipMemcpyDefault, g->stream));
-            return FGI_OK;
-        });
-    }
-    // host-side sum: every rank copies its array out, the group adds them, every rank copies the sum in
-    fgi_status allreduce_u32(fgi_graph* g, uint32_t* dev, uint64_t n) override {
-        PartState* p = ps(g);
-        p->u32_host.resize(n);
-        if (n) FGI_HIP(g, hipMemcpyAsync(p->u32_host.data(), dev, n * 4, hipMemcpyDeviceToHost, g->stream));
-        FGI_HIP(g, hipStreamSynchronize(g->stream));
-        if (!grp->arrive()) return peer_failed(g);
-        std::vector<uint32_t> sum(n, 0);
-        for (size_t q = 0; q < grp->gs.size(); ++q) {
-            const std::vector<uint32_t>& h = ps(grp->gs[q])->u32_host;
-            for (uint64_t i = 0; i < n; ++i) sum[i] += h[i];
+
+    fgi_status gather_words(fgi_graph* g, const unsigned long long* src, bool src_dev, uint32_t words, uint64_t* all,
+                            const char*) override {
+        const size_t W = grp->gs.size();
+        if (src_dev) {
+#if FGI_SPIN_WAIT
+            FGI_TRY(publish_wait(g, g->stream, src, words, g->red_pub));
+            src = g->red_pub;
+#else
+            unsigned long long* host = words > 4 ? ps(g)->red_host : ps(g)->scalar_host;
+            FGI_HIP(g, hipMemcpyAsync(host, src, 8 * words, hipMemcpyDeviceToHost, g->stream));
+            FGI_HIP(g, hipStreamSynchronize(g->stream));
+            src = host;
+#endif
         }
-        if (!grp->arrive()) return peer_failed(g);   // nobody changes its copy before all have read it
+        return meet(
+            g,
+            [&](uint32_t slot) -> fgi_status {
+                for (uint32_t i = 0; i < words; ++i) grp->vals[(slot * W + rank) * kPartRedMax + i] = src[i];
+                return FGI_OK;
+            },
+            [&](uint32_t slot) {
+                for (size_t q = 0; q < W; ++q)
+                    for (uint32_t i = 0; i < words; ++i) all[q * words + i] = grp->vals[(slot * W + q) * kPartRedMax + i];
+            });
+    }
+    // host-side sum: every rank copies its array out, adds up everyone's and copies the sum in
+    fgi_status allreduce_u32(fgi_graph* g, uint32_t* dev, uint64_t n) override {
+        std::vector<uint32_t> sum(n, 0);
+        FGI_TRY(meet(
+            g,
+            [&](uint32_t slot) -> fgi_status {
+                std::vector<uint32_t>& h = ps(g)->u32_host[slot];
+                h.resize(n);
+                if (n) FGI_HIP(g, hipMemcpyAsync(h.data(), dev, n * 4, hipMemcpyDeviceToHost, g->stream));
+                FGI_HIP(g, hipStreamSynchronize(g->stream));
+                return FGI_OK;
+            },
+            [&](uint32_t slot) {
+                for (size_t q = 0; q < grp->gs.size(); ++q) {
+                    const std::vector<uint32_t>& h = ps(grp->gs[q])->u32_host[slot];
+                    for (uint64_t i = 0; i < n; ++i) sum[i] += h[i];
+                }
+            }));
         if (n) FGI_HIP(g, hipMemcpyAsync(dev, sum.data(), n * 4, hipMemcpyHostToDevice, g->stream));
         FGI_HIP(g, hipStreamSynchronize(g->stream));
         return FGI_OK;
     }
-    fgi_status allgather_words(fgi_graph* g, const uint64_t* mine, uint32_t words, uint64_t* all) override {
-        const size_t W = grp->gs.size();
-        {
-            std::lock_guard<std::mutex> lk(grp->mu);
-            for (uint32_t i = 0; i < words; ++i) grp->vals[(size_t)rank * kPartRedMax + i] = mine[i];
-        }
-        if (!grp->arrive()) return peer_failed(g);
-        for (size_t q = 0; q < W; ++q)
-            for (uint32_t i = 0; i < words; ++i) all[q * words + i] = grp->vals[q * kPartRedMax + i];
-        if (!grp->arrive()) return peer_failed(g);   // nobody overwrites vals before all have read them
-        return FGI_OK;
+    fgi_status allgather_dev(fgi_graph* g, const void* src, void* dst, uint64_t bytes) override {
+        return exchange_dev(g, src, nullptr, false, [&]() -> fgi_status {
+            for (size_t q = 0; q < grp->gs.size(); ++q)
+                FGI_HIP(g, hipMemcpyAsync(static_cast<char*>(dst) + q * bytes, grp->xsrc[q], bytes, hipMemcpyDefault, g->stream));
+            return FGI_OK;
+        });
     }
-    // device copies out of the senders' buffers, between two barriers (as exchange_delta)
-    fgi_status alltoallv(fgi_graph* g, const void* src, const uint64_t* soff, const uint64_t* sbytes, void* dst,
-                         const uint64_t* roff, const uint64_t* rbytes) override {
-        (void)sbytes;
-        const size_t W = grp->gs.size();
-        FGI_HIP(g, hipStreamSynchronize(g->stream));   // this rank's source is complete
-        {
-            std::lock_guard<std::mutex> lk(grp->mu);
-            grp->xsrc[rank] = static_cast<const char*>(src);
-            for (size_t q = 0; q < W; ++q) grp->xoff[rank * W + q] = soff[q];
-        }
-        if (!grp->arrive()) return peer_failed(g);
-        for (size_t q = 0; q < W; ++q)
-            if (rbytes[q])
-                FGI_HIP(g, hipMemcpyAsync(static_cast<char*>(dst) + roff[q], grp->xsrc[q] + grp->xoff[q * W + rank], rbytes[q],
+    fgi_status alltoall_dev(fgi_graph* g, const void* src, void* dst, uint64_t bytes) override {
+        return exchange_dev(g, src, nullptr, false, [&]() -> fgi_status {
+            for (size_t q = 0; q < grp->gs.size(); ++q)
+                FGI_HIP(g, hipMemcpyAsync(static_cast<char*>(dst) + q * bytes, grp->xsrc[q] + rank * bytes, bytes,
                                           hipMemcpyDefault, g->stream));
-        FGI_HIP(g, hipStreamSynchronize(g->stream));
-        if (!grp->arrive()) return peer_failed(g);     // the senders keep their buffers until every copy is done
-        return FGI_OK;
+            return FGI_OK;
+        });
+    }
+    fgi_status alltoallv(fgi_graph* g, const void* src, const uint64_t* soff, const uint64_t*, void* dst, const uint64_t* roff,
+                         const uint64_t* rbytes, uint64_t, bool, const char*) override {
+        // Always the host-waiting form: its callers' hosts have just waited for the counts, and at 8 ranks the
+        // marks' 2 x 7 stream waits per rank cost a host-driven level more than the two short waits do
+        // (profiles/part_transport_ab.txt).
+        const size_t W = grp->gs.size();
+        return exchange_dev(g, src, soff, true, [&]() -> fgi_status {
+            for (size_t q = 0; q < W; ++q)
+                if (rbytes[q])
+                    FGI_HIP(g, hipMemcpyAsync(static_cast<char*>(dst) + roff[q], grp->xsrc[q] + grp->xoff[q * W + rank],
+                                              rbytes[q], hipMemcpyDefault, g->stream));
+            return FGI_OK;
+        });
     }
 };
 
+// ---- the protocols, once, above the transport -----------------------------------------------------
+// This level's forwarded targets: send_buf[q] (send_cnt[q] entries) to owner q; the targets received from
+// every other rank are concatenated at recv_buf (stream-ordered: the level's apply kernel reads them).
+// send_cnt[world, world + 1] carry the rank's local {F, T} of the next level, summed with the targets
+// sent by all ranks into glob = {sum F, sum T, sum sent} on the way: the count all-gather doubles as the
+// level's all-reduce, so a push level waits for the host once (the gather).
 fgi_status part_exchange(fgi_graph* g, uint64_t* n_recv, uint64_t* n_sent, uint64_t* glob) {
-    return ps(g)->ops->exchange(g, n_recv, n_sent, glob);
+    PartState* p = ps(g);
+    const uint32_t W = p->v.world, R = p->v.rank, S = W + 2;
+    uint64_t c[8 * 10];   // c[q * S + r]: sent by q to r; c[q * S + W + i]: q's F, T
+    FGI_TRY(p->ops->gather_words(g, p->v.send_cnt, true, S, c, "all-gather of the push level's counts"));
+    sum_counts(c, W, glob);
+    uint64_t soff[8], sb[8], roff[8], rb[8], recv = 0, sent = 0, mx = 0;
+    for (uint32_t q = 0; q < W; ++q) {
+        soff[q] = (uint64_t)q * p->v.block * 4;
+        sb[q] = q == R ? 0 : c[(size_t)R * S + q] * 4;
+        roff[q] = recv * 4;
+        rb[q] = q == R ? 0 : c[(size_t)q * S + R] * 4;
+        recv += rb[q] / 4;
+        sent += sb[q] / 4;
+        for (uint32_t r = 0; r < W; ++r)
+            if (r != q) mx = std::max(mx, c[(size_t)q * S + r] * 4);
+    }
+    FGI_TRY(p->ops->alltoallv(g, p->v.send_buf, soff, sb, p->v.recv_buf, roff, rb, mx, false,
+                              "exchange of a push level's targets"));
+    *n_recv = recv;
+    *n_sent = sent;
+    return FGI_OK;
 }
 
-fgi_status part_allgather_front_async(fgi_graph* g) {
+// every rank's local invalidated-bitmap words inv_bm[0, block/32) into front_global, stream-ordered
+// (the planned waves' frontier exchange; part_allgather_front's full mode)
+fgi_status part_allgather_front_full(fgi_graph* g) {
     PartState* p = ps(g);
     ++p->front_full;
     p->front_bytes += (uint64_t)(p->v.world - 1) * p->v.block / 8;
-    return p->ops->allgather_front_async(g);
+    return p->ops->allgather_dev(g, g->inv_bm, p->v.front_global, (uint64_t)(p->v.block / 32) * 4);
 }
 
-fgi_status part_alltoall_async(fgi_graph* g) { return ps(g)->ops->alltoall_async(g); }
+// a2a_send[q * C, + C) to rank q, into a2a_recv[r * C, + C) from every rank r (stream-ordered)
+fgi_status part_alltoall_async(fgi_graph* g) {
+    PartState* p = ps(g);
+    return p->ops->alltoall_dev(g, p->a2a_send, p->a2a_recv, (uint64_t)p->a2a_C * 4);
+}
 
 fgi_status part_allreduce_u32(fgi_graph* g, uint32_t* dev, uint64_t n) { return ps(g)->ops->allreduce_u32(g, dev, n); }
 
@@ -968,19 +834,24 @@ fgi_status part_cur_buffers(fgi_graph* g, unsigned long long** local, unsigned l
     return FGI_OK;
 }
 
-fgi_status part_allgather_cur(fgi_graph* g) { return ps(g)->ops->allgather_cur_async(g); }
+fgi_status part_allgather_cur(fgi_graph* g) {
+    PartState* p = ps(g);
+    return p->ops->allgather_dev(g, p->cur_local, p->cur_all, p->cur_w64 * 8);
+}
 
 // the sharded loads' collectives (shard.hip)
 fgi_status part_allgather_words(fgi_graph* g, const uint64_t* mine, uint32_t words, uint64_t* all) {
     if (words < 1 || words > kShardWords) return set_err(g, FGI_EINVAL, "part_allgather_words: %u words", words);
-    return ps(g)->ops->allgather_words(g, mine, words, all);
+    return ps(g)->ops->gather_words(g, reinterpret_cast<const unsigned long long*>(mine), false, words, all,
+                                    "all-gather of a sharded load's counts");
 }
 fgi_status part_allgatherv(fgi_graph* g, const void* src, const uint64_t* bytes, void* dst) {
     return ps(g)->ops->allgatherv(g, src, bytes, dst);
 }
 fgi_status part_alltoallv(fgi_graph* g, const void* src, const uint64_t* soff, const uint64_t* sbytes, void* dst,
                           const uint64_t* roff, const uint64_t* rbytes) {
-    return ps(g)->ops->alltoallv(g, src, soff, sbytes, dst, roff, rbytes);
+    return ps(g)->ops->alltoallv(g, src, soff, sbytes, dst, roff, rbytes, kPairUnknown, true,
+                                 "variable-size exchange of a sharded load");
 }
 uint32_t* part_weight(fgi_graph* g) { return ps(g)->weight; }
 
@@ -1076,33 +947,38 @@ __global__ void k_front_apply(uint64_t n, const uint64_t* __restrict__ rbuf, uin
 fgi_status part_allgather_front(fgi_graph* g) {
     PartState* p = ps(g);
     const int mode = g->opt_front_exchange;
-    if (mode == 1) {
-        ++p->front_full;
-        p->front_bytes += (uint64_t)(p->v.world - 1) * p->v.block / 8;
-        return p->ops->allgather_front(g);
-    }
+    if (mode == 1) return part_allgather_front_full(g);
     hipStream_t s = g->stream;
-    const uint32_t words = p->v.block / 32, W = p->v.world;
+    const uint32_t words = p->v.block / 32, W = p->v.world, R = p->v.rank;
     FGI_HIP(g, hipMemsetAsync(p->dcnt, 0, 8, s));
     hipLaunchKernelGGL(k_front_delta, dim3((words + 255) / 256), dim3(256), 0, s, words, g->inv_bm,
                        p->v.front_global + (uint64_t)p->v.rank * words, p->v.rank * words, p->dbuf, p->dcnt);
     FGI_HIP(g, hipGetLastError());
-    uint64_t mine = 0;
+    unsigned long long mine = 0;
     FGI_HIP(g, hipMemcpyAsync(&mine, p->dcnt, 8, hipMemcpyDeviceToHost, s));
     FGI_HIP(g, hipStreamSynchronize(s));
     uint64_t cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    FGI_TRY(p->ops->allgather_count(g, mine, cnt));
+    FGI_TRY(p->ops->gather_words(g, &mine, false, 1, cnt, "all-gather of a count"));
     uint64_t total = 0;
     for (uint32_t q = 0; q < W; ++q) total += cnt[q];
     const uint64_t full_bytes = (uint64_t)(W - 1) * words * 4;
     if (mode == 0 && 8 * total >= full_bytes) {   // dense: the plain all-gather moves fewer bytes
         ++p->front_full;
         p->front_bytes += full_bytes;
-        return p->ops->allgather_front(g);
+        return p->ops->allgather_dev(g, g->inv_bm, p->v.front_global, (uint64_t)words * 4);
     }
     ++p->front_delta;
-    uint64_t n_recv = 0;
-    FGI_TRY(p->ops->exchange_delta(g, cnt, &n_recv));
+    // every rank's list dbuf[0, cnt[rank]) to every other rank, concatenated at rbuf (self skipped)
+    uint64_t soff[8], sb[8], roff[8], rb[8], n_recv = 0, mx = 0;
+    for (uint32_t q = 0; q < W; ++q) {
+        soff[q] = 0;
+        sb[q] = q == R ? 0 : cnt[R] * 8;
+        roff[q] = n_recv * 8;
+        rb[q] = q == R ? 0 : cnt[q] * 8;
+        n_recv += rb[q] / 8;
+        if (W > 1) mx = std::max(mx, cnt[q] * 8);
+    }
+    FGI_TRY(p->ops->alltoallv(g, p->dbuf, soff, sb, p->rbuf, roff, rb, mx, false, "exchange of the frontier's delta lists"));
     p->front_bytes += 8 * n_recv;
     if (n_recv)
         hipLaunchKernelGGL(k_front_apply, dim3((uint32_t)((n_recv + 255) / 256)), dim3(256), 0, s, n_recv, p->rbuf,
@@ -1355,7 +1231,7 @@ __global__ void k_pc_move_global(uint32_t N, const uint32_t* __restrict__ gc, co
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= N) return;
     const uint32_t c = gc[x];
-    ver[c] = ver_old[x];
+    if (ver) ver[c] = ver_old[x];   // null: the weights only
     w[c] = w_old[x];
 }
 // local handles <-> local code indices (owned range only), in place
@@ -1437,10 +1313,13 @@ fgi_status part_codes_choose(fgi_graph* g, uint32_t* weight_dev) {
             st = set_err(g, FGI_ENOMEM, "partition code moves");
             break;
         }
-        hipMemcpyAsync(ver_old, p->v.ver_all, (size_t)N * 8, hipMemcpyDeviceToDevice, s);
-        hipMemcpyAsync(w_old, weight_dev, (size_t)N * 4, hipMemcpyDeviceToDevice, s);
-        hipMemcpyAsync(node_old, g->node, (size_t)nl * 8, hipMemcpyDeviceToDevice, s);
-        hipMemcpyAsync(used_old, g->used_cnt, (size_t)nl * 4, hipMemcpyDeviceToDevice, s);
+        if (hipMemcpyAsync(ver_old, p->v.ver_all, (size_t)N * 8, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(w_old, weight_dev, (size_t)N * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+            (nl && hipMemcpyAsync(node_old, g->node, (size_t)nl * 8, hipMemcpyDeviceToDevice, s) != hipSuccess) ||
+            (nl && hipMemcpyAsync(used_old, g->used_cnt, (size_t)nl * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)) {
+            st = set_err(g, FGI_EDEVICE, "partition code moves");
+            break;
+        }
         hipLaunchKernelGGL(k_pc_move_global, dim3(nblk(N)), dim3(256), 0, s, N, g->pg_gc, ver_old, p->v.ver_all, w_old,
                            weight_dev);
         if (nl)
@@ -1732,7 +1611,7 @@ static fgi_status part_alloc(fgi_graph* g, uint32_t n_global) {
     if (hipMalloc(&p->v.send_buf, (size_t)W * block * 4) != hipSuccess) return fail("send buffer");
     if (hipMalloc(&p->v.recv_buf, (size_t)W * block * 4) != hipSuccess) return fail("recv buffer");
     if (hipMalloc(&p->v.send_cnt, (size_t)(W + 2) * 8) != hipSuccess) return fail("counts");
-    if (hipMalloc(&p->all_cnt, (size_t)W * (W + 2) * 8) != hipSuccess) return fail("counts");
+    if (hipMalloc(&p->gw, (size_t)(1 + W) * kPartRedMax * 8) != hipSuccess) return fail("counts");
     if (hipMalloc(&p->scalar, 32) != hipSuccess) return fail("scalar");
     // even, so the hot heads' snapshot past its end (kHot / 32 words, build_candidates) is 64-bit aligned
     p->v.front_words_global = ((uint64_t)n_global / 32 + 3) & ~1ull;
@@ -1749,7 +1628,7 @@ static fgi_status part_alloc(fgi_graph* g, uint32_t n_global) {
         hipMalloc(&p->dcnt, 8) != hipSuccess)
         return fail("frontier delta buffers");
     if (hipMemset(p->weight, 0, (size_t)n_global * 4) != hipSuccess) return fail("list weights");
-    if (hipHostMalloc(reinterpret_cast<void**>(&p->all_cnt_host), (size_t)W * (W + 2) * 8) != hipSuccess)
+    if (hipHostMalloc(reinterpret_cast<void**>(&p->gw_host), (size_t)(1 + W) * kPartRedMax * 8) != hipSuccess)
         return fail("host");
     if (hipHostMalloc(reinterpret_cast<void**>(&p->scalar_host), 32) != hipSuccess) return fail("host");
     // planned waves: buckets of a2a_C words per peer (a push level's forwarded targets beyond that wait
@@ -1996,14 +1875,19 @@ fgi_status fgi_part_synth_rmat(fgi_graph* g, uint32_t scale, uint32_t edge_facto
                 st = set_err(g, FGI_ENOMEM, "weights");
                 break;
             }
-            hipMemcpyAsync(w2, p->weight, (size_t)N * 4, hipMemcpyDeviceToDevice, s);
-            hipLaunchKernelGGL(k_pc_move_global, dim3(nblk(N)), dim3(256), 0, s, N, (const uint32_t*)g->pg_gc,
-                               (const uint64_t*)p->v.ver_all, p->v.ver_all, (const uint32_t*)w2, p->weight);
-            hipStreamSynchronize(s);
+            hipError_t e = hipMemcpyAsync(w2, p->weight, (size_t)N * 4, hipMemcpyDeviceToDevice, s);
+            // the weights only: ver_all was written at the codes above
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(k_pc_move_global, dim3(nblk(N)), dim3(256), 0, s, N, (const uint32_t*)g->pg_gc,
+                                   (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)w2, p->weight);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
             hipFree(w2);
-            // k_pc_move_global also moved ver_all: write it again at the codes
-            hipLaunchKernelGGL(k_versions_all, dim3((N + 255) / 256), dim3(256), 0, s, N, seed, p->v.ver_all,
-                               (const uint32_t*)g->pg_ig);
+            if (e != hipSuccess) {
+                st = hip_check(g, e, "weights into code order");
+                break;
+            }
         }
         std::vector<unsigned long long> hc(2 * kGenBlocks), ho(2 * kGenBlocks);
         if (hipMemcpyAsync(hc.data(), cnt, hc.size() * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||

@@ -4568,7 +4568,7 @@ static fgi_status run_part_planned(fgi_graph* g, const PartView& pv, const WaveP
             const int buf = L & 1;
             if (pull) {
                 FGI_TRY(part_pull_begin(g, pv, pl, L));
-                if (coll) FGI_TRY(part_allgather_front_async(g));
+                if (coll) FGI_TRY(part_allgather_front_full(g));
             }
             FGI_TRY(launch_part_level(g, pv, pl, wp, L, timing ? &g->ev[2 * (L - L0)] : nullptr));
             if (!pull && coll) {

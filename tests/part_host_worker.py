@@ -19,6 +19,21 @@ WAVES = [(48, 0x5EED1027), (16, 99), (48, 0x5EED1027)]
 MIX = dict(hubs=64, leaves=40, per_round=8, delay_pct=10, seed=0x5EED00E0, rounds=5)
 
 
+def one_way_graph():
+    """3 x 64 slots for 3 ranks; every edge leads from a slot of rank 0 to a slot of rank 2 (pairs of slots
+    share a target, a third of the edges are stale); the roots are rank 0's. So rank 1 sends and receives
+    nothing in any exchange, rank 2 receives from rank 0 only and rank 0 receives nothing.
+    Returns n, versions, used, dependant, tags, roots."""
+    block, n = 64, 192
+    versions = (np.arange(n, dtype=np.uint64) + 1) * 3
+    u = np.repeat(np.arange(block, dtype=np.uint32), 3)
+    k = np.tile(np.arange(3, dtype=np.uint32), block)
+    d = (2 * block + np.choose(k, [5 * u, 3 * (u // 2) + 1, u + 9]) % block).astype(np.uint32)
+    t = versions[d].copy()
+    t[k == 2] += 1
+    return n, versions, u, d, t, np.arange(16, dtype=np.uint32)
+
+
 def mix_schedule(W):
     """The streaming mix's batches (test_gpu_part_mutations.py's schedule), as (kind, args...) steps."""
     mix = W.StreamMix(MIX["hubs"], MIX["leaves"], MIX["per_round"], MIX["delay_pct"], MIX["seed"])
@@ -41,7 +56,7 @@ def mix_schedule(W):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenario", required=True, choices=["rmat", "mix"])
+    ap.add_argument("--scenario", required=True, choices=["rmat", "mix", "oneway"])
     ap.add_argument("--out", required=True)
     ap.add_argument("--stale", type=int, default=0)
     ap.add_argument("--bucket", type=int, default=0)
@@ -80,6 +95,26 @@ def main():
             res[f"w{w}_stats"] = np.array([st.v_inv, st.e_trav, st.levels, st.host_syncs, st.pull_levels], np.uint64)
             v, f = g.dump_states()
             res[f"w{w}_ver"], res[f"w{w}_flags"] = v, f
+    elif args.scenario == "oneway":
+        n, versions, used, dep, tag, roots = one_way_graph()
+        block = -(-n // world)
+        d_roots = torch.from_numpy(roots.astype(np.int32)).cuda()
+        # push only, then (a fresh graph) pull only with the delta frontier exchange
+        for key, direction, front in (("push", 1, 0), ("pull", 2, 2)):
+            g = pkg.Graph(block, rank=rank, world=world)
+            g.part_init_host(n)
+            g.set_option(pkg.fgi.OPT_DIRECTION, direction)
+            g.set_option(pkg.fgi.OPT_FRONT_EXCHANGE, front)
+            g.part_register_nodes(np.arange(n, dtype=np.uint32), versions)
+            g.part_load_edges(used, dep, tag)
+            st = pkg.WaveStats()
+            g.part_invalidate(len(roots), d_roots.data_ptr(), 0, st)
+            res[f"{key}_ids"] = g.part_export_ids()
+            full, delta, _ = g.part_front_stats()
+            res[f"{key}_stats"] = np.array([st.v_inv, st.remote_msgs, full, delta], np.uint64)
+            res[f"{key}_ver"], res[f"{key}_flags"] = g.dump_states()
+            if key == "push":
+                g.close()
     else:
         mix = W.StreamMix(MIX["hubs"], MIX["leaves"], MIX["per_round"], MIX["delay_pct"], MIX["seed"])
         n = mix.n

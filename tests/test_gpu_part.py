@@ -64,6 +64,47 @@ def test_partitioned_wave_matches_oracle(pkg, gpu_available, P, stale, direction
     assert np.array_equal(np.sort(ids2), np.sort(o.inv_log()))
 
 
+@pytest.mark.parametrize("direction,front", [(1, "auto"), (2, "delta")])
+def test_one_way_graph_exchanges_with_empty_pairs(pkg, gpu_available, direction, front):
+    """part_host_worker.one_way_graph on an in-process group of 3: every variable-size exchange of the wave
+    has pairs of ranks that move nothing. Push only: rank 0 forwards to rank 2, rank 1 neither sends nor
+    receives. Pull only with delta frontier lists: the lists of ranks 1 and 2 are empty in the first level."""
+    from part_host_worker import one_way_graph
+    n, versions, used, dep, tag, roots = one_way_graph()
+    P, block = 3, 64
+    gs = [pkg.Graph(block, rank=r, world=P) for r in range(P)]
+    pkg.fgi.part_init_local(gs, n)
+    for g in gs:
+        g.set_option(pkg.fgi.OPT_DIRECTION, direction)
+        g.set_option(pkg.fgi.OPT_FRONT_EXCHANGE, FRONT[front])
+        g.part_register_nodes(np.arange(n, dtype=np.uint32), versions)
+        g.part_load_edges(used, dep, tag)
+    o = O.Oracle(n)
+    o.load_graph(versions, None, used, dep, tag)
+    st = o.invalidate_slots(roots)
+    want = np.sort(o.inv_log())
+    stats = pkg.fgi.part_local_invalidate(gs, roots)
+    ids = [g.part_export_ids() for g in gs]
+    assert np.array_equal(np.sort(np.concatenate(ids)), want)
+    assert np.array_equal(np.sort(ids[0]), roots) and len(ids[1]) == 0
+    targets = int((want >= 2 * block).sum())   # the distinct matched targets: all rank 2's, none has dependants
+    assert len(ids[2]) == targets > 0
+    assert sum(x.v_inv for x in stats) == st.v_inv and sum(x.e_trav for x in stats) == st.e_trav
+    if direction == 1:
+        assert [x.remote_msgs for x in stats] == [targets, 0, 0]
+    else:
+        assert all(x.pull_levels == x.levels for x in stats)
+        full, delta, _ = gs[0].part_front_stats()
+        assert full == 0 and delta > 0
+    ov, of = o.dump_states()
+    for r, g in enumerate(gs):
+        v, f = g.dump_states()
+        assert np.array_equal(v[:block], ov[r * block:(r + 1) * block])
+        assert np.array_equal(f[:block], of[r * block:(r + 1) * block])
+        g.close()
+    o.close()
+
+
 def test_partition_owns_rows_of_its_slots(pkg, gpu_available):
     scale, ef, seed, P = 10, 8, 7, 4
     n = 1 << scale

@@ -86,6 +86,30 @@ def test_rmat_waves_across_processes(gpu_available, tmp_path, P, stale, bucket, 
     o.close()
 
 
+def test_one_way_graph_across_processes(gpu_available, tmp_path):
+    """part_host_worker.one_way_graph in 3 processes: the variable-size exchange's padded all-gather with
+    rows that are all empty (rank 1, and every rank but 0 as a sender), with the pair sizes known from the
+    counts (a push level's targets, the delta frontier lists of a pull level). The sharded loads'
+    exchanges, which do not know them, are test_gpu_part_shard_host.py's."""
+    ranks = _launch(3, tmp_path, "--scenario", "oneway")
+    n, versions, used, dep, tag, roots = PW.one_way_graph()
+    for key in ("push", "pull"):
+        o = O.Oracle(n)
+        o.load_graph(versions, None, used, dep, tag)
+        st = o.invalidate_slots(roots)
+        want = np.sort(o.inv_log())
+        ids = np.concatenate([r[f"{key}_ids"] for r in ranks])
+        assert np.array_equal(np.sort(ids), want), key
+        assert sum(int(r[f"{key}_stats"][0]) for r in ranks) == st.v_inv
+        assert len(ranks[1][f"{key}_ids"]) == 0 and len(ranks[2][f"{key}_ids"]) == int((want >= 128).sum()) > 0
+        _states_match(ranks, key, *o.dump_states())
+        o.close()
+    # push only: rank 0 forwards each matched target once, nobody else forwards anything
+    assert [int(r["push_stats"][1]) for r in ranks] == [int((want >= 128).sum()), 0, 0]
+    # pull only: every frontier exchange was a delta exchange
+    assert all(int(r["pull_stats"][2]) == 0 and int(r["pull_stats"][3]) > 0 for r in ranks)
+
+
 @pytest.mark.parametrize("P", [2, 3])
 def test_streaming_batches_and_prune_across_processes(gpu_available, tmp_path, P):
     """BASELINE.json configs[4]'s schedule at 64 hubs x 40 leaves (10% delayed) through

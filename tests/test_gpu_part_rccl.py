@@ -54,6 +54,35 @@ def test_rccl_partition_world1_matches_oracle(pkg, gpu_available, stale, directi
 
 
 @pytest.mark.parametrize("collectives", [1, 0])
+def test_rccl_partition_world1_planned_wave(pkg, gpu_available, collectives):
+    """A repeated wave follows the plan its first run learnt: the levels' {F, T} ride on one all-reduce of
+    2 + 2 * levels words (the widest the transport sums), and the host waits for that one only (and, with
+    the collectives forced, for the start's all-reduce too)."""
+    scale, ef, seed = 12, 16, 0x5EED0027
+    n = 1 << scale
+    g = pkg.Graph(n, rank=0, world=1)
+    g.part_init(n, pkg.fgi.part_unique_id())
+    g.part_synth_rmat(scale, ef, seed, 0, 0)
+    g.set_option(pkg.fgi.OPT_PART_COLLECTIVES, collectives)
+    g.snapshot()
+    s, d = O.gen_rmat(scale, ef, seed)
+    o = O.Oracle(n)
+    o.load_graph(O.version_of(seed, np.arange(n)), None, s, d, O.gen_tags(s, d, seed))
+    roots = O.gen_roots(48, n, 0x5EED1027, np.bincount(s, minlength=n))
+    st = o.invalidate_slots(roots)
+    d_roots = torch.from_numpy(roots.astype(np.int32)).cuda()
+    for rep in range(2):
+        g.restore()
+        stats = pkg.fgi.WaveStats()
+        g.part_invalidate(len(roots), d_roots.data_ptr(), 0, stats)
+        assert np.array_equal(np.sort(g.part_export_ids()), np.sort(o.inv_log())), rep
+        assert (stats.v_inv, stats.e_trav) == (st.v_inv, st.e_trav), rep
+    assert stats.levels > 1 and stats.host_syncs == (2 if collectives else 1), stats.as_dict()
+    g.close()
+    o.close()
+
+
+@pytest.mark.parametrize("collectives", [1, 0])
 def test_rccl_partition_world1_mutations_match_oracle(pkg, gpu_available, collectives):
     """fgi_part_run_batch / fgi_part_invalidate_all / fgi_part_prune through a real RCCL communicator
     (world size 1): the add_used and begin_compute all-reduces, the cascades and the prune's
