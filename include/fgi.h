@@ -419,8 +419,8 @@ fgi_status fgi_invalidate_all(fgi_graph* g, uint32_t* out_ids, uint64_t cap, uin
  * (*out_n holds the count). The entries leave the table when the lists are made, not when they are copied.
  * n_peers must exceed every stored peer id (and be at most FGI_MAX_PEERS), else FGI_EINVAL and nothing is
  * removed. After fgi_restore, or before any wave: FGI_OK with 0 entries. After fgi_run_batch or an asynchronous
- * ticket: FGI_ENOTSUP (use fgi_fanout_ids). On a partitioned graph every call of this section returns
- * FGI_ENOTSUP; on a poisoned graph FGI_ESTATE.
+ * ticket: FGI_ENOTSUP (use fgi_fanout_ids). On a partitioned graph these four calls return FGI_ENOTSUP (each
+ * rank has its own: the fgi_part_* section below); on a poisoned graph FGI_ESTATE.
  * A host that subscribes takes the fan-out of every wave before it begins a new computation on an invalidated
  * slot: an entry left on a slot whose node a wave invalidated would otherwise fire with the next node there.
  * fgi_fanout_ids is the same join for any strictly ascending handle list the host already holds (a batch's
@@ -460,6 +460,62 @@ typedef struct fgi_sub_stats {
     double last_kernel_ms;
 } fgi_sub_stats;
 fgi_status fgi_sub_stats_get(fgi_graph* g, fgi_sub_stats* out);
+
+/* ---- replica fan-out per rank of a partition (C-ABI 0.10) ------------------------------------------ */
+/* The same subscriptions (RpcInboundComputeCall.cs:53-62, 102-106; ComputedExt.WhenInvalidated,
+ * ComputedExt.cs:99-125) on a partitioned graph: each rank keeps the entries of the slots it owns and returns
+ * its own share of a wave's fan-out in the host's numbering. Every call here is rank-local: none joins a
+ * collective, and a rank may call them at any time and in any order, as fgi_part_last_wave_ids. On a graph
+ * that is not partitioned they return FGI_ENOTSUP (use the call of the section above), on a poisoned graph
+ * FGI_ESTATE. fgi_sub_stats_get reads a rank's table as it is. The contract is the section above's, per rank,
+ * with these differences.
+ * fgi_part_subscribe: slots are global ids in the host's numbering (partition codes are never visible). A slot
+ * >= n_global or a peer >= FGI_MAX_PEERS returns FGI_EINVAL and stores nothing. A slot this rank does not own
+ * gets FGI_SUB_NOT_OWNED and is not stored, so a host may hand every rank the same list or each rank its share.
+ * An owned slot that is empty or Invalidated gets FGI_SUB_INVALIDATED; anything else is stored under the local
+ * handle slot - rank * block and gets FGI_SUB_ADDED. The state is the node's as it stands after the rank's last
+ * wave (its node word and visit bit, what the rank's state view reports): no fold, no pass over the graph, and
+ * fgi_part_last_wave_ids / _bits and fgi_part_last_flagged answer as before the call. Detached handles cannot be
+ * subscribed to: a partition addresses slots.
+ * fgi_part_last_wave_fanout returns the entries of every owned slot the rank's last wave invalidated. It is
+ * valid exactly where fgi_part_last_wave_ids is, until the rank's next call that runs a cascade or a fan-out,
+ * or fgi_restore. slots[i] is the global slot whose invalidation released call_ids[i]; within a peer the order
+ * is ascending slot. The lists are made once per wave: a second call returns the same arrays, and so does a
+ * retry after FGI_ECAPACITY (*out_n holds the count; the entries have left the table). n_peers at or below a
+ * stored peer id: FGI_EINVAL, nothing is removed. After fgi_part_begin_compute, fgi_part_set_output or
+ * fgi_part_run_batch: FGI_ENOTSUP (pass their ids to fgi_part_fanout_ids). Before any wave and after
+ * fgi_restore: FGI_OK with 0 entries. A rank whose share of the wave is empty launches nothing.
+ * fgi_part_fanout_ids is the same join for a strictly ascending list of global slots (an entry >= n_global or a
+ * list that does not ascend: FGI_EINVAL). Slots the rank does not own are skipped on the device, so one
+ * cascade's share of fgi_part_run_batch's or fgi_part_local_run_batch's out_ids can be passed as it is. A short
+ * cap returns FGI_ECAPACITY with *out_n set and removes nothing.
+ * Entries follow the node: where fgi_part_begin_compute, directly or as a batch's step, hands out a detached
+ * handle on the owner (out_detached[i] != FGI_NONE), the slot's entries move to that local detached handle and
+ * never fire with the slot's next node. No partitioned cascade reaches a detached node (a partition's roots
+ * are slots), so those entries leave in three ways only: through fgi_part_fanout_detached when the host ends
+ * the displaced node itself (its delay timer, its own TrySetOutput) - handles: this rank's detached handles,
+ * strictly ascending, within [n_slots, n_slots + n_detached), else FGI_EINVAL; handles_out[i] is the detached
+ * handle that released call_ids[i] -, through fgi_release, which drops them (fgi_sub_stats.dropped), and
+ * through fgi_part_unsubscribe_peer.
+ * FGI_OPT_FANOUT_PATH on a partition: 1 the rank's ascending id list (made if absent), 2 the bitmap form (the
+ * host-order bitmap if fgi_part_last_wave_bits made it; else, with partition codes, the wave's bitmap probed at
+ * the subscribed handles only; else the wave's bitmap in place), 0 the list if the rank's ascending ids already
+ * stand, else the bitmap form. 3 is for measurement: the bitmap form with the host-order bitmap made inside the
+ * call (the gather or scatter of fgi_part_last_wave_bits), the form the probe replaces; on a single device it is
+ * 2. Results never depend on it. */
+#define FGI_SUB_NOT_OWNED 2u
+fgi_status fgi_part_subscribe(fgi_graph* g, uint32_t n, const uint32_t* slot /*global*/, const uint32_t* peer,
+                              const uint64_t* call_id, uint32_t* out_result /*nullable*/);
+fgi_status fgi_part_last_wave_fanout(fgi_graph* g, uint32_t n_peers, uint64_t* peer_off /*n_peers+1*/,
+                                     uint64_t* call_ids /*nullable*/, uint32_t* slots /*nullable*/,
+                                     uint64_t cap, uint64_t* out_n);
+fgi_status fgi_part_fanout_ids(fgi_graph* g, uint64_t n, const uint32_t* slots_in /*host, global, strictly ascending*/,
+                               uint32_t n_peers, uint64_t* peer_off, uint64_t* call_ids, uint32_t* slots,
+                               uint64_t cap, uint64_t* out_n);
+fgi_status fgi_part_fanout_detached(fgi_graph* g, uint64_t n, const uint32_t* handles /*host, this rank's detached
+                               local handles, strictly ascending*/, uint32_t n_peers, uint64_t* peer_off,
+                               uint64_t* call_ids, uint32_t* handles_out, uint64_t cap, uint64_t* out_n);
+fgi_status fgi_part_unsubscribe_peer(fgi_graph* g, uint32_t peer, uint64_t* out_dropped /*nullable*/);
 
 /* ---- streaming batches (BASELINE.json configs[4]) ------------------------------- */
 /* One step of a batch: the arguments of the matching single call. */
@@ -637,7 +693,7 @@ fgi_status fgi_stream(fgi_graph* g, void** stream);
  *   FGI_OPT_FANOUT_PATH [0]  which form of the invalidated set a fan-out joins with the subscriptions: 0 by what
  *                            the wave left (its kept bitmap, else its id list), 1 the id list, 2 the bitmap
  *                            (made from the list if the wave kept none). Results never depend on it (tests pin
- *                            both paths).
+ *                            both paths). On a partition: the fgi_part_* section; 3 there is a measurement form.
  *   FGI_OPT_RUN_OFFSET_BITS [28] tests only: a pull candidate's record names its tail run by an offset
  *                            below 2^bits words from its pull block's base; a candidate past that is
  *                            found through the per-slot list offsets instead (tests pin that path on

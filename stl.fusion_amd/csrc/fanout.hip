@@ -1,5 +1,7 @@
 // fanout.hip — the replica fan-out on the device (C-ABI 0.9): fgi_subscribe,
-// fgi_last_wave_fanout, fgi_fanout_ids, fgi_unsubscribe_peer, fgi_sub_stats_get.
+// fgi_last_wave_fanout, fgi_fanout_ids, fgi_unsubscribe_peer, fgi_sub_stats_get; and per rank of a partition
+// (C-ABI 0.10): fgi_part_subscribe, fgi_part_last_wave_fanout, fgi_part_fanout_ids, fgi_part_fanout_detached,
+// fgi_part_unsubscribe_peer, over the rank's own handles, sources and outputs in the host's numbering.
 //
 // The table (fgi::Fanout) chains 16-byte records {call id, peer, next} from a head per boundary handle, with
 // a has-entries bitmap beside it. A fan-out joins it with an invalidated set given as a bitmap over boundary
@@ -13,6 +15,7 @@
 //                64 handles are staged in LDS in handle order and emitted 64 at a time; the rank among lanes
 //                with the same peer comes from a ballot loop over the distinct peers present. What is
 //                delivered is unlinked, and record i of the output goes to the free stack at free_n + i.
+//   k_fo_probe   a partition rank with codes: inv & has in handle order, probed from the subscribed handles
 // No kernel waits on another block, and every chain walk is capped at the pool size: a longer chain sets an
 // error word and the call fails with FGI_ESTATE.
 // Everything is allocated at the first fgi_subscribe; a graph that never subscribes launches nothing here.
@@ -48,11 +51,18 @@ struct SubArgs {
     uint64_t free_n, bump, cap;
     unsigned long long* pcnt;
     unsigned long long* ctr;
+    // a partition rank (fgi_part_subscribe): handle[] holds global slots, of which the rank owns
+    // [base, base + n_local); gc: slot -> code, null without partition codes. No partition: all zero.
+    bool part;
+    uint32_t base, n_local;
+    const uint32_t* gc;
 };
 
 // One entry per thread. The node's state is its word and its visit bit: nothing is folded.
 // A stored entry takes record number i of the call (one atomic per wavefront): the free stack's top first,
 // then the never-used range; the host checked that n records are there.
+// On a partition rank the entry's handle is slot - base and its node sits at engine index gc[slot] - base
+// (view.hip's view_label); an entry of a slot the rank does not own writes its result and takes no record.
 __global__ __launch_bounds__(kFBlock) void k_sub_insert(SubArgs a) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63;
@@ -62,14 +72,26 @@ __global__ __launch_bounds__(kFBlock) void k_sub_insert(SubArgs a) {
         h = a.handle[i];
         p = a.peer[i];
         uint32_t l = h + a.K;
-        if (a.s2l && h < a.ext_slots) {
+        bool owned = true;
+        if (a.part) {   // (a partition has no hub-first labels, part_alloc drops them: K = 0, no s2l, as view_label)
+            const uint32_t slot = h;
+            h = slot - a.base;
+            owned = h < a.n_local;   // (a slot below base wraps past n_local)
+            l = h;
+            if (owned && a.gc) {
+                l = a.gc[slot] - a.base;
+                owned = l < a.n_local;   // a code stays in its owner's range (part_out.hip checks the same)
+            }
+        } else if (a.s2l && h < a.ext_slots) {
             const uint32_t hot = a.s2l[h];
             if (hot != FGI_NONE) l = hot;
         }
-        unsigned long long w = a.node[l];
-        if (a.vis && ((a.vis[l >> 5] >> (l & 31)) & 1u)) w = visited_word(w);
-        store = (w & kVMask) != 0 && word_state(w) != FGI_INVALIDATED;
-        if (a.result) a.result[i] = store ? FGI_SUB_ADDED : FGI_SUB_INVALIDATED;
+        if (owned) {
+            unsigned long long w = a.node[l];
+            if (a.vis && ((a.vis[l >> 5] >> (l & 31)) & 1u)) w = visited_word(w);
+            store = (w & kVMask) != 0 && word_state(w) != FGI_INVALIDATED;
+        }
+        if (a.result) a.result[i] = !owned ? FGI_SUB_NOT_OWNED : store ? FGI_SUB_ADDED : FGI_SUB_INVALIDATED;
     }
     const unsigned long long m = __ballot(store);
     if (!m) return;
@@ -98,7 +120,9 @@ struct FoArgs {
     const uint32_t* ids;             // list source
     uint64_t n_ids;
     uint64_t words;                  // bitmap words of the table
-    uint32_t n_handles;
+    uint32_t n_handles;              // handles that may join: the table's, or a partition rank's owned slots
+    uint32_t id_base;                // list source: an id's handle is id - id_base (a rank's first slot; else 0)
+    uint32_t hnd_base;               // added to a handle on its way out (a rank's slots leave as global ids)
     uint32_t per;
     uint32_t n_tiles, n_peers;
     uint32_t* head;
@@ -121,7 +145,7 @@ __device__ inline bool fo_lane(const FoArgs& a, uint32_t t, uint32_t gi, uint32_
     if (kList) {
         const uint64_t i = (uint64_t)t * a.per + (uint64_t)gi * 64 + lane;
         if (i >= a.n_ids) return false;
-        const uint32_t x = a.ids[i];
+        const uint32_t x = a.ids[i] - a.id_base;   // (an id below the base wraps past n_handles: not owned)
         *h = x;
         return x < a.n_handles && ((a.has[x >> 6] >> (x & 63)) & 1ull);
     }
@@ -293,7 +317,7 @@ __global__ __launch_bounds__(64) void k_fo_write(FoArgs a) {
                         const uint64_t pos = (uint64_t)base + __popcll(m & ((1ull << lane) - 1));
                         if (pos < a.out_n && a.free_n + pos < a.cap) {
                             a.out_call[pos] = call;
-                            a.out_hnd[pos] = hh;
+                            a.out_hnd[pos] = hh + a.hnd_base;
                             a.fstack[a.free_n + pos] = r;
                         } else {
                             atomicAdd(a.ctr + kCErrOut, 1ull);
@@ -311,12 +335,41 @@ __global__ __launch_bounds__(64) void k_fo_write(FoArgs a) {
     }
 }
 
-// an ascending handle list as a bitmap (zeroed first)
-__global__ __launch_bounds__(kFBlock) void k_fo_scatter(const uint32_t* ids, uint64_t n, uint32_t n_handles, unsigned long long* bits) {
+// an ascending id list as a bitmap over handles id - id_base (zeroed first)
+__global__ __launch_bounds__(kFBlock) void k_fo_scatter(const uint32_t* ids, uint64_t n, uint32_t id_base, uint32_t n_handles,
+                                                        unsigned long long* bits) {
     const uint64_t nthr = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += nthr) {
-        const uint32_t h = ids[i];
+        const uint32_t h = ids[i] - id_base;
         if (h < n_handles) atomicOr(bits + (h >> 6), 1ull << (h & 63));
+    }
+}
+
+// A partition rank's wave with codes, joined where the subscriptions are: inv64 is the wave's bitmap over
+// engine indices, has is over handles, and owned handle h sits at engine index gc[base + h] - base. A
+// wavefront per word x of has (grid-strided, wave-uniform trip count): a zero word stores 0; otherwise the
+// lanes whose has bit is set probe their handle's bit of inv64, and one ballot is the word inv & has in
+// handle order, stored whole by lane 0. The code table and the bitmap are read for subscribed handles only.
+__global__ __launch_bounds__(kFBlock) void k_fo_probe(const unsigned long long* __restrict__ inv64,
+                                                      const unsigned long long* __restrict__ has,
+                                                      const uint32_t* __restrict__ gc, uint32_t base, uint32_t n_local,
+                                                      unsigned long long* out, uint64_t words) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t x = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; x < words; x += nwaves) {   // wave-uniform
+        const unsigned long long hw = has[x];
+        if (!hw) {   // wave-uniform: every lane read the same word
+            if (lane == 0) out[x] = 0ull;
+            continue;
+        }
+        const uint64_t h = x * 64 + lane;
+        bool hit = false;
+        if (((hw >> lane) & 1ull) && h < n_local) {
+            const uint32_t e = gc[base + (uint32_t)h] - base;
+            hit = e < n_local && ((inv64[e >> 6] >> (e & 63)) & 1ull);
+        }
+        const unsigned long long w = __ballot(hit);
+        if (lane == 0) out[x] = w;   // the wavefront owns word x: a plain store of the whole word
     }
 }
 
@@ -434,7 +487,7 @@ fgi_status fan_create(fgi_graph* g) {
         fanout_destroy(g);
         return set_err(g, FGI_ENOMEM, "the subscription table of %u handles", g->ext_handles);
     }
-    for (int k = 0; k < 4; ++k)
+    for (int k = 0; k < 6; ++k)
         if (hipEventCreate(&f->ev[k]) != hipSuccess) {
             fanout_destroy(g);
             return set_err(g, FGI_EDEVICE, "the fan-out's timing events");
@@ -498,10 +551,18 @@ void account_dropped(Fanout* f) {
     f->dropped += d;
 }
 
+// how a source's ids and the table's handles relate (FoArgs): a single device joins the whole table as it is
+struct FoMap {
+    uint32_t n_handles, id_base, hnd_base;
+};
+inline FoMap whole_table(const fgi_graph* g) { return FoMap{g->ext_handles, 0u, 0u}; }
+// a partition rank's owned slots: sources in the host's numbering, handles leave as global slots
+inline FoMap owned_slots(const PartView& pv) { return FoMap{pv.n_local, pv.base, pv.base}; }
+
 // The join: the invalidated set as a bitmap (inv) or as n_ids ascending ids, against the table. *total: the
 // entries found. dry: count only (nothing leaves the table). The lists are left in out_call / out_hnd / off.
-fgi_status fan_join(fgi_graph* g, const unsigned long long* inv, const uint32_t* ids, uint64_t n_ids, uint32_t n_peers,
-                    uint64_t cap_or_all, const char* what, uint64_t* total, bool* wrote) {
+fgi_status fan_join(fgi_graph* g, const unsigned long long* inv, const uint32_t* ids, uint64_t n_ids, const FoMap& map,
+                    uint32_t n_peers, uint64_t cap_or_all, const char* what, uint64_t* total, bool* wrote) {
     Fanout* f = g->fan;
     hipStream_t s = g->stream;
     const bool list = inv == nullptr;
@@ -516,7 +577,9 @@ fgi_status fan_join(fgi_graph* g, const unsigned long long* inv, const uint32_t*
     a.ids = ids;
     a.n_ids = n_ids;
     a.words = f->words;
-    a.n_handles = g->ext_handles;
+    a.n_handles = map.n_handles;
+    a.id_base = map.id_base;
+    a.hnd_base = map.hnd_base;
     a.per = (uint32_t)(list ? gpt * 64 : gpt);
     a.n_tiles = n_tiles;
     a.n_peers = n_peers;
@@ -603,6 +666,121 @@ fgi_status fan_usable(fgi_graph* g, const char* what) {
     if (g->aw[0].busy || g->aw[1].busy) FGI_TRY(drain_async(g));
     return FGI_OK;
 }
+// and every fgi_part_* one: a rank's own table, no collective (a partition runs no asynchronous waves, so
+// there is nothing to drain). single: the call that serves a graph on one device.
+fgi_status part_fan_usable(fgi_graph* g, const char* what, const char* single, PartView* pv) {
+    if (!g->part || !part_view(g, pv)) return set_err(g, FGI_ENOTSUP, "%s: not a partitioned graph (%s)", what, single);
+    if (g->failed) return set_err(g, FGI_ESTATE, "%s: the graph is poisoned; fgi_restore or fgi_destroy", what);
+    hipSetDevice(g->device);
+    return FGI_OK;
+}
+
+// fgi_subscribe and fgi_part_subscribe behind their checks. pv: the rank's ranges, null on a single device.
+fgi_status sub_insert(fgi_graph* g, const char* what, uint32_t n, const uint32_t* handle, const uint32_t* peer,
+                      const uint64_t* call_id, uint32_t* out_result, const PartView* pv) {
+    FGI_TRY(fan_create(g));
+    FGI_TRY(fan_reserve(g, n));
+    FGI_TRY(flush_vis(g));   // fgi_restore may have left the visit bitmap's clearing to the next wave
+    Fanout* f = g->fan;
+    hipStream_t s = g->stream;
+    // the upload: handles, peers, results (4 B each), then the call ids
+    const uint64_t words32 = 3ull * n + 2ull * n + 2;
+    FGI_TRY(grow(g, &f->ids, &f->ids_cap, std::max<uint64_t>(words32, 4096), "subscription upload"));
+    uint32_t* dh = f->ids;
+    uint32_t* dp = dh + n;
+    uint32_t* dr = dp + n;
+    unsigned long long* dc = reinterpret_cast<unsigned long long*>(f->ids + ((3ull * n + 1) & ~1ull));
+    FGI_HIP(g, hipMemcpyAsync(dh, handle, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    FGI_HIP(g, hipMemcpyAsync(dp, peer, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    FGI_HIP(g, hipMemcpyAsync(dc, call_id, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    FGI_HIP(g, hipMemsetAsync(f->ctr, 0, kCWords * 8, s));
+    SubArgs a{};
+    a.n = n;
+    a.handle = dh;
+    a.peer = dp;
+    a.call = dc;
+    a.result = out_result ? dr : nullptr;
+    a.node = reinterpret_cast<const unsigned long long*>(g->node);
+    a.vis = g->v_dirty && !g->vis_stale ? g->vis_bm : nullptr;
+    a.s2l = g->lbl_hot ? g->s2l : nullptr;
+    a.ext_slots = g->ext_slots;
+    a.K = g->lbl_K;
+    a.head = f->head;
+    a.has = f->has;
+    a.rec = f->rec;
+    a.fstack = f->fstack;
+    a.free_n = f->free_n;
+    a.bump = f->bump;
+    a.cap = f->cap;
+    a.pcnt = f->pcnt;
+    a.ctr = f->ctr;
+    if (pv) {
+        a.part = true;
+        a.base = pv->base;
+        a.n_local = pv->n_local;
+        a.gc = g->lbl_perm ? g->pg_gc : nullptr;
+    }
+    hipLaunchKernelGGL(k_sub_insert, dim3((n + kFBlock - 1) / kFBlock), dim3(kFBlock), 0, s, a);
+    if (out_result) FGI_HIP(g, hipMemcpyAsync(out_result, dr, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    FGI_TRY(read_ctr(g));
+    const uint64_t stored = std::min<uint64_t>(f->ctr_h[kCStored], n);
+    const uint64_t reused = std::min(stored, f->free_n);
+    f->free_n -= reused;
+    f->bump += stored - reused;
+    f->live += stored;
+    return check_chain(g, what);
+}
+
+// the repeat call of a wave's fan-out: the arrays made before, again
+fgi_status fan_again(fgi_graph* g, const char* what, uint32_t n_peers, uint64_t* peer_off, uint64_t* call_ids,
+                     uint32_t* handles, uint64_t cap, uint64_t* out_n) {
+    const Fanout* f = g->fan;
+    if (f->made_peers != n_peers)
+        return set_err(g, FGI_EINVAL, "%s: this wave's lists were made for %u peers", what, f->made_peers);
+    if (out_n) *out_n = f->made_n;
+    if ((call_ids || handles) && f->made_n > cap)
+        return set_err(g, FGI_ECAPACITY, "the fan-out holds %llu entries, the buffers %llu", (unsigned long long)f->made_n,
+                       (unsigned long long)cap);
+    return fan_copy(g, n_peers, f->made_n, peer_off, call_ids, handles);
+}
+
+// A host list (checked by the caller: ascending, in range) joined with the table: one upload, then the list
+// form, or with FGI_OPT_FANOUT_PATH 2 the list scattered into a bitmap over the map's handles.
+fgi_status fan_from_list(fgi_graph* g, const char* what, uint64_t n, const uint32_t* ids, const FoMap& map, uint32_t n_peers,
+                         uint64_t* peer_off, uint64_t* call_ids, uint32_t* handles, uint64_t cap, uint64_t* out_n) {
+    Fanout* f = g->fan;
+    f->made_serial = 0;   // a fan-out: the last wave's lists are gone
+    FGI_TRY(grow(g, &f->ids, &f->ids_cap, std::max<uint64_t>(n, 4096), "handle list"));
+    FGI_HIP(g, hipMemcpyAsync(f->ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));   // the one upload
+    const unsigned long long* inv = nullptr;
+    const uint32_t* src = f->ids;
+    if (g->opt_fanout_path >= 2) {
+        FGI_HIP(g, hipMemsetAsync(f->bits, 0, f->words * 8, g->stream));
+        hipLaunchKernelGGL(k_fo_scatter, dim3(fgrid(n)), dim3(kFBlock), 0, g->stream, (const uint32_t*)f->ids, n, map.id_base,
+                           map.n_handles, f->bits);
+        inv = f->bits;
+        src = nullptr;
+    }
+    uint64_t total = 0;
+    bool wrote = false;
+    FGI_TRY(fan_join(g, inv, src, n, map, n_peers, (call_ids || handles) ? cap : ~0ull, what, &total, &wrote));
+    if (out_n) *out_n = total;
+    if (total && !wrote)
+        return set_err(g, FGI_ECAPACITY, "the fan-out holds %llu entries, the buffers %llu (nothing was removed)",
+                       (unsigned long long)total, (unsigned long long)cap);
+    return fan_copy(g, n_peers, total, peer_off, call_ids, handles);
+}
+
+fgi_status drop_peer(fgi_graph* g, const char* what, uint32_t peer, uint64_t* out_dropped) {
+    Fanout* f = g->fan;
+    hipStream_t s = g->stream;
+    FGI_HIP(g, hipMemsetAsync(f->ctr, 0, kCWords * 8, s));
+    hipLaunchKernelGGL(k_fo_drop_peer, dim3(fgrid(g->ext_handles)), dim3(kFBlock), 0, s, edit_args(g), peer);
+    FGI_TRY(read_ctr(g));
+    if (out_dropped) *out_dropped = std::min<uint64_t>(f->ctr_h[kCDropped], f->live);
+    account_dropped(f);
+    return check_chain(g, what);
+}
 
 }  // namespace
 
@@ -662,51 +840,7 @@ fgi_status fgi_subscribe(fgi_graph* g, uint32_t n, const uint32_t* handle, const
         if (peer[i] >= FGI_MAX_PEERS) return set_err(g, FGI_EINVAL, "fgi_subscribe: peer %u at %u, at most %u peers", peer[i], i, FGI_MAX_PEERS);
     }
     if (!n) return FGI_OK;
-    FGI_TRY(fan_create(g));
-    FGI_TRY(fan_reserve(g, n));
-    FGI_TRY(flush_vis(g));   // fgi_restore may have left the visit bitmap's clearing to the next wave
-    Fanout* f = g->fan;
-    hipStream_t s = g->stream;
-    // the upload: handles, peers, results (4 B each), then the call ids
-    const uint64_t words32 = 3ull * n + 2ull * n + 2;
-    FGI_TRY(grow(g, &f->ids, &f->ids_cap, std::max<uint64_t>(words32, 4096), "subscription upload"));
-    uint32_t* dh = f->ids;
-    uint32_t* dp = dh + n;
-    uint32_t* dr = dp + n;
-    unsigned long long* dc = reinterpret_cast<unsigned long long*>(f->ids + ((3ull * n + 1) & ~1ull));
-    FGI_HIP(g, hipMemcpyAsync(dh, handle, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    FGI_HIP(g, hipMemcpyAsync(dp, peer, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    FGI_HIP(g, hipMemcpyAsync(dc, call_id, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    FGI_HIP(g, hipMemsetAsync(f->ctr, 0, kCWords * 8, s));
-    SubArgs a{};
-    a.n = n;
-    a.handle = dh;
-    a.peer = dp;
-    a.call = dc;
-    a.result = out_result ? dr : nullptr;
-    a.node = reinterpret_cast<const unsigned long long*>(g->node);
-    a.vis = g->v_dirty && !g->vis_stale ? g->vis_bm : nullptr;
-    a.s2l = g->lbl_hot ? g->s2l : nullptr;
-    a.ext_slots = g->ext_slots;
-    a.K = g->lbl_K;
-    a.head = f->head;
-    a.has = f->has;
-    a.rec = f->rec;
-    a.fstack = f->fstack;
-    a.free_n = f->free_n;
-    a.bump = f->bump;
-    a.cap = f->cap;
-    a.pcnt = f->pcnt;
-    a.ctr = f->ctr;
-    hipLaunchKernelGGL(k_sub_insert, dim3((n + kFBlock - 1) / kFBlock), dim3(kFBlock), 0, s, a);
-    if (out_result) FGI_HIP(g, hipMemcpyAsync(out_result, dr, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    FGI_TRY(read_ctr(g));
-    const uint64_t stored = std::min<uint64_t>(f->ctr_h[kCStored], n);
-    const uint64_t reused = std::min(stored, f->free_n);
-    f->free_n -= reused;
-    f->bump += stored - reused;
-    f->live += stored;
-    return check_chain(g, "fgi_subscribe");
+    return sub_insert(g, "fgi_subscribe", n, handle, peer, call_id, out_result, nullptr);
 }
 
 fgi_status fgi_last_wave_fanout(fgi_graph* g, uint32_t n_peers, uint64_t* peer_off, uint64_t* call_ids, uint32_t* handles,
@@ -720,21 +854,14 @@ fgi_status fgi_last_wave_fanout(fgi_graph* g, uint32_t n_peers, uint64_t* peer_o
                        g->casc_kind == kCascBatch ? "fgi_run_batch" : "an asynchronous wave");
     Fanout* f = g->fan;
     const bool want = call_ids || handles;
-    if (f && f->made_serial == g->casc_serial && f->made_serial) {   // made already: the same arrays again
-        if (f->made_peers != n_peers)
-            return set_err(g, FGI_EINVAL, "fgi_last_wave_fanout: this wave's lists were made for %u peers", f->made_peers);
-        if (out_n) *out_n = f->made_n;
-        if (want && f->made_n > cap)
-            return set_err(g, FGI_ECAPACITY, "the fan-out holds %llu entries, the buffers %llu", (unsigned long long)f->made_n,
-                           (unsigned long long)cap);
-        return fan_copy(g, n_peers, f->made_n, peer_off, call_ids, handles);
-    }
+    if (f && f->made_serial == g->casc_serial && f->made_serial)   // made already: the same arrays again
+        return fan_again(g, "fgi_last_wave_fanout", n_peers, peer_off, call_ids, handles, cap, out_n);
     memset(peer_off, 0, ((size_t)n_peers + 1) * 8);
     if (!fanout_live(g) || g->casc_kind != kCascWave || g->last_wave_n == 0) return FGI_OK;
     // the source: the bitmap the wave kept (boundary order without hot labels), else its id list
     const bool kept = !g->ids_valid && g->lbl_K == 0;
     const int path = g->opt_fanout_path;
-    const bool bits = path == 2 || (path == 0 && kept);
+    const bool bits = path >= 2 || (path == 0 && kept);   // (3 is a partition's measurement form: 2 here)
     const unsigned long long* inv = nullptr;
     const uint32_t* ids = nullptr;
     if (bits && kept) {
@@ -745,14 +872,14 @@ fgi_status fgi_last_wave_fanout(fgi_graph* g, uint32_t n_peers, uint64_t* peer_o
         if (bits) {
             FGI_HIP(g, hipMemsetAsync(f->bits, 0, f->words * 8, g->stream));
             hipLaunchKernelGGL(k_fo_scatter, dim3(fgrid(g->last_wave_n)), dim3(kFBlock), 0, g->stream, ids, g->last_wave_n,
-                               g->ext_handles, f->bits);
+                               0u, g->ext_handles, f->bits);
             inv = f->bits;
             ids = nullptr;
         }
     }
     uint64_t total = 0;
     bool wrote = false;
-    const fgi_status st = fan_join(g, inv, ids, g->last_wave_n, n_peers, ~0ull, "fgi_last_wave_fanout", &total, &wrote);
+    const fgi_status st = fan_join(g, inv, ids, g->last_wave_n, whole_table(g), n_peers, ~0ull, "fgi_last_wave_fanout", &total, &wrote);
     if (wrote || (st == FGI_OK && total == 0)) {
         f->made_serial = g->casc_serial;
         f->made_peers = n_peers;
@@ -778,27 +905,7 @@ fgi_status fgi_fanout_ids(fgi_graph* g, uint64_t n, const uint32_t* ids, uint32_
                            (unsigned long long)i);
     memset(peer_off, 0, ((size_t)n_peers + 1) * 8);
     if (!fanout_live(g) || n == 0) return FGI_OK;
-    Fanout* f = g->fan;
-    f->made_serial = 0;   // a fan-out: the last wave's lists are gone
-    FGI_TRY(grow(g, &f->ids, &f->ids_cap, std::max<uint64_t>(n, 4096), "handle list"));
-    FGI_HIP(g, hipMemcpyAsync(f->ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));   // the one upload
-    const unsigned long long* inv = nullptr;
-    const uint32_t* src = f->ids;
-    if (g->opt_fanout_path == 2) {
-        FGI_HIP(g, hipMemsetAsync(f->bits, 0, f->words * 8, g->stream));
-        hipLaunchKernelGGL(k_fo_scatter, dim3(fgrid(n)), dim3(kFBlock), 0, g->stream, (const uint32_t*)f->ids, n, g->ext_handles,
-                           f->bits);
-        inv = f->bits;
-        src = nullptr;
-    }
-    uint64_t total = 0;
-    bool wrote = false;
-    FGI_TRY(fan_join(g, inv, src, n, n_peers, (call_ids || handles) ? cap : ~0ull, "fgi_fanout_ids", &total, &wrote));
-    if (out_n) *out_n = total;
-    if (total && !wrote)
-        return set_err(g, FGI_ECAPACITY, "the fan-out holds %llu entries, the buffers %llu (nothing was removed)",
-                       (unsigned long long)total, (unsigned long long)cap);
-    return fan_copy(g, n_peers, total, peer_off, call_ids, handles);
+    return fan_from_list(g, "fgi_fanout_ids", n, ids, whole_table(g), n_peers, peer_off, call_ids, handles, cap, out_n);
 }
 
 fgi_status fgi_unsubscribe_peer(fgi_graph* g, uint32_t peer, uint64_t* out_dropped) {
@@ -807,14 +914,132 @@ fgi_status fgi_unsubscribe_peer(fgi_graph* g, uint32_t peer, uint64_t* out_dropp
     FGI_TRY(fan_usable(g, "fgi_unsubscribe_peer"));
     if (peer >= FGI_MAX_PEERS) return set_err(g, FGI_EINVAL, "fgi_unsubscribe_peer: peer %u, at most %u peers", peer, FGI_MAX_PEERS);
     if (!fanout_live(g)) return FGI_OK;
+    return drop_peer(g, "fgi_unsubscribe_peer", peer, out_dropped);
+}
+
+// ---- per rank of a partition (C-ABI 0.10): a rank's own table over its own handles, no collective ----
+
+fgi_status fgi_part_subscribe(fgi_graph* g, uint32_t n, const uint32_t* slot, const uint32_t* peer, const uint64_t* call_id,
+                              uint32_t* out_result) {
+    if (!g || (n && (!slot || !peer || !call_id))) return FGI_EINVAL;
+    PartView pv;
+    FGI_TRY(part_fan_usable(g, "fgi_part_subscribe", "fgi_subscribe", &pv));
+    for (uint32_t i = 0; i < n; ++i) {
+        if (slot[i] >= pv.n_global)
+            return set_err(g, FGI_EINVAL, "fgi_part_subscribe: entry %u is slot %u of %u", i, slot[i], pv.n_global);
+        if (peer[i] >= FGI_MAX_PEERS)
+            return set_err(g, FGI_EINVAL, "fgi_part_subscribe: peer %u at %u, at most %u peers", peer[i], i, FGI_MAX_PEERS);
+    }
+    if (!n) return FGI_OK;
+    return sub_insert(g, "fgi_part_subscribe", n, slot, peer, call_id, out_result, &pv);
+}
+
+fgi_status fgi_part_last_wave_fanout(fgi_graph* g, uint32_t n_peers, uint64_t* peer_off, uint64_t* call_ids, uint32_t* slots,
+                                     uint64_t cap, uint64_t* out_n) {
+    if (!g || !peer_off) return FGI_EINVAL;
+    if (out_n) *out_n = 0;
+    PartView pv;
+    FGI_TRY(part_fan_usable(g, "fgi_part_last_wave_fanout", "fgi_last_wave_fanout", &pv));
+    if (n_peers == 0 || n_peers > FGI_MAX_PEERS)
+        return set_err(g, FGI_EINVAL, "fgi_part_last_wave_fanout: n_peers must be 1..%u", FGI_MAX_PEERS);
+    if (g->pout_kind == kPoutOther)
+        return set_err(g, FGI_ENOTSUP, "fgi_part_last_wave_fanout: this rank's last call that ran cascades was no single wave; "
+                                       "pass the ids it returned to fgi_part_fanout_ids");
     Fanout* f = g->fan;
-    hipStream_t s = g->stream;
-    FGI_HIP(g, hipMemsetAsync(f->ctr, 0, kCWords * 8, s));
-    hipLaunchKernelGGL(k_fo_drop_peer, dim3(fgrid(g->ext_handles)), dim3(kFBlock), 0, s, edit_args(g), peer);
-    FGI_TRY(read_ctr(g));
-    if (out_dropped) *out_dropped = std::min<uint64_t>(f->ctr_h[kCDropped], f->live);
-    account_dropped(f);
-    return check_chain(g, "fgi_unsubscribe_peer");
+    if (f && f->made_serial == g->pout_serial && f->made_serial)   // made already: the same arrays again
+        return fan_again(g, "fgi_part_last_wave_fanout", n_peers, peer_off, call_ids, slots, cap, out_n);
+    memset(peer_off, 0, ((size_t)n_peers + 1) * 8);
+    if (!fanout_live(g) || g->pout_kind != kPoutWave || g->last_wave_n == 0) return FGI_OK;
+    // The source. List: the rank's ascending global ids (part_out.hip). Bitmap: the host-order one if it
+    // stands; else, with codes, inv & has probed from the subscribed handles; else the wave's own bitmap,
+    // which is in handle order already (the map keeps what lies past the owned slots out of the join).
+    const int path = g->opt_fanout_path;
+    const bool list = path == 1 || (path == 0 && g->pout && g->pout->ids_valid);
+    const unsigned long long* inv = nullptr;
+    const uint32_t* ids = nullptr;
+    f->last_ms = 0;   // (a call that fails before the join's kernels leaves no earlier call's time behind)
+    FGI_HIP(g, hipEventRecord(f->ev[4], g->stream));   // what makes the source counts in last_kernel_ms
+    if (list) {
+        FGI_TRY(part_out_ids(g, &ids, nullptr));
+    } else if (g->pout && g->pout->bits_valid) {
+        inv = g->pout->bits;
+    } else if (path == 3) {   // measurement only: the whole bitmap renumbered first (part_out_bits), then the AND
+        uint64_t w = 0;
+        FGI_TRY(part_out_bits(g, &inv, &w));
+    } else if (g->lbl_perm) {
+        hipLaunchKernelGGL(k_fo_probe, dim3(fgrid(f->words * 64)), dim3(kFBlock), 0, g->stream,
+                           reinterpret_cast<const unsigned long long*>(g->inv_bm), (const unsigned long long*)f->has,
+                           (const uint32_t*)g->pg_gc, pv.base, pv.n_local, f->bits, f->words);
+        FGI_HIP(g, hipGetLastError());
+        inv = f->bits;
+    } else {
+        inv = reinterpret_cast<const unsigned long long*>(g->inv_bm);
+    }
+    FGI_HIP(g, hipEventRecord(f->ev[5], g->stream));
+    uint64_t total = 0;
+    bool wrote = false;
+    const fgi_status st = fan_join(g, inv, ids, g->last_wave_n, owned_slots(pv), n_peers, ~0ull, "fgi_part_last_wave_fanout",
+                                   &total, &wrote);
+    float src_ms = 0;   // (fan_join waited for the stream)
+    if (hipEventElapsedTime(&src_ms, f->ev[4], f->ev[5]) == hipSuccess) f->last_ms += src_ms;
+    if (wrote || (st == FGI_OK && total == 0)) {
+        f->made_serial = g->pout_serial;
+        f->made_peers = n_peers;
+        f->made_n = total;
+    }
+    FGI_TRY(st);
+    if (out_n) *out_n = total;
+    if ((call_ids || slots) && total > cap)
+        return set_err(g, FGI_ECAPACITY, "the fan-out holds %llu entries, the buffers %llu", (unsigned long long)total,
+                       (unsigned long long)cap);
+    return fan_copy(g, n_peers, total, peer_off, call_ids, slots);
+}
+
+fgi_status fgi_part_fanout_ids(fgi_graph* g, uint64_t n, const uint32_t* slots_in, uint32_t n_peers, uint64_t* peer_off,
+                               uint64_t* call_ids, uint32_t* slots, uint64_t cap, uint64_t* out_n) {
+    if (!g || !peer_off || (n && !slots_in)) return FGI_EINVAL;
+    if (out_n) *out_n = 0;
+    PartView pv;
+    FGI_TRY(part_fan_usable(g, "fgi_part_fanout_ids", "fgi_fanout_ids", &pv));
+    if (n_peers == 0 || n_peers > FGI_MAX_PEERS) return set_err(g, FGI_EINVAL, "fgi_part_fanout_ids: n_peers must be 1..%u", FGI_MAX_PEERS);
+    for (uint64_t i = 0; i < n; ++i)
+        if (slots_in[i] >= pv.n_global || (i && slots_in[i] <= slots_in[i - 1]))
+            return set_err(g, FGI_EINVAL, "fgi_part_fanout_ids: the slots must be below %u and strictly ascending (entry %llu)",
+                           pv.n_global, (unsigned long long)i);
+    memset(peer_off, 0, ((size_t)n_peers + 1) * 8);
+    if (!fanout_live(g) || n == 0) return FGI_OK;
+    // (the slots of other ranks are skipped in the kernels: one compare each)
+    return fan_from_list(g, "fgi_part_fanout_ids", n, slots_in, owned_slots(pv), n_peers, peer_off, call_ids, slots, cap, out_n);
+}
+
+fgi_status fgi_part_fanout_detached(fgi_graph* g, uint64_t n, const uint32_t* handles, uint32_t n_peers, uint64_t* peer_off,
+                                    uint64_t* call_ids, uint32_t* handles_out, uint64_t cap, uint64_t* out_n) {
+    if (!g || !peer_off || (n && !handles)) return FGI_EINVAL;
+    if (out_n) *out_n = 0;
+    PartView pv;
+    FGI_TRY(part_fan_usable(g, "fgi_part_fanout_detached", "fgi_fanout_ids", &pv));
+    if (n_peers == 0 || n_peers > FGI_MAX_PEERS)
+        return set_err(g, FGI_EINVAL, "fgi_part_fanout_detached: n_peers must be 1..%u", FGI_MAX_PEERS);
+    for (uint64_t i = 0; i < n; ++i)
+        if (handles[i] < g->ext_slots || handles[i] >= g->ext_handles || (i && handles[i] <= handles[i - 1]))
+            return set_err(g, FGI_EINVAL, "fgi_part_fanout_detached: the handles must be this rank's detached ones, %u..%u, "
+                                          "and strictly ascending (entry %llu)", g->ext_slots, g->ext_handles - 1,
+                           (unsigned long long)i);
+    memset(peer_off, 0, ((size_t)n_peers + 1) * 8);
+    if (!fanout_live(g) || n == 0) return FGI_OK;
+    return fan_from_list(g, "fgi_part_fanout_detached", n, handles, whole_table(g), n_peers, peer_off, call_ids, handles_out, cap,
+                         out_n);
+}
+
+fgi_status fgi_part_unsubscribe_peer(fgi_graph* g, uint32_t peer, uint64_t* out_dropped) {
+    if (!g) return FGI_EINVAL;
+    if (out_dropped) *out_dropped = 0;
+    PartView pv;
+    FGI_TRY(part_fan_usable(g, "fgi_part_unsubscribe_peer", "fgi_unsubscribe_peer", &pv));
+    if (peer >= FGI_MAX_PEERS)
+        return set_err(g, FGI_EINVAL, "fgi_part_unsubscribe_peer: peer %u, at most %u peers", peer, FGI_MAX_PEERS);
+    if (!fanout_live(g)) return FGI_OK;
+    return drop_peer(g, "fgi_part_unsubscribe_peer", peer, out_dropped);
 }
 
 fgi_status fgi_sub_stats_get(fgi_graph* g, fgi_sub_stats* out) {

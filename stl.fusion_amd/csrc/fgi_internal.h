@@ -458,10 +458,10 @@ struct Fanout {
     uint32_t* ids = nullptr;               // fgi_fanout_ids' upload
     uint64_t ids_cap = 0;
     unsigned long long* bits = nullptr;    // [words] the invalidated set as a bitmap when the wave kept none
-    uint64_t made_serial = 0;              // casc_serial the lists were made for (0: none)
+    uint64_t made_serial = 0;              // casc_serial (a partition rank: pout_serial) the lists were made for (0: none)
     uint32_t made_peers = 0;
     uint64_t made_n = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // 4, 5: a rank's source (fgi_part_last_wave_fanout)
     uint64_t live = 0, delivered = 0, dropped = 0, fanouts = 0, from_list = 0, from_bits = 0;
     double last_ms = 0;
 };
@@ -799,9 +799,11 @@ struct fgi_graph {
     // fgi_part_wave_ids_dev). pout_kind: what the rank's last call that ran cascades was
     // (kPoutNone: none since create or fgi_restore; kPoutWave: one wave, whose result the accessors make on
     // demand; kPoutOther: a mutation or a batch, which report ids through their own out_ids). pout: the
-    // buffers, null until an accessor or fgi_part_invalidate_host first needs them.
+    // buffers, null until an accessor or fgi_part_invalidate_host first needs them. pout_serial counts
+    // part_out_mark's calls: fgi_part_last_wave_fanout makes its lists once per serial (Fanout::made_serial).
     fgi::PartOut* pout = nullptr;
     int pout_kind = 0;
+    uint64_t pout_serial = 0;
     int opt_part_ids_path = 0;         // FGI_OPT_PART_IDS_PATH: 0 by the wave's count, 1 scatter, 2 gather
     // Replica fan-out (fanout.hip). fan: the subscription table, null until the first
     // fgi_subscribe. casc_serial counts the calls that ran cascades (and fgi_restore), casc_kind says what
@@ -809,7 +811,7 @@ struct fgi_graph {
     fgi::Fanout* fan = nullptr;
     uint64_t casc_serial = 0;
     int casc_kind = 0;
-    int opt_fanout_path = 0;           // FGI_OPT_FANOUT_PATH: 0 by what the wave left, 1 id list, 2 bitmap
+    int opt_fanout_path = 0;           // FGI_OPT_FANOUT_PATH: 0 by what the wave left, 1 id list, 2 bitmap, 3 (measurement) a rank's bitmap renumbered whole
 };
 
 // ---- internal entry points shared between translation units ----------------------------------
@@ -1062,6 +1064,7 @@ fgi_status part_flagged_begin(fgi_graph* g, uint64_t cascades, uint64_t extra);
 // Touches host fields only.
 inline void part_out_mark(fgi_graph* g, int kind) {
     g->pout_kind = kind;
+    ++g->pout_serial;   // the rank's fan-out lists of the wave before are forgotten too (fanout.hip)
     if (g->pout) g->pout->bits_valid = g->pout->ids_valid = false;
 }
 // n host roots (global slots) and their `immediately` bytes (nullable) through the graph's pinned buffer

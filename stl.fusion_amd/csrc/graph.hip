@@ -1918,7 +1918,9 @@ fgi_status fgi_version(uint32_t* major, uint32_t* minor) {
     //      (fgi_part_invalidate_host, fgi_part_invalidate_bits, fgi_part_last_wave_ids / _bits, fgi_part_wave_ids_dev)
     // 0.9: the replica fan-out on the device (fgi_subscribe, fgi_last_wave_fanout, fgi_fanout_ids,
     //      fgi_unsubscribe_peer, fgi_sub_stats_get)
-    if (minor) *minor = 9;
+    // 0.10: the same per rank of a partition (fgi_part_subscribe, fgi_part_last_wave_fanout, fgi_part_fanout_ids,
+    //      fgi_part_fanout_detached, fgi_part_unsubscribe_peer)
+    if (minor) *minor = 10;
     return FGI_OK;
 }
 
@@ -2575,7 +2577,7 @@ fgi_status fgi_set_option(fgi_graph* g, int option, int64_t value) {
         if (g->pout) g->pout->bits_valid = g->pout->ids_valid = false;
         return FGI_OK;
     case FGI_OPT_FANOUT_PATH:
-        if (value < 0 || value > 2) return set_err(g, FGI_EINVAL, "fan-out path must be 0, 1 or 2");
+        if (value < 0 || value > 3) return set_err(g, FGI_EINVAL, "fan-out path must be 0, 1, 2 or 3");
         g->opt_fanout_path = (int)value;
         return FGI_OK;
     case FGI_OPT_PROBE_SUMMARY:
@@ -4076,6 +4078,11 @@ fgi_status part_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, co
         FGI_TRY(install_nodes(g, m, cnt[1], ds, dv, dd, dcls, dout, tf));
         FGI_TRY(d2h(g, od.data(), dout, m));
         g->free_detached.resize(g->free_detached.size() - (size_t)cnt[1]);
+        if (fanout_live(g)) {   // subscriptions follow the node (fanout.hip): the slot's handle is slot - base
+            std::vector<uint32_t> from(m);
+            for (uint32_t j = 0; j < m; ++j) from[j] = part_slot_of(g, ls[j] + pv.base) - pv.base;
+            FGI_TRY(fanout_move(g, m, from.data(), od.data()));
+        }
         if (view_on(g)) {   // the owned slots' new nodes and the detached handles handed out (the cascade's share is in)
             view_begin(g);
             FGI_TRY(view_refresh(g, kViewLabels, ds, m));

@@ -36,6 +36,7 @@ OPT_PART_IDS_PATH = 19    # partitions with codes, a wave's ids / bitmap in the 
 OPT_FANOUT_PATH = 20      # the replica fan-out's source: 0 by what the wave left, 1 its id list, 2 its bitmap
 MAX_PEERS = 4096
 SUB_ADDED, SUB_INVALIDATED = 0, 1
+SUB_NOT_OWNED = 2           # fgi_part_subscribe: a slot another rank owns (not stored)
 DIR_AUTO, DIR_PUSH, DIR_PULL = 0, 1, 2
 NONE = 0xFFFFFFFF
 COMPUTING, CONSISTENT, INVALIDATED = 0, 1, 2
@@ -255,6 +256,11 @@ SIGNATURES = {
     "fgi_fanout_ids": [_G, C.c_uint64, _u32p, C.c_uint32, _u64p, _u64p, _u32p, C.c_uint64, _u64p],
     "fgi_unsubscribe_peer": [_G, C.c_uint32, _u64p],
     "fgi_sub_stats_get": [_G, C.POINTER(SubStats)],
+    "fgi_part_subscribe": [_G, C.c_uint32, _u32p, _u32p, _u64p, _u32p],
+    "fgi_part_last_wave_fanout": [_G, C.c_uint32, _u64p, _u64p, _u32p, C.c_uint64, _u64p],
+    "fgi_part_fanout_ids": [_G, C.c_uint64, _u32p, C.c_uint32, _u64p, _u64p, _u32p, C.c_uint64, _u64p],
+    "fgi_part_fanout_detached": [_G, C.c_uint64, _u32p, C.c_uint32, _u64p, _u64p, _u32p, C.c_uint64, _u64p],
+    "fgi_part_unsubscribe_peer": [_G, C.c_uint32, _u64p],
 }
 
 _lib = None
@@ -627,6 +633,57 @@ class Graph:
         """fgi_unsubscribe_peer: drop a disconnected peer's entries; returns how many."""
         n = C.c_uint64()
         self._check(self.lib.fgi_unsubscribe_peer(self.h, peer, C.byref(n)), "unsubscribe_peer")
+        return int(n.value)
+
+    # ---- replica fan-out per rank of a partition (C-ABI 0.10): rank-local, no collective ----
+    def part_subscribe(self, slots, peers, call_ids) -> np.ndarray:
+        """fgi_part_subscribe: store (global slot, peer, call id) entries on this rank; returns SUB_ADDED /
+        SUB_INVALIDATED / SUB_NOT_OWNED per entry (only SUB_ADDED entries are stored)."""
+        h, p, c = _u32(slots), _u32(peers), _u64(call_ids)
+        if not (len(h) == len(p) == len(c)):
+            raise ValueError("part_subscribe: slots, peers and call_ids differ in length")
+        res = np.zeros(len(h), np.uint32)
+        self._check(self.lib.fgi_part_subscribe(self.h, len(h), _ptr(h, C.c_uint32), _ptr(p, C.c_uint32),
+                                                _ptr(c, C.c_uint64), _ptr(res, C.c_uint32)), "part_subscribe")
+        return res
+
+    def part_last_wave_fanout(self, n_peers: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """fgi_part_last_wave_fanout: (peer_off, call_ids, slots) of the entries this rank's last wave released,
+        slots as global ids, ascending within a peer. One-shot: they leave the rank's table."""
+        off = np.zeros(n_peers + 1, np.uint64)
+        n = C.c_uint64()
+        self._check(self.lib.fgi_part_last_wave_fanout(self.h, n_peers, _ptr(off, C.c_uint64), None, None, 0, C.byref(n)),
+                    "part_last_wave_fanout")
+        calls, slots = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint32)
+        self._check(self.lib.fgi_part_last_wave_fanout(self.h, n_peers, _ptr(off, C.c_uint64), _ptr(calls, C.c_uint64),
+                                                       _ptr(slots, C.c_uint32), len(calls), C.byref(n)),
+                    "part_last_wave_fanout")
+        return off, calls, slots
+
+    def _part_fanout_list(self, fn, what, ids, n_peers):
+        i = _u32(ids)
+        cap = int(self.sub_stats()["live"])
+        off = np.zeros(n_peers + 1, np.uint64)
+        calls, hnd = np.zeros(cap, np.uint64), np.zeros(cap, np.uint32)
+        n = C.c_uint64()
+        self._check(fn(self.h, len(i), _ptr(i, C.c_uint32), n_peers, _ptr(off, C.c_uint64), _ptr(calls, C.c_uint64),
+                       _ptr(hnd, C.c_uint32), cap, C.byref(n)), what)
+        return off, calls[:n.value].copy(), hnd[:n.value].copy()
+
+    def part_fanout_ids(self, slots, n_peers: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """fgi_part_fanout_ids: this rank's share of the join for a strictly ascending list of global slots
+        (the slots of other ranks are skipped)."""
+        return self._part_fanout_list(self.lib.fgi_part_fanout_ids, "part_fanout_ids", slots, n_peers)
+
+    def part_fanout_detached(self, handles, n_peers: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """fgi_part_fanout_detached: the entries that followed displaced nodes to this rank's detached handles
+        (strictly ascending local handles); the third array holds the detached handles."""
+        return self._part_fanout_list(self.lib.fgi_part_fanout_detached, "part_fanout_detached", handles, n_peers)
+
+    def part_unsubscribe_peer(self, peer: int) -> int:
+        """fgi_part_unsubscribe_peer: drop a disconnected peer's entries on this rank; returns how many."""
+        n = C.c_uint64()
+        self._check(self.lib.fgi_part_unsubscribe_peer(self.h, peer, C.byref(n)), "part_unsubscribe_peer")
         return int(n.value)
 
     def sub_stats(self) -> dict:
