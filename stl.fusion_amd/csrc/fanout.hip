@@ -455,20 +455,6 @@ __global__ __launch_bounds__(kFBlock) void k_fo_drop_peer(EditArgs a, uint32_t p
 
 inline uint32_t fgrid(uint64_t n) { return (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(1, (n + kFBlock - 1) / kFBlock)); }
 
-template <class T>
-fgi_status grow(fgi_graph* g, T** p, uint64_t* cap, uint64_t need, const char* what) {
-    if (*cap >= need && *p) return FGI_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T)) != hipSuccess) {
-        *p = nullptr;
-        return set_err(g, FGI_ENOMEM, "the fan-out's %s (%llu entries)", what, (unsigned long long)need);
-    }
-    *cap = need;
-    return FGI_OK;
-}
-
 // the table, allocated at the first fgi_subscribe
 fgi_status fan_create(fgi_graph* g) {
     if (g->fan) return FGI_OK;
@@ -504,21 +490,19 @@ fgi_status fan_reserve(fgi_graph* g, uint64_t need) {
     if (f->free_n + (f->cap - f->bump) >= need) return FGI_OK;
     const uint64_t want = std::max<uint64_t>({f->bump + (need - f->free_n), 2 * f->cap, 1024});
     if (want >= FGI_NONE) return set_err(g, FGI_ENOMEM, "the subscription table holds at most 2^32 - 2 entries");
-    SubRec* rec = nullptr;
-    uint32_t* fs = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&rec), want * sizeof(SubRec)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&fs), want * 4) != hipSuccess) {
-        if (rec) (void)hipFree(rec);
+    DevOwn<SubRec> rec;   // until they are installed
+    DevOwn<uint32_t> fs;
+    if (hipMalloc(reinterpret_cast<void**>(&rec.p), want * sizeof(SubRec)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&fs.p), want * 4) != hipSuccess)
         return set_err(g, FGI_ENOMEM, "a subscription pool of %llu records", (unsigned long long)want);
-    }
     hipStream_t s = g->stream;
-    if (f->bump) FGI_HIP(g, hipMemcpyAsync(rec, f->rec, f->bump * sizeof(SubRec), hipMemcpyDeviceToDevice, s));
-    if (f->free_n) FGI_HIP(g, hipMemcpyAsync(fs, f->fstack, f->free_n * 4, hipMemcpyDeviceToDevice, s));
+    if (f->bump) FGI_HIP(g, hipMemcpyAsync(rec.p, f->rec, f->bump * sizeof(SubRec), hipMemcpyDeviceToDevice, s));
+    if (f->free_n) FGI_HIP(g, hipMemcpyAsync(fs.p, f->fstack, f->free_n * 4, hipMemcpyDeviceToDevice, s));
     FGI_HIP(g, hipStreamSynchronize(s));
-    if (f->rec) (void)hipFree(f->rec);
-    if (f->fstack) (void)hipFree(f->fstack);
-    f->rec = rec;
-    f->fstack = fs;
+    dfree(f->rec);
+    dfree(f->fstack);
+    f->rec = rec.release();
+    f->fstack = fs.release();
     f->cap = want;
     return FGI_OK;
 }
@@ -571,7 +555,7 @@ fgi_status fan_join(fgi_graph* g, const unsigned long long* inv, const uint32_t*
     const uint64_t units = list ? (n_ids + 63) / 64 : f->words;   // groups of 64 handles
     const uint64_t gpt = std::max<uint64_t>(1, (units + max_tiles - 1) / max_tiles);   // groups per tile
     const uint32_t n_tiles = (uint32_t)std::max<uint64_t>(1, (units + gpt - 1) / gpt);
-    FGI_TRY(grow(g, &f->tcnt, &f->tcnt_cap, (uint64_t)n_tiles * n_peers, "tile counts"));
+    FGI_TRY(grow(g, &f->tcnt, &f->tcnt_cap, (uint64_t)n_tiles * n_peers, "the fan-out's tile counts"));
     FoArgs a{};
     a.inv = inv;
     a.ids = ids;
@@ -615,18 +599,9 @@ fgi_status fan_join(fgi_graph* g, const unsigned long long* inv, const uint32_t*
     if (n > f->live) return set_err(g, FGI_ESTATE, "%s: %llu entries found, %llu stored", what, (unsigned long long)n,
                                     (unsigned long long)f->live);
     if (n == 0 || n > cap_or_all) return FGI_OK;
-    if (f->out_cap < n) {
-        if (f->out_call) (void)hipFree(f->out_call);
-        if (f->out_hnd) (void)hipFree(f->out_hnd);
-        f->out_call = nullptr;
-        f->out_hnd = nullptr;
-        f->out_cap = 0;
-        const uint64_t c = std::max<uint64_t>(n, 4096);
-        if (hipMalloc(reinterpret_cast<void**>(&f->out_call), c * 8) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&f->out_hnd), c * 4) != hipSuccess)
-            return set_err(g, FGI_ENOMEM, "the fan-out's lists (%llu entries)", (unsigned long long)n);
-        f->out_cap = c;
-    }
+    uint64_t hnd_cap = f->out_cap;   // the two lists grow together
+    FGI_TRY(grow(g, &f->out_hnd, &hnd_cap, std::max<uint64_t>(n, 4096), "the fan-out's lists"));
+    FGI_TRY(grow(g, &f->out_call, &f->out_cap, std::max<uint64_t>(n, 4096), "the fan-out's lists"));
     a.out_call = f->out_call;
     a.out_hnd = f->out_hnd;
     a.out_n = n;
@@ -685,7 +660,7 @@ fgi_status sub_insert(fgi_graph* g, const char* what, uint32_t n, const uint32_t
     hipStream_t s = g->stream;
     // the upload: handles, peers, results (4 B each), then the call ids
     const uint64_t words32 = 3ull * n + 2ull * n + 2;
-    FGI_TRY(grow(g, &f->ids, &f->ids_cap, std::max<uint64_t>(words32, 4096), "subscription upload"));
+    FGI_TRY(grow(g, &f->ids, &f->ids_cap, std::max<uint64_t>(words32, 4096), "the fan-out's subscription upload"));
     uint32_t* dh = f->ids;
     uint32_t* dp = dh + n;
     uint32_t* dr = dp + n;
@@ -750,7 +725,7 @@ fgi_status fan_from_list(fgi_graph* g, const char* what, uint64_t n, const uint3
                          uint64_t* peer_off, uint64_t* call_ids, uint32_t* handles, uint64_t cap, uint64_t* out_n) {
     Fanout* f = g->fan;
     f->made_serial = 0;   // a fan-out: the last wave's lists are gone
-    FGI_TRY(grow(g, &f->ids, &f->ids_cap, std::max<uint64_t>(n, 4096), "handle list"));
+    FGI_TRY(grow(g, &f->ids, &f->ids_cap, std::max<uint64_t>(n, 4096), "the fan-out's handle list"));
     FGI_HIP(g, hipMemcpyAsync(f->ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));   // the one upload
     const unsigned long long* inv = nullptr;
     const uint32_t* src = f->ids;
@@ -788,7 +763,7 @@ fgi_status fanout_move(fgi_graph* g, uint32_t n, const uint32_t* from, const uin
     if (!fanout_live(g) || !n) return FGI_OK;
     Fanout* f = g->fan;
     hipStream_t s = g->stream;
-    FGI_TRY(grow(g, &f->ids, &f->ids_cap, std::max<uint64_t>(2ull * n, 4096), "handle list"));
+    FGI_TRY(grow(g, &f->ids, &f->ids_cap, std::max<uint64_t>(2ull * n, 4096), "the fan-out's handle list"));
     FGI_HIP(g, hipMemcpyAsync(f->ids, from, (size_t)n * 4, hipMemcpyHostToDevice, s));
     FGI_HIP(g, hipMemcpyAsync(f->ids + n, to, (size_t)n * 4, hipMemcpyHostToDevice, s));
     FGI_HIP(g, hipMemsetAsync(f->ctr, 0, kCWords * 8, s));
@@ -802,7 +777,7 @@ fgi_status fanout_drop_handles(fgi_graph* g, uint32_t n, const uint32_t* handles
     if (!fanout_live(g) || !n) return FGI_OK;
     Fanout* f = g->fan;
     hipStream_t s = g->stream;
-    FGI_TRY(grow(g, &f->ids, &f->ids_cap, std::max<uint64_t>(n, 4096), "handle list"));
+    FGI_TRY(grow(g, &f->ids, &f->ids_cap, std::max<uint64_t>(n, 4096), "the fan-out's handle list"));
     FGI_HIP(g, hipMemcpyAsync(f->ids, handles, (size_t)n * 4, hipMemcpyHostToDevice, s));
     FGI_HIP(g, hipMemsetAsync(f->ctr, 0, kCWords * 8, s));
     hipLaunchKernelGGL(k_fo_drop_handles, dim3((n + kFBlock - 1) / kFBlock), dim3(kFBlock), 0, s, edit_args(g), n,

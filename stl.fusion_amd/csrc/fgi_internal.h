@@ -17,6 +17,7 @@
 
 #include <chrono>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <string>
 #include <utility>
@@ -405,6 +406,18 @@ struct View {
 // handles on and scatters below (FGI_OPT_PART_VIEW_PATH pins either)
 constexpr uint32_t kPartViewGatherDen = 16;
 
+// Host roots on their way to the device: n roots (4 B each), then their `immediately` bytes at cap * 4, in
+// one pinned and one device buffer of cap * 5 bytes, moved by two copies on the graph's stream. The owner
+// sees to it that the previous call's copies have been consumed before it stages again.
+struct RootStage {
+    char* h = nullptr;   // pinned
+    char* d = nullptr;
+    uint64_t cap = 0;
+    // imm nullable (*imm_dev is then null); nothing waits
+    fgi_status stage(fgi_graph* g, uint32_t n, const uint32_t* roots, const uint8_t* imm, uint32_t** roots_dev, uint8_t** imm_dev);
+    void release();
+};
+
 // A partition rank's last wave in the host's numbering (part_out.hip): the bitmap over the
 // rank's boundary handles (bit h = global slot base + h, as the state view's planes) and the ascending
 // global ids made from it, both on the device, each made at most once per wave; and the staging of
@@ -417,10 +430,7 @@ struct PartOut {
     unsigned long long* bsum = nullptr;   // [bsum_cap] per-block popcounts, scanned in place; then the total
     uint64_t bsum_cap = 0;
     bool bits_valid = false, ids_valid = false;   // of the rank's last wave (part_out_mark clears them)
-    char* stage_h = nullptr;              // pinned: roots_cap roots, then roots_cap `immediately` bytes
-    uint32_t* roots_d = nullptr;
-    uint8_t* imm_d = nullptr;
-    uint64_t roots_cap = 0;
+    RootStage roots;                      // fgi_part_invalidate_host's
 };
 enum { kPoutNone = 0, kPoutWave = 1, kPoutOther = 2 };
 // With codes, a wave's host-order bitmap is gathered from n_local / kPartIdsGatherDen invalidated slots on
@@ -512,8 +522,8 @@ struct fgi_graph {
     uint32_t* home = nullptr;          // [n_detached]: home slot of a detached handle
     std::vector<uint32_t> free_detached;  // host free list of detached handles
     std::vector<uint8_t> seen_slots;      // host scratch, a byte per slot, all-zero between uses (slot-repeat checks)
-    // device temporaries of the mutation calls, kept for reuse (same stream, so reuse is ordered
-    // after the previous user) instead of a hipMalloc + hipFree (an implicit device sync) per call
+    // device temporaries (Tmp), kept for reuse (same stream, so reuse is ordered after the previous
+    // user) instead of a hipMalloc + hipFree (an implicit device sync) per call
     std::vector<std::pair<size_t, void*>> tmp_cache;
     size_t tmp_cached = 0;
 
@@ -568,9 +578,7 @@ struct fgi_graph {
     uint32_t* inv_alt = nullptr;
     uint32_t* inv_cur = nullptr;
     // fgi_invalidate_async_host: per ticket parity, the roots staged in pinned memory and their device copy
-    uint32_t* ar_h[2] = {nullptr, nullptr};
-    uint32_t* ar_d[2] = {nullptr, nullptr};
-    uint64_t ar_cap[2] = {0, 0};
+    fgi::RootStage ar[2];
     bool lists_wanted = false;         // a wave met a frontier heavy enough to pull (async waves build lists first)
     bool ids_valid = false;            // inv holds the last wave's list (else ensure_ids rebuilds it)
     int last_levels = 4;               // non-empty levels of the last wave (sizes the first level group)
@@ -782,7 +790,7 @@ struct fgi_graph {
     // which opened the call itself (part_flagged_begin) and numbers the cascades by pflg_step.
     unsigned long long* prec = nullptr;
     uint64_t prec_cap = 0;
-    unsigned long long* pcur = nullptr;   // [1 + pcur_cap]
+    unsigned long long* pcur = nullptr;   // [pcur_cap]: the cursor, then a mark per cascade
     uint64_t pcur_cap = 0;
     struct PartRun {
         uint32_t step = 0;
@@ -812,6 +820,7 @@ struct fgi_graph {
     uint64_t casc_serial = 0;
     int casc_kind = 0;
     int opt_fanout_path = 0;           // FGI_OPT_FANOUT_PATH: 0 by what the wave left, 1 id list, 2 bitmap, 3 (measurement) a rank's bitmap renumbered whole
+    bool tmp_poison = false;           // FGI_TMP_POISON=1: every temporary is handed out filled with 0xA5
 };
 
 // ---- internal entry points shared between translation units ----------------------------------
@@ -1124,3 +1133,114 @@ fgi_status load_rows_dev(fgi_graph* g, uint64_t m, const uint64_t* dev_keys, con
         fgi_status _s = (call);                \
         if (_s != FGI_OK) return _s;           \
     } while (0)
+
+// ---- device memory of a call and of the graph -----------------------------------------
+namespace fgi {
+template <class T>
+fgi_status dmalloc(fgi_graph* g, T** p, size_t count) {
+    *p = nullptr;
+    if (count == 0) count = 1;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
+    if (e != hipSuccess) return hip_check(g, e, "hipMalloc");
+    return FGI_OK;
+}
+
+template <class T>
+void dfree(T*& p) {
+    if (p) hipFree(p);
+    p = nullptr;
+}
+
+// a fresh device allocation until its owner takes it (buffers that grow by copying)
+template <class T>
+struct DevOwn {
+    T* p = nullptr;
+    DevOwn() = default;
+    DevOwn(const DevOwn&) = delete;
+    DevOwn& operator=(const DevOwn&) = delete;
+    ~DevOwn() { dfree(p); }
+    T* release() {
+        T* q = p;
+        p = nullptr;
+        return q;
+    }
+};
+
+// An owned (pointer, capacity) pair that grows by replacement: the contents are not kept. `what` names
+// the buffer in the error ("the fan-out's tile counts").
+template <class T>
+fgi_status grow(fgi_graph* g, T** p, uint64_t* cap, uint64_t need, const char* what) {
+    if (*cap >= need && (*p || !need)) return FGI_OK;
+    dfree(*p);
+    *cap = 0;
+    if (hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T)) != hipSuccess) {
+        *p = nullptr;
+        return set_err(g, FGI_ENOMEM, "%s (%llu entries)", what, (unsigned long long)need);
+    }
+    *cap = need;
+    return FGI_OK;
+}
+
+// Device temporaries of one ABI call. Small ones (power-of-two size classes up to kTmpKeepMax,
+// kTmpKeepTotal in all) go back to the graph's cache when their scope ends (or at reset()); every user
+// of a temporary runs on the graph's stream, so a later reuse is ordered after it. A request above
+// kTmpKeepMax never enters the cache and is allocated at its exact size. A block's contents are
+// undefined: FGI_TMP_POISON=1 (read at fgi_create) fills every block handed out with 0xA5 bytes.
+constexpr size_t kTmpKeepMax = 64ull << 20;
+constexpr size_t kTmpKeepTotal = 512ull << 20;
+void tmp_release(fgi_graph* g, void* p, size_t bytes);
+void tmp_drain(fgi_graph* g);
+struct Tmp {
+    fgi_graph* g = nullptr;
+    void* p = nullptr;
+    size_t bytes = 0;
+    Tmp() = default;
+    Tmp(Tmp&& o) noexcept : g(o.g), p(o.p), bytes(o.bytes) { o.p = nullptr; }
+    Tmp& operator=(const Tmp&) = delete;
+    void reset() {
+        if (p) tmp_release(g, p, bytes);
+        p = nullptr;
+        bytes = 0;
+    }
+    ~Tmp() { reset(); }
+};
+fgi_status tmp_take(fgi_graph* g, Tmp& t, size_t bytes);
+template <class T>
+fgi_status tmalloc(fgi_graph* g, Tmp& t, T** p, size_t count) {
+    *p = nullptr;
+    FGI_TRY(tmp_take(g, t, (count ? count : 1) * sizeof(T)));
+    *p = reinterpret_cast<T*>(t.p);
+    return FGI_OK;
+}
+
+inline void RootStage::release() {
+    if (h) (void)hipHostFree(h);
+    h = nullptr;
+    dfree(d);
+    cap = 0;
+}
+inline fgi_status RootStage::stage(fgi_graph* g, uint32_t n, const uint32_t* roots, const uint8_t* imm, uint32_t** roots_dev,
+                                   uint8_t** imm_dev) {
+    if (cap < n || !h) {
+        release();
+        const uint64_t c = n > 4096 ? n : 4096;
+        if (hipHostMalloc(reinterpret_cast<void**>(&h), c * 5, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&d), c * 5) != hipSuccess) {
+            release();
+            return set_err(g, FGI_ENOMEM, "the staging of %u host roots", n);
+        }
+        cap = c;
+    }
+    *roots_dev = reinterpret_cast<uint32_t*>(d);
+    *imm_dev = nullptr;
+    if (!n) return FGI_OK;
+    memcpy(h, roots, (size_t)n * 4);
+    FGI_HIP(g, hipMemcpyAsync(d, h, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+    if (imm) {
+        memcpy(h + cap * 4, imm, n);
+        FGI_HIP(g, hipMemcpyAsync(d + cap * 4, h + cap * 4, n, hipMemcpyHostToDevice, g->stream));
+        *imm_dev = reinterpret_cast<uint8_t*>(d + cap * 4);
+    }
+    return FGI_OK;
+}
+}  // namespace fgi

@@ -42,30 +42,6 @@ fgi_status hip_check(fgi_graph* g, hipError_t e, const char* what) {
     return set_err(g, e == hipErrorOutOfMemory ? FGI_ENOMEM : FGI_EDEVICE, "%s: %s", what, hipGetErrorString(e));
 }
 
-namespace {
-
-template <class T>
-fgi_status dmalloc(fgi_graph* g, T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-    if (e != hipSuccess) return hip_check(g, e, "hipMalloc");
-    return FGI_OK;
-}
-
-template <class T>
-void dfree(T*& p) {
-    if (p) hipFree(p);
-    p = nullptr;
-}
-
-// RAII device temporaries for non-hot-path operations
-// Device temporaries of one ABI call. Small ones (power-of-two size classes up to kTmpKeepMax,
-// kTmpKeepTotal in all) go back to the graph's cache when the call ends; every user of a
-// temporary runs on the graph's stream, so a later reuse is ordered after it.
-constexpr size_t kTmpKeepMax = 64ull << 20;
-constexpr size_t kTmpKeepTotal = 512ull << 20;
-
 void tmp_release(fgi_graph* g, void* p, size_t bytes) {
     if (g && bytes <= kTmpKeepMax && g->tmp_cached + bytes <= kTmpKeepTotal) {
         g->tmp_cache.emplace_back(bytes, p);
@@ -81,44 +57,38 @@ void tmp_drain(fgi_graph* g) {
     g->tmp_cached = 0;
 }
 
-struct Tmp {
-    fgi_graph* g = nullptr;
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~Tmp() {
-        if (p) tmp_release(g, p, bytes);
-    }
-};
-template <class T>
-fgi_status tmalloc(fgi_graph* g, Tmp& t, T** p, size_t count) {
-    size_t want = 4096;
-    while (want < (count ? count : 1) * sizeof(T)) want <<= 1;
+fgi_status tmp_take(fgi_graph* g, Tmp& t, size_t bytes) {
+    t.reset();
+    size_t want = bytes;
+    if (bytes <= kTmpKeepMax)
+        for (want = 4096; want < bytes;) want <<= 1;
     t.g = g;
-    for (size_t i = 0; i < g->tmp_cache.size(); ++i) {
+    for (size_t i = 0; i < g->tmp_cache.size() && !t.p; ++i) {
         if (g->tmp_cache[i].first == want) {
             t.p = g->tmp_cache[i].second;
-            t.bytes = want;
             g->tmp_cache[i] = g->tmp_cache.back();
             g->tmp_cache.pop_back();
             g->tmp_cached -= want;
-            *p = reinterpret_cast<T*>(t.p);
-            return FGI_OK;
         }
     }
-    hipError_t e = hipMalloc(&t.p, want);
-    if (e != hipSuccess && !g->tmp_cache.empty()) {   // give the cache back and retry once
-        hipStreamSynchronize(g->stream);
-        tmp_drain(g);
-        e = hipMalloc(&t.p, want);
-    }
-    if (e != hipSuccess) {
-        t.p = nullptr;
-        return hip_check(g, e, "hipMalloc(tmp)");
+    if (!t.p) {
+        hipError_t e = hipMalloc(&t.p, want);
+        if (e != hipSuccess && !g->tmp_cache.empty()) {   // give the cache back and retry once
+            hipStreamSynchronize(g->stream);
+            tmp_drain(g);
+            e = hipMalloc(&t.p, want);
+        }
+        if (e != hipSuccess) {
+            t.p = nullptr;
+            return hip_check(g, e, "hipMalloc(tmp)");
+        }
     }
     t.bytes = want;
-    *p = reinterpret_cast<T*>(t.p);
+    if (g->tmp_poison) FGI_HIP(g, hipMemsetAsync(t.p, 0xA5, want, g->stream));
     return FGI_OK;
 }
+
+namespace {
 
 __device__ __forceinline__ uint32_t home_of(uint32_t h, uint32_t n_slots, const uint32_t* home) {
     return h < n_slots ? h : home[h - n_slots];
@@ -1325,14 +1295,11 @@ fgi_status gather_live(fgi_graph* g, Tmp& tk, Tmp& tt, uint64_t** keys, uint64_t
 // the chunk maps of the two frontier lists: one entry per kFine edges of a level's frontier
 fgi_status ensure_cstart(fgi_graph* g, uint64_t total_edges) {
     const uint64_t need = total_edges / kFine + 4;
-    if (g->cstart_cap >= need) return FGI_OK;
-    dfree(g->cstart[0]);
-    dfree(g->cstart[1]);
+    if (g->cstart_cap >= need && g->cstart[0] && g->cstart[1]) return FGI_OK;
     const uint64_t cap = std::max<uint64_t>(need, g->cstart_cap * 3 / 2);
-    FGI_TRY(dmalloc(g, &g->cstart[0], cap));
-    FGI_TRY(dmalloc(g, &g->cstart[1], cap));
-    g->cstart_cap = cap;
-    return FGI_OK;
+    uint64_t cap1 = g->cstart_cap;   // the two grow together
+    FGI_TRY(grow(g, &g->cstart[1], &cap1, cap, "the chunk maps"));
+    return grow(g, &g->cstart[0], &g->cstart_cap, cap, "the chunk maps");
 }
 
 fgi_status ensure_pool(fgi_graph* g, uint64_t entries) {
@@ -1344,23 +1311,19 @@ fgi_status ensure_pool(fgi_graph* g, uint64_t entries) {
         return set_err(g, FGI_ENOTSUP, "edge pool of %llu entries exceeds 2^32 per device", (unsigned long long)entries);
     const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>({entries, g->pool_cap + g->pool_cap / 2, (uint64_t)1024}),
                                             kMaxPool);
-    uint32_t* col = nullptr;
-    uint64_t* tag = nullptr;
-    FGI_TRY(dmalloc(g, &col, cap));
-    fgi_status st = dmalloc(g, &tag, cap);
-    if (st != FGI_OK) {
-        hipFree(col);
-        return st;
-    }
+    DevOwn<uint32_t> col;   // until they are installed
+    DevOwn<uint64_t> tag;
+    FGI_TRY(dmalloc(g, &col.p, cap));
+    FGI_TRY(dmalloc(g, &tag.p, cap));
     if (g->pool_top) {
-        FGI_HIP(g, hipMemcpyAsync(col, g->pool_col, g->pool_top * sizeof(uint32_t), hipMemcpyDeviceToDevice, g->stream));
-        FGI_HIP(g, hipMemcpyAsync(tag, g->pool_tag, g->pool_top * sizeof(uint64_t), hipMemcpyDeviceToDevice, g->stream));
+        FGI_HIP(g, hipMemcpyAsync(col.p, g->pool_col, g->pool_top * sizeof(uint32_t), hipMemcpyDeviceToDevice, g->stream));
+        FGI_HIP(g, hipMemcpyAsync(tag.p, g->pool_tag, g->pool_top * sizeof(uint64_t), hipMemcpyDeviceToDevice, g->stream));
         FGI_HIP(g, hipStreamSynchronize(g->stream));
     }
     dfree(g->pool_col);
     dfree(g->pool_tag);
-    g->pool_col = col;
-    g->pool_tag = tag;
+    g->pool_col = col.release();
+    g->pool_tag = tag.release();
     g->pool_cap = cap;
     return ensure_cstart(g, cap);
 }
@@ -1386,12 +1349,7 @@ fgi_status ensure_in_lists(fgi_graph* g) {
     FGI_TRY(d2h(g, &last_off, g->uin_off + N - 1, 1));
     FGI_TRY(d2h(g, &last_len, g->uin_len + N - 1, 1));
     const uint64_t total = last_off + last_len;
-    if (total > g->uin_cap || !g->uin_src) {
-        dfree(g->uin_src);
-        const uint64_t cap = std::max<uint64_t>(total, 1024);
-        FGI_TRY(dmalloc(g, &g->uin_src, cap));
-        g->uin_cap = cap;
-    }
+    FGI_TRY(grow(g, &g->uin_src, &g->uin_cap, std::max<uint64_t>(total, 1024), "the dependency lists"));
     // Fill and order the lists with one stable radix sort of (dependant, weight) pairs over the pool:
     // every list ordered by its entries' own dependency counts (descending; ties in pool order), so a
     // pull level finds a parent in the frontier among the first entries (in the two heads, mostly).
@@ -1571,14 +1529,8 @@ fgi_status build_candidates(fgi_graph* g) {
     FGI_TRY(d2h(g, &rlp, rpos + N - 1, 1));
     FGI_TRY(d2h(g, &rlw, rwords + N - 1, 1));
     const uint64_t run_total = rlp + rlw;
-    if (g->trun_cap < run_total || !g->trun) {
-        dfree(g->trun);
-        g->trun = nullptr;
-        g->trun_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(run_total, 1024);
-        FGI_TRY(dmalloc(g, &g->trun, cap + 2));   // a pull level reads three words of a two-word run
-        g->trun_cap = cap;
-    }
+    // (+ 2: a pull level reads three words of a two-word run)
+    FGI_TRY(grow(g, &g->trun, &g->trun_cap, std::max<uint64_t>(run_total, 1024) + 2, "the tail runs"));
     hipLaunchKernelGGL(k_run_fill, dim3(nblk(N)), dim3(256), 0, s, N, g->uin_len, g->uin_off, g->uin_src, rpos, g->trun);
     // hot heads (a partition's heads are global ids: ranked over all n_global slots, their snapshot
     // taken from the all-gathered invalidated bitmap)
@@ -1934,6 +1886,8 @@ fgi_status fgi_create(const fgi_config* cfg, fgi_graph** out) {
     if ((uint64_t)K + cfg->n_slots + cfg->n_detached >= 0xFFFFFFF0ull) return FGI_EINVAL;
     *out = nullptr;
     fgi_graph* g = new fgi_graph();
+    const char* poison = getenv("FGI_TMP_POISON");
+    g->tmp_poison = poison && poison[0] == '1';
     g->device = cfg->device;
     g->opt_labels = labels;
     g->lbl_K = K;
@@ -2023,10 +1977,7 @@ fgi_status fgi_destroy(fgi_graph* g) {
     dfree(g->pool_top_dev);
     dfree(g->inv);
     dfree(g->inv_alt);
-    for (int k = 0; k < 2; ++k) {
-        if (g->ar_h[k]) (void)hipHostFree(g->ar_h[k]);
-        dfree(g->ar_d[k]);
-    }
+    for (int k = 0; k < 2; ++k) g->ar[k].release();
     for (int k = 0; k < 2; ++k)
         if (g->apub[k]) hipHostFree(g->apub[k]);
     for (int i = 0; i < 2; ++i) {
@@ -2054,12 +2005,11 @@ fgi_status fgi_destroy(fgi_graph* g) {
     }
     dfree(g->vis_bm);
     dfree(g->vis_spare);
-    if (g->flg_bm) (void)hipFree(g->flg_bm);
-    if (g->flg_cnt) (void)hipFree(g->flg_cnt);
-    for (int k = 0; k < 2; ++k)
-        if (g->flg_out[k]) (void)hipFree(g->flg_out[k]);
-    if (g->prec) (void)hipFree(g->prec);
-    if (g->pcur) (void)hipFree(g->pcur);
+    dfree(g->flg_bm);
+    dfree(g->flg_cnt);
+    for (int k = 0; k < 2; ++k) dfree(g->flg_out[k]);
+    dfree(g->prec);
+    dfree(g->pcur);
     dfree(g->cls_bm);
     dfree(g->uin_more);
     dfree(g->sum_bm);
@@ -2086,7 +2036,7 @@ fgi_status fgi_destroy(fgi_graph* g) {
     dfree(g->fold_base);
     dfree(g->xbm);
     dfree(g->fold_status);
-    if (g->scratch) hipFree(g->scratch);
+    dfree(g->scratch);
     if (g->ctr_host) hipHostFree(g->ctr_host);
     if (g->ctr_pub) hipHostFree(g->ctr_pub);
     if (g->red_pub) hipHostFree(g->red_pub);
@@ -2616,14 +2566,10 @@ static fgi_status single_only(fgi_graph* g, const char* what) {
     return g->part ? set_err(g, FGI_ESTATE, "%s: partitioned graph, use the fgi_part_* entry points", what) : FGI_OK;
 }
 static fgi_status stage_roots(fgi_graph* g, uint64_t n) {
-    if (g->roots_cap >= n && g->roots_buf) return FGI_OK;
-    dfree(g->roots_buf);
-    dfree(g->imm_buf);
     const uint64_t cap = std::max<uint64_t>(n, 4096);
-    FGI_TRY(dmalloc(g, &g->roots_buf, cap));
-    FGI_TRY(dmalloc(g, &g->imm_buf, cap));
-    g->roots_cap = cap;
-    return FGI_OK;
+    uint64_t imm_cap = g->roots_cap;   // the two grow together
+    FGI_TRY(grow(g, &g->imm_buf, &imm_cap, cap, "the staging of the roots' flags"));
+    return grow(g, &g->roots_buf, &g->roots_cap, cap, "the staging of the roots");
 }
 
 static fgi_status copy_ids(fgi_graph* g, uint32_t* out_ids, uint64_t cap, uint64_t* out_n) {
@@ -3251,19 +3197,11 @@ fgi_status Batch::check_kinds() {
 // capacities, before anything is queued: the ids of every cascade, pool headroom for the rows
 // the add_used steps may relocate (an add_used step that needs more resumes after a growth)
 fgi_status Batch::ensure_capacities() {
-    auto grow = [this](auto*& buf, uint64_t& have, uint64_t need) -> fgi_status {
-        if (have >= need) return FGI_OK;
-        dfree(buf);
-        have = 0;
-        FGI_TRY(dmalloc(g, &buf, need));
-        have = need;
-        return FGI_OK;
-    };
-    FGI_TRY(grow(g->bout, g->bout_cap, std::max<uint64_t>(1, n_waves) * g->n_handles));
+    FGI_TRY(grow(g, &g->bout, &g->bout_cap, std::max<uint64_t>(1, n_waves) * g->n_handles, "a batch's ids"));
     // the cascades' flag-only records: each of a node's two flag bits goes 0 -> 1 at most
     // once in its life and every record reports at least one such change, so a batch writes at most two per
     // node it ever holds: those of its handles and one more per begin_compute entry
-    FGI_TRY(grow(g->brec, g->brec_cap, rec_on ? 2 * ((uint64_t)g->n_handles + n_begin) : 0));
+    FGI_TRY(grow(g, &g->brec, &g->brec_cap, rec_on ? 2 * ((uint64_t)g->n_handles + n_begin) : 0, "a batch's flagged records"));
     if (n_add) FGI_TRY(ensure_pool(g, g->pool_top + std::max<uint64_t>(1ull << 20, 4 * n_add)));
     return ensure_cstart(g, std::max<uint64_t>(g->pool_top, g->pool_cap));
 }
@@ -3777,23 +3715,20 @@ static fgi_status defragment(fgi_graph* g) {
     constexpr uint64_t kMaxPool = 1ull << 32;
     if (total > kMaxPool) return FGI_OK;
     const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(total + total / 8, 1024), kMaxPool);
-    uint32_t* ncol = nullptr;
-    uint64_t* ntag = nullptr;
-    FGI_TRY(dmalloc(g, &ncol, cap));
-    if (dmalloc(g, &ntag, cap) != FGI_OK) {
-        hipFree(ncol);
-        return FGI_ENOMEM;
-    }
+    DevOwn<uint32_t> ncol;   // until they are installed
+    DevOwn<uint64_t> ntag;
+    FGI_TRY(dmalloc(g, &ncol.p, cap));
+    FGI_TRY(dmalloc(g, &ntag.p, cap));
     const uint32_t grid = (uint32_t)std::min<uint64_t>(nblk((uint64_t)H * 64), 8192);
     hipLaunchKernelGGL(k_defrag_rows, dim3(grid), dim3(256), 0, s, H, noff, g->row_off, g->row_len, g->pool_col,
-                       g->pool_tag, ncol, ntag);
+                       g->pool_tag, ncol.p, ntag.p);
     hipLaunchKernelGGL(k_defrag_apply, dim3(nblk(H)), dim3(256), 0, s, H, noff, cap64, g->row_off, g->row_cap);
     FGI_HIP(g, hipGetLastError());
     FGI_HIP(g, hipStreamSynchronize(s));
     dfree(g->pool_col);
     dfree(g->pool_tag);
-    g->pool_col = ncol;
-    g->pool_tag = ntag;
+    g->pool_col = ncol.release();
+    g->pool_tag = ntag.release();
     g->pool_cap = cap;
     g->pool_top = total;
     g->pool_epoch++;

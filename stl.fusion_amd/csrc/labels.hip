@@ -228,45 +228,30 @@ fgi_status labels_unmap_keys(fgi_graph* g, uint64_t* keys, uint64_t m) {
     return FGI_OK;
 }
 
-fgi_status labels_choose(fgi_graph* g, const uint64_t* keys, uint64_t m) {
-    if (!g->lbl_K || g->lbl_done || g->part) return FGI_OK;
+// labels_choose's work; a failure may leave fold tables half built (labels_choose drops them)
+static fgi_status labels_build(fgi_graph* g, const uint64_t* keys, uint64_t m) {
     hipStream_t s = g->stream;
     const uint32_t n = g->ext_slots;
     FGI_TRY(fold(g));   // node words are moved below: no visit may be pending
-    uint32_t *cnt = nullptr, *hist = nullptr, *cb = nullptr;
-    uint64_t *k0 = nullptr, *k1 = nullptr;
-    void* tmp = nullptr;
-    auto cleanup = [&]() {
-        for (void* p : {(void*)cnt, (void*)hist, (void*)cb, (void*)k0, (void*)k1, tmp})
-            if (p) hipFree(p);
-    };
-    // a failure leaves no hot set (lbl_hot stays 0, lbl_done false) and no half-built fold tables: a retry
-    // starts from the same state
-    auto fail = [&](hipError_t e, const char* what) {
-        cleanup();
-        for (void** p : {(void**)&g->fold_start, (void**)&g->fold_off, (void**)&g->fold_base}) {
-            if (*p) hipFree(*p);
-            *p = nullptr;
-        }
-        return hip_check(g, e, what);
-    };
-    hipError_t e;
-    if ((e = hipMalloc(&cnt, (size_t)n * 4)) != hipSuccess) return fail(e, "labels: weights");
-    if ((e = hipMalloc(&hist, kLabelClasses * 4)) != hipSuccess) return fail(e, "labels: histogram");
-    if ((e = hipMalloc(&k0, (size_t)n * 8)) != hipSuccess) return fail(e, "labels: keys");
-    if ((e = hipMalloc(&k1, (size_t)n * 8)) != hipSuccess) return fail(e, "labels: keys");
-    (void)hipMemsetAsync(cnt, 0, (size_t)n * 4, s);
-    (void)hipMemsetAsync(hist, 0, kLabelClasses * 4, s);
+    Tmp tcnt, thist, tcb, tk0, tk1, ttmp;
+    uint32_t *cnt, *hist, *cb;
+    uint64_t *k0, *k1;
+    char* tmp;
+    FGI_TRY(tmalloc(g, tcnt, &cnt, n));
+    FGI_TRY(tmalloc(g, thist, &hist, kLabelClasses));
+    FGI_TRY(tmalloc(g, tk0, &k0, n));
+    FGI_TRY(tmalloc(g, tk1, &k1, n));
+    FGI_HIP(g, hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
+    FGI_HIP(g, hipMemsetAsync(hist, 0, kLabelClasses * 4, s));
     if (m) hipLaunchKernelGGL(k_lbl_weights, dim3(std::min<uint32_t>(nblk(m), 16384)), dim3(256), 0, s, m, keys, n, cnt);
     hipLaunchKernelGGL(k_lbl_keys, dim3(nblk(n)), dim3(256), 0, s, n, cnt, k0, hist);
     size_t tb = 0;
-    if ((e = rocprim::radix_sort_keys_desc(nullptr, tb, k0, k1, (size_t)n, 0, 64, s)) != hipSuccess) return fail(e, "labels: sort");
-    if ((e = hipMalloc(&tmp, tb)) != hipSuccess) return fail(e, "labels: sort");
-    if ((e = rocprim::radix_sort_keys_desc(tmp, tb, k0, k1, (size_t)n, 0, 64, s)) != hipSuccess) return fail(e, "labels: sort");
+    FGI_HIP(g, rocprim::radix_sort_keys_desc(nullptr, tb, k0, k1, (size_t)n, 0, 64, s));
+    FGI_TRY(tmalloc(g, ttmp, &tmp, tb));
+    FGI_HIP(g, rocprim::radix_sort_keys_desc(tmp, tb, k0, k1, (size_t)n, 0, 64, s));
     std::vector<uint32_t> h(kLabelClasses);
-    if ((e = hipMemcpyAsync(h.data(), hist, kLabelClasses * 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (e = hipStreamSynchronize(s)) != hipSuccess)
-        return fail(e, "labels: histogram");
+    FGI_HIP(g, hipMemcpyAsync(h.data(), hist, kLabelClasses * 4, hipMemcpyDeviceToHost, s));
+    FGI_HIP(g, hipStreamSynchronize(s));
     // the hot set: whole classes from the heaviest down, at most an eighth of the slots (and the
     // prefix capacity), at most kMaxHotClasses classes; weightless slots stay cold
     const uint64_t cap = std::min<uint64_t>(g->lbl_K, std::max<uint64_t>(1, n / 8));
@@ -282,39 +267,27 @@ fgi_status labels_choose(fgi_graph* g, const uint64_t* keys, uint64_t m) {
     bases.push_back((uint32_t)H);
     const uint32_t tiles = (uint32_t)(((uint64_t)g->ext_handles + kFoldTile - 1) / kFoldTile);
     // each map on its own: a retry after a failed allocation finds the one that exists and makes the other
-    if (!g->s2l && (e = hipMalloc(&g->s2l, (size_t)n * 4)) != hipSuccess) {
-        g->s2l = nullptr;
-        return fail(e, "labels: slot map");
-    }
-    if (!g->l2s && (e = hipMalloc(&g->l2s, (size_t)g->lbl_K * 4)) != hipSuccess) {
-        g->l2s = nullptr;
-        return fail(e, "labels: label map");
-    }
-    (void)hipMemsetAsync(g->s2l, 0xFF, (size_t)n * 4, s);
-    (void)hipMemsetAsync(g->l2s, 0xFF, (size_t)g->lbl_K * 4, s);
+    if (!g->s2l) FGI_TRY(dmalloc(g, &g->s2l, n));
+    if (!g->l2s) FGI_TRY(dmalloc(g, &g->l2s, g->lbl_K));
+    FGI_HIP(g, hipMemsetAsync(g->s2l, 0xFF, (size_t)n * 4, s));
+    FGI_HIP(g, hipMemsetAsync(g->l2s, 0xFF, (size_t)g->lbl_K * 4, s));
+    std::vector<uint32_t> tb_host(tiles + 1, 0);   // (outlives the stream's copies from it)
     if (H) {
         hipLaunchKernelGGL(k_lbl_assign, dim3(nblk(H)), dim3(256), 0, s, (uint32_t)H, k1, g->s2l, g->l2s);
-        if (g->fold_start) hipFree(g->fold_start);
-        g->fold_start = nullptr;
-        if ((e = hipMalloc(&g->fold_start, (size_t)ncls * (tiles + 1) * 4)) != hipSuccess) return fail(e, "labels: fold table");
-        if ((e = hipMalloc(&cb, bases.size() * 4)) != hipSuccess) return fail(e, "labels: class bases");
-        if ((e = hipMemcpyAsync(cb, bases.data(), bases.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
-            return fail(e, "labels: class bases");
+        dfree(g->fold_start);
+        FGI_TRY(dmalloc(g, &g->fold_start, (size_t)ncls * (tiles + 1)));
+        FGI_TRY(tmalloc(g, tcb, &cb, bases.size()));
+        FGI_HIP(g, hipMemcpyAsync(cb, bases.data(), bases.size() * 4, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_lbl_fold_start, dim3(nblk((uint64_t)ncls * (tiles + 1))), dim3(256), 0, s, ncls, tiles, cb,
                            g->l2s, g->fold_start);
         // the fold's per-tile offset runs: tile counts, their prefix (host: tiles words), the offsets
-        for (void* p : {(void*)g->fold_off, (void*)g->fold_base})
-            if (p) hipFree(p);
-        g->fold_off = nullptr;
-        g->fold_base = nullptr;
-        if ((e = hipMalloc(&g->fold_off, ((size_t)H + 8ull * tiles + 8) * 2)) != hipSuccess ||
-            (e = hipMalloc(&g->fold_base, (size_t)(tiles + 1) * 4)) != hipSuccess)
-            return fail(e, "labels: fold offsets");
+        dfree(g->fold_off);
+        dfree(g->fold_base);
+        FGI_TRY(dmalloc(g, &g->fold_off, (size_t)H + 8ull * tiles + 8));
+        FGI_TRY(dmalloc(g, &g->fold_base, (size_t)tiles + 1));
         hipLaunchKernelGGL(k_lbl_tile_tot, dim3(nblk(tiles)), dim3(256), 0, s, ncls, tiles, g->fold_start, g->fold_base);
-        std::vector<uint32_t> tb_host(tiles + 1, 0);
-        if ((e = hipMemcpyAsync(tb_host.data(), g->fold_base, (size_t)tiles * 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-            (e = hipStreamSynchronize(s)) != hipSuccess)
-            return fail(e, "labels: fold tile counts");
+        FGI_HIP(g, hipMemcpyAsync(tb_host.data(), g->fold_base, (size_t)tiles * 4, hipMemcpyDeviceToHost, s));
+        FGI_HIP(g, hipStreamSynchronize(s));
         // each tile's run starts 16-byte aligned (8 entries): the fold stages it with 16-byte loads
         uint64_t run = 0, covered = 0;
         for (uint32_t t = 0; t <= tiles; ++t) {
@@ -323,17 +296,11 @@ fgi_status labels_choose(fgi_graph* g, const uint64_t* keys, uint64_t m) {
             run += (c + 7u) & ~7u;
             covered += c;
         }
-        if (covered != H) {
-            cleanup();
+        if (covered != H)
             return set_err(g, FGI_EDEVICE, "labels: fold runs cover %llu of %llu hot labels", (unsigned long long)covered,
                            (unsigned long long)H);
-        }
-        if (run > (1ull << 32)) {
-            cleanup();
-            return set_err(g, FGI_ENOTSUP, "labels: fold offsets exceed 2^32 entries");
-        }
-        if ((e = hipMemcpyAsync(g->fold_base, tb_host.data(), (size_t)(tiles + 1) * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
-            return fail(e, "labels: fold bases");
+        if (run > (1ull << 32)) return set_err(g, FGI_ENOTSUP, "labels: fold offsets exceed 2^32 entries");
+        FGI_HIP(g, hipMemcpyAsync(g->fold_base, tb_host.data(), (size_t)(tiles + 1) * 4, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_lbl_fold_off, dim3(tiles), dim3(256), 0, s, ncls, g->fold_start, g->fold_base, g->l2s,
                            g->fold_off);
         hipLaunchKernelGGL(k_lbl_move_words, dim3(nblk(H)), dim3(256), 0, s, (uint32_t)H, g->l2s, g->lbl_K,
@@ -342,8 +309,8 @@ fgi_status labels_choose(fgi_graph* g, const uint64_t* keys, uint64_t m) {
             hipLaunchKernelGGL(k_lbl_home, dim3(nblk(g->n_detached)), dim3(256), 0, s, g->n_detached, g->home, n, g->s2l,
                                g->lbl_K);
     }
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(s)) != hipSuccess) return fail(e, "labels");
-    cleanup();
+    FGI_HIP(g, hipGetLastError());
+    FGI_HIP(g, hipStreamSynchronize(s));
     g->lbl_hot = (uint32_t)H;
     g->lbl_ncls = ncls;
     g->fold_tiles = tiles;
@@ -354,6 +321,19 @@ fgi_status labels_choose(fgi_graph* g, const uint64_t* keys, uint64_t m) {
         fprintf(stderr, "[fgi] labels: %llu hot slots of %u in %u classes (capacity %u)\n", (unsigned long long)H, n, ncls,
                 g->lbl_K);
     return FGI_OK;
+}
+
+fgi_status labels_choose(fgi_graph* g, const uint64_t* keys, uint64_t m) {
+    if (!g->lbl_K || g->lbl_done || g->part) return FGI_OK;
+    const fgi_status st = labels_build(g, keys, m);
+    // a failure leaves no hot set (lbl_hot stays 0, lbl_done false) and no half-built fold tables: a retry
+    // starts from the same state
+    if (st != FGI_OK) {
+        dfree(g->fold_start);
+        dfree(g->fold_off);
+        dfree(g->fold_base);
+    }
+    return st;
 }
 
 }  // namespace fgi

@@ -144,7 +144,7 @@ struct PartState {
     unsigned long long* cur_all = nullptr;
     std::vector<uint32_t> u32_host[2];         // allreduce_u32's host copies (in-process groups: LocalComm::meet)
     uint32_t* roots_codes = nullptr;           // fgi_part_invalidate's roots as codes (partition codes)
-    uint32_t roots_cap = 0;
+    uint64_t roots_cap = 0;
 };
 
 static PartState* ps(fgi_graph* g) { return reinterpret_cast<PartState*>(g->part); }
@@ -885,14 +885,13 @@ fgi_status part_kill_used(fgi_graph* g, std::vector<uint32_t> slots) {
     if (slots.empty() || p->in_n == 0) return FGI_OK;
     std::sort(slots.begin(), slots.end());
     slots.erase(std::unique(slots.begin(), slots.end()), slots.end());
-    uint32_t* d = nullptr;
-    if (hipMalloc(&d, slots.size() * 4) != hipSuccess) return set_err(g, FGI_ENOMEM, "displaced-slot list");
-    hipMemcpyAsync(d, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, g->stream);
+    Tmp td;
+    uint32_t* d;
+    FGI_TRY(tmalloc(g, td, &d, slots.size()));
+    FGI_HIP(g, hipMemcpyAsync(d, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, g->stream));
     hipLaunchKernelGGL(k_in_kill, dim3((uint32_t)((p->in_n + 255) / 256)), dim3(256), 0, g->stream, p->in_n, p->in_keys, p->in_tags, d,
                        (uint32_t)slots.size());
-    const hipError_t e = hipStreamSynchronize(g->stream);
-    hipFree(d);
-    FGI_HIP(g, e);
+    FGI_HIP(g, hipStreamSynchronize(g->stream));
     return FGI_OK;
 }
 
@@ -1253,16 +1252,17 @@ __global__ void k_pc_global(uint64_t n, uint32_t* a, const uint32_t* __restrict_
 fgi_status scan_flags(fgi_graph* g, const uint32_t* flag, uint32_t* pos, uint64_t m, uint64_t* total) {
     hipStream_t s = g->stream;
     size_t tb = 0;
-    rocprim::exclusive_scan(nullptr, tb, flag, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), s);
-    void* tmp = nullptr;
-    FGI_HIP(g, hipMalloc(&tmp, std::max<size_t>(tb, 16)));
-    rocprim::exclusive_scan(tmp, tb, flag, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), s);
+    FGI_HIP(g, rocprim::exclusive_scan(nullptr, tb, flag, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), s));
+    Tmp tt;
+    char* tmp;
+    FGI_TRY(tmalloc(g, tt, &tmp, tb));
+    FGI_HIP(g, rocprim::exclusive_scan(tmp, tb, flag, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), s));
     uint32_t lp = 0, lf = 0;
-    hipMemcpyAsync(&lp, pos + m - 1, 4, hipMemcpyDeviceToHost, s);
-    hipMemcpyAsync(&lf, flag + m - 1, 4, hipMemcpyDeviceToHost, s);
-    const hipError_t e = hipStreamSynchronize(s);
-    hipFree(tmp);
+    hipError_t e = hipMemcpyAsync(&lp, pos + m - 1, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&lf, flag + m - 1, 4, hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);   // also when a copy failed: the other may be writing lp
     FGI_HIP(g, e);
+    FGI_HIP(g, es);
     *total = (uint64_t)lp + lf;
     return FGI_OK;
 }
@@ -1281,62 +1281,44 @@ fgi_status part_codes_choose(fgi_graph* g, uint32_t* weight_dev) {
     const uint32_t N = p->v.n_global, B = p->v.block, base = p->v.base, nl = p->v.n_local;
     hipStream_t s = g->stream;
     FGI_TRY(fold(g));
-    uint64_t *k0 = nullptr, *k1 = nullptr, *ver_old = nullptr;
-    uint32_t *w_old = nullptr, *used_old = nullptr;
-    unsigned long long* node_old = nullptr;
-    void* tmp = nullptr;
-    fgi_status st = FGI_OK;
-    do {
-        if (!g->pg_gc && (hipMalloc(&g->pg_gc, (size_t)N * 4) != hipSuccess || hipMalloc(&g->pg_ig, (size_t)N * 4) != hipSuccess)) {
-            st = set_err(g, FGI_ENOMEM, "partition codes");
-            break;
-        }
-        if (hipMalloc(&k0, (size_t)N * 8) != hipSuccess || hipMalloc(&k1, (size_t)N * 8) != hipSuccess) {
-            st = set_err(g, FGI_ENOMEM, "partition code keys");
-            break;
-        }
-        hipLaunchKernelGGL(k_pc_keys, dim3(nblk(N)), dim3(256), 0, s, N, B, weight_dev, k0);
-        size_t tb = 0;
-        rocprim::radix_sort_keys(nullptr, tb, k0, k1, (size_t)N, 0, 56, s);
-        if (hipMalloc(&tmp, std::max<size_t>(tb, 16)) != hipSuccess) {
-            st = set_err(g, FGI_ENOMEM, "partition code sort");
-            break;
-        }
-        rocprim::radix_sort_keys(tmp, tb, k0, k1, (size_t)N, 0, 56, s);
-        uint32_t pgrid = 0, ptpb = 0;
-        pull_geometry(g, &pgrid, &ptpb);
-        const uint32_t T = pgrid ? ptpb * kPullTile : 0u;   // the slots a pull block owns
-        hipLaunchKernelGGL(k_pc_tables, dim3(nblk(N)), dim3(256), 0, s, N, B, T, k1, g->pg_gc, g->pg_ig);
-        if (hipMalloc(&ver_old, (size_t)N * 8) != hipSuccess || hipMalloc(&w_old, (size_t)N * 4) != hipSuccess ||
-            hipMalloc(&node_old, (size_t)std::max<uint32_t>(nl, 1) * 8) != hipSuccess ||
-            hipMalloc(&used_old, (size_t)std::max<uint32_t>(nl, 1) * 4) != hipSuccess) {
-            st = set_err(g, FGI_ENOMEM, "partition code moves");
-            break;
-        }
-        if (hipMemcpyAsync(ver_old, p->v.ver_all, (size_t)N * 8, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(w_old, weight_dev, (size_t)N * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            (nl && hipMemcpyAsync(node_old, g->node, (size_t)nl * 8, hipMemcpyDeviceToDevice, s) != hipSuccess) ||
-            (nl && hipMemcpyAsync(used_old, g->used_cnt, (size_t)nl * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)) {
-            st = set_err(g, FGI_EDEVICE, "partition code moves");
-            break;
-        }
-        hipLaunchKernelGGL(k_pc_move_global, dim3(nblk(N)), dim3(256), 0, s, N, g->pg_gc, ver_old, p->v.ver_all, w_old,
-                           weight_dev);
-        if (nl)
-            hipLaunchKernelGGL(k_pc_move_local, dim3(nblk(nl)), dim3(256), 0, s, nl, base, g->pg_gc, node_old,
-                               reinterpret_cast<unsigned long long*>(g->node), used_old, g->used_cnt);
-        g->pg_gc_h.resize(N);
-        g->pg_ig_h.resize(N);
-        if (hipMemcpyAsync(g->pg_gc_h.data(), g->pg_gc, (size_t)N * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(g->pg_ig_h.data(), g->pg_ig, (size_t)N * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            st = set_err(g, FGI_EDEVICE, "partition codes");
-            break;
-        }
-    } while (0);
-    for (void* q : {(void*)k0, (void*)k1, (void*)ver_old, (void*)w_old, (void*)node_old, (void*)used_old, tmp})
-        if (q) hipFree(q);
-    if (st != FGI_OK) return st;
+    if (!g->pg_gc) FGI_TRY(dmalloc(g, &g->pg_gc, N));
+    if (!g->pg_ig) FGI_TRY(dmalloc(g, &g->pg_ig, N));
+    Tmp tk0, tk1, tt, tv, tw, tn, tu;
+    uint64_t *k0, *k1, *ver_old;
+    uint32_t *w_old, *used_old;
+    unsigned long long* node_old;
+    char* tmp;
+    FGI_TRY(tmalloc(g, tk0, &k0, N));
+    FGI_TRY(tmalloc(g, tk1, &k1, N));
+    hipLaunchKernelGGL(k_pc_keys, dim3(nblk(N)), dim3(256), 0, s, N, B, weight_dev, k0);
+    size_t tb = 0;
+    FGI_HIP(g, rocprim::radix_sort_keys(nullptr, tb, k0, k1, (size_t)N, 0, 56, s));
+    FGI_TRY(tmalloc(g, tt, &tmp, tb));
+    FGI_HIP(g, rocprim::radix_sort_keys(tmp, tb, k0, k1, (size_t)N, 0, 56, s));
+    uint32_t pgrid = 0, ptpb = 0;
+    pull_geometry(g, &pgrid, &ptpb);
+    const uint32_t T = pgrid ? ptpb * kPullTile : 0u;   // the slots a pull block owns
+    hipLaunchKernelGGL(k_pc_tables, dim3(nblk(N)), dim3(256), 0, s, N, B, T, k1, g->pg_gc, g->pg_ig);
+    FGI_TRY(tmalloc(g, tv, &ver_old, N));
+    FGI_TRY(tmalloc(g, tw, &w_old, N));
+    FGI_TRY(tmalloc(g, tn, &node_old, nl));
+    FGI_TRY(tmalloc(g, tu, &used_old, nl));
+    FGI_HIP(g, hipMemcpyAsync(ver_old, p->v.ver_all, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
+    FGI_HIP(g, hipMemcpyAsync(w_old, weight_dev, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
+    if (nl) {
+        FGI_HIP(g, hipMemcpyAsync(node_old, g->node, (size_t)nl * 8, hipMemcpyDeviceToDevice, s));
+        FGI_HIP(g, hipMemcpyAsync(used_old, g->used_cnt, (size_t)nl * 4, hipMemcpyDeviceToDevice, s));
+    }
+    hipLaunchKernelGGL(k_pc_move_global, dim3(nblk(N)), dim3(256), 0, s, N, g->pg_gc, ver_old, p->v.ver_all, w_old,
+                       weight_dev);
+    if (nl)
+        hipLaunchKernelGGL(k_pc_move_local, dim3(nblk(nl)), dim3(256), 0, s, nl, base, g->pg_gc, node_old,
+                           reinterpret_cast<unsigned long long*>(g->node), used_old, g->used_cnt);
+    g->pg_gc_h.resize(N);
+    g->pg_ig_h.resize(N);
+    FGI_HIP(g, hipMemcpyAsync(g->pg_gc_h.data(), g->pg_gc, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+    FGI_HIP(g, hipMemcpyAsync(g->pg_ig_h.data(), g->pg_ig, (size_t)N * 4, hipMemcpyDeviceToHost, s));
+    FGI_HIP(g, hipStreamSynchronize(s));
     // the table's fingerprint: the wave's first all-reduce checks that every rank chose the same codes (each
     // rank chooses them alone, from the same arrays; a rank given other arrays would number slots otherwise)
     uint64_t hsh = 0xcbf29ce484222325ull;
@@ -1364,77 +1346,47 @@ fgi_status part_rebuild_lists(fgi_graph* g) {
     if (p->v.block % 32 != 0) return FGI_OK;   // pull levels all-gather whole bitmap words per rank
     FGI_HIP(g, hipMemsetAsync(g->uin_len, 0, (size_t)g->n_slots * 4, s));
     FGI_HIP(g, hipMemsetAsync(g->uin_off, 0, (size_t)g->n_slots * 8, s));
-    if (!g->uin_src) {
-        FGI_HIP(g, hipMalloc(&g->uin_src, 1024 * 4));
-        g->uin_cap = 1024;
-    }
-    uint32_t *flag = nullptr, *pos = nullptr, *keep = nullptr, *kpos = nullptr;
-    uint64_t *k1 = nullptr, *k2 = nullptr;
-    void* st = nullptr;
-    fgi_status rc = FGI_OK;
+    if (!g->uin_src) FGI_TRY(grow(g, &g->uin_src, &g->uin_cap, 1024, "the dependency lists"));
+    Tmp tf, tp;
+    uint32_t *flag = nullptr, *pos = nullptr;
     uint64_t mi = 0;
-    do {
-        if (m) {
-            if (hipMalloc(&flag, m * 4) != hipSuccess || hipMalloc(&pos, m * 4) != hipSuccess) {
-                rc = set_err(g, FGI_ENOMEM, "dependency-list build buffers");
-                break;
-            }
-            hipLaunchKernelGGL(k_in_live, dim3(nblk(m)), dim3(256), 0, s, m, p->in_keys, p->in_tags,
-                               reinterpret_cast<const unsigned long long*>(g->node), flag);
-            rc = scan_flags(g, flag, pos, m, &mi);
-            if (rc != FGI_OK) break;
-        }
-        if (mi == 0) {
-            rc = build_in_heads(g);
-            break;
-        }
-        if (hipMalloc(&k1, mi * 8) != hipSuccess || hipMalloc(&k2, mi * 8) != hipSuccess ||
-            hipMalloc(&keep, mi * 4) != hipSuccess || hipMalloc(&kpos, mi * 4) != hipSuccess) {
-            rc = set_err(g, FGI_ENOMEM, "dependency-list build buffers");
-            break;
-        }
+    if (m) {
+        FGI_TRY(tmalloc(g, tf, &flag, m));
+        FGI_TRY(tmalloc(g, tp, &pos, m));
+        hipLaunchKernelGGL(k_in_live, dim3(nblk(m)), dim3(256), 0, s, m, p->in_keys, p->in_tags,
+                           reinterpret_cast<const unsigned long long*>(g->node), flag);
+        FGI_TRY(scan_flags(g, flag, pos, m, &mi));
+    }
+    if (mi) {
+        Tmp tk1, tk2, tkeep, tkpos, tst;
+        uint64_t *k1, *k2;
+        uint32_t *keep, *kpos;
+        char* st;
+        FGI_TRY(tmalloc(g, tk1, &k1, mi));
+        FGI_TRY(tmalloc(g, tk2, &k2, mi));
+        FGI_TRY(tmalloc(g, tkeep, &keep, mi));
+        FGI_TRY(tmalloc(g, tkpos, &kpos, mi));
         hipLaunchKernelGGL(k_compact64, dim3(nblk(m)), dim3(256), 0, s, m, p->in_keys, flag, pos, k1);
-        hipFree(flag);
-        hipFree(pos);
-        flag = pos = nullptr;
+        tf.reset();   // before the sort's buffers
+        tp.reset();
         size_t sb = 0;
-        rocprim::radix_sort_keys(nullptr, sb, k1, k2, (size_t)mi, 0, 64, s);
-        if (hipMalloc(&st, std::max(sb, (size_t)16)) != hipSuccess) {
-            rc = set_err(g, FGI_ENOMEM, "sort temp");
-            break;
-        }
-        rocprim::radix_sort_keys(st, sb, k1, k2, (size_t)mi, 0, 64, s);
+        FGI_HIP(g, rocprim::radix_sort_keys(nullptr, sb, k1, k2, (size_t)mi, 0, 64, s));
+        FGI_TRY(tmalloc(g, tst, &st, sb));
+        FGI_HIP(g, rocprim::radix_sort_keys(st, sb, k1, k2, (size_t)mi, 0, 64, s));
         hipLaunchKernelGGL(k_in_part_unique, dim3(nblk(mi)), dim3(256), 0, s, mi, k2, keep);
         uint64_t total = 0;
-        rc = scan_flags(g, keep, kpos, mi, &total);
-        if (rc != FGI_OK) break;
-        if (total > g->uin_cap) {
-            hipFree(g->uin_src);
-            g->uin_src = nullptr;
-            if (hipMalloc(&g->uin_src, std::max<uint64_t>(total, 1024) * 4) != hipSuccess) {
-                rc = set_err(g, FGI_ENOMEM, "dependency lists");
-                break;
-            }
-            g->uin_cap = std::max<uint64_t>(total, 1024);
-        }
+        FGI_TRY(scan_flags(g, keep, kpos, mi, &total));
+        // (the lists are rebuilt whole: nothing of the old ones is kept)
+        FGI_TRY(grow(g, &g->uin_src, &g->uin_cap, std::max<uint64_t>(total, 1024), "the dependency lists"));
         hipLaunchKernelGGL(k_in_part_rows, dim3(nblk(mi)), dim3(256), 0, s, mi, k2, keep, kpos, g->uin_src, g->uin_off,
                            g->uin_len);
         hipLaunchKernelGGL(k_in_part_fix, dim3(nblk(g->n_slots)), dim3(256), 0, s, g->n_slots, g->uin_off, g->uin_len);
-        rc = sort_in_lists(g, total, p->weight, p->v.n_global);
-        if (rc != FGI_OK) break;
-        rc = build_in_heads(g);
-        if (rc != FGI_OK) break;
-        if (hipStreamSynchronize(s) != hipSuccess) rc = set_err(g, FGI_EDEVICE, "dependency-list build");
-    } while (0);
-    hipFree(flag);
-    hipFree(pos);
-    hipFree(k1);
-    hipFree(k2);
-    hipFree(keep);
-    hipFree(kpos);
-    hipFree(st);
-    if (rc == FGI_OK) g->uin_epoch = g->mut_epoch;   // rows, versions and lists agree
-    return rc;
+        FGI_TRY(sort_in_lists(g, total, p->weight, p->v.n_global));
+    }
+    FGI_TRY(build_in_heads(g));
+    FGI_HIP(g, hipStreamSynchronize(s));
+    g->uin_epoch = g->mut_epoch;   // rows, versions and lists agree
+    return FGI_OK;
 }
 
 fgi_status part_ensure_lists(fgi_graph* g) {
@@ -1476,20 +1428,18 @@ static fgi_status part_store_in(fgi_graph* g, const uint64_t* keys, const uint64
     if (m == 0) return FGI_OK;
     if (p->in_n + m > p->in_cap) {
         const uint64_t cap = std::max<uint64_t>(p->in_n + m, p->in_cap + p->in_cap / 2);
-        uint64_t *nk = nullptr, *nt = nullptr;
-        if (hipMalloc(&nk, cap * 8) != hipSuccess || hipMalloc(&nt, cap * 8) != hipSuccess) {
-            hipFree(nk);
+        DevOwn<uint64_t> nk, nt;   // until they are installed
+        if (hipMalloc(&nk.p, cap * 8) != hipSuccess || hipMalloc(&nt.p, cap * 8) != hipSuccess)
             return set_err(g, FGI_ENOMEM, "dependency-entry store");
-        }
         if (p->in_n) {
-            FGI_HIP(g, hipMemcpyAsync(nk, p->in_keys, p->in_n * 8, hipMemcpyDeviceToDevice, g->stream));
-            FGI_HIP(g, hipMemcpyAsync(nt, p->in_tags, p->in_n * 8, hipMemcpyDeviceToDevice, g->stream));
+            FGI_HIP(g, hipMemcpyAsync(nk.p, p->in_keys, p->in_n * 8, hipMemcpyDeviceToDevice, g->stream));
+            FGI_HIP(g, hipMemcpyAsync(nt.p, p->in_tags, p->in_n * 8, hipMemcpyDeviceToDevice, g->stream));
             FGI_HIP(g, hipStreamSynchronize(g->stream));
         }
         hipFree(p->in_keys);
         hipFree(p->in_tags);
-        p->in_keys = nk;
-        p->in_tags = nt;
+        p->in_keys = nk.release();
+        p->in_tags = nt.release();
         p->in_cap = cap;
     }
     FGI_HIP(g, hipMemcpyAsync(p->in_keys + p->in_n, keys, m * 8, hipMemcpyDefault, g->stream));
@@ -1676,26 +1626,29 @@ fgi_status fgi_part_local_invalidate(fgi_graph* const* gs, uint32_t P, uint32_t 
         ts.emplace_back([&, r]() {
             fgi_graph* g = gs[r];
             hipSetDevice(g->device);
-            uint32_t* rd = nullptr;
-            uint8_t* id = nullptr;
-            fgi_status s = FGI_OK;
-            if (n_roots && (hipMalloc(&rd, n_roots * 4) != hipSuccess ||
-                            (immediately && hipMalloc(&id, n_roots) != hipSuccess)))
-                s = set_err(g, FGI_ENOMEM, "root buffers");
+            // the rank's own graph and stream only: its temporaries come from its own cache
             std::vector<uint32_t> mapped;
             const uint32_t* rr = part_codes_in(g, n_roots, roots, mapped);
-            if (s == FGI_OK && n_roots) {
-                if (hipMemcpy(rd, rr, n_roots * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                    (immediately && hipMemcpy(id, immediately, n_roots, hipMemcpyHostToDevice) != hipSuccess))
-                    s = set_err(g, FGI_EDEVICE, "root copy");
-            }
+            Tmp tr, ti;
+            uint32_t* rd = nullptr;
+            uint8_t* id = nullptr;
+            auto wave = [&]() -> fgi_status {
+                if (n_roots) {
+                    FGI_TRY(tmalloc(g, tr, &rd, n_roots));
+                    FGI_HIP(g, hipMemcpyAsync(rd, rr, (size_t)n_roots * 4, hipMemcpyHostToDevice, g->stream));
+                    if (immediately) {
+                        FGI_TRY(tmalloc(g, ti, &id, n_roots));
+                        FGI_HIP(g, hipMemcpyAsync(id, immediately, n_roots, hipMemcpyHostToDevice, g->stream));
+                    }
+                    FGI_HIP(g, hipStreamSynchronize(g->stream));   // pageable sources
+                }
+                FGI_TRY(run_part_wave(g, n_roots, rd, id, stats ? stats + r : nullptr));
+                part_out_mark(g, kPoutWave);
+                return FGI_OK;
+            };
             part_out_mark(g, kPoutOther);   // until the rank's wave stands
-            if (s == FGI_OK) s = run_part_wave(g, n_roots, rd, id, stats ? stats + r : nullptr);
-            if (s == FGI_OK) part_out_mark(g, kPoutWave);
-            if (s != FGI_OK) c0->grp->fail();
-            hipFree(rd);
-            hipFree(id);
-            st[r] = s;
+            st[r] = wave();
+            if (st[r] != FGI_OK) c0->grp->fail();
         });
     }
     for (auto& t : ts) t.join();
@@ -1842,99 +1795,63 @@ fgi_status fgi_part_synth_rmat(fgi_graph* g, uint32_t scale, uint32_t edge_facto
     // the rank's rows and dependency entries, generated by edge-index range (k_rmat_part)
     const uint64_t m = (uint64_t)edge_factor << scale;
     const uint64_t per = (m + kGenBlocks - 1) / kGenBlocks;
-    unsigned long long *cnt = nullptr, *off = nullptr;
-    uint64_t *rows = nullptr, *ins = nullptr, *tags = nullptr, *rtags = nullptr;
-    auto cleanup = [&]() {
-        hipFree(cnt);
-        hipFree(off);
-        hipFree(rows);
-        hipFree(ins);
-        hipFree(tags);
-        hipFree(rtags);
-    };
-    fgi_status st = FGI_OK;
-    do {
-        if (hipMalloc(&cnt, 2 * kGenBlocks * 8) != hipSuccess || hipMalloc(&off, 2 * kGenBlocks * 8) != hipSuccess) {
-            st = set_err(g, FGI_ENOMEM, "generator counts");
-            break;
+    Tmp tcnt, toff, trows, tins, ttags, trtags;
+    unsigned long long *cnt, *off;
+    uint64_t *rows, *ins, *tags, *rtags = nullptr;
+    FGI_TRY(tmalloc(g, tcnt, &cnt, 2 * kGenBlocks));
+    FGI_TRY(tmalloc(g, toff, &off, 2 * kGenBlocks));
+    hipLaunchKernelGGL(k_rmat_part, dim3(kGenBlocks), dim3(256), 0, s, m, per, scale, seed, base, nl, stale_pct,
+                       stale_seed, 0, cnt, (const unsigned long long*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr,
+                       p->weight, (const uint32_t*)nullptr, (uint64_t*)nullptr);
+    if (choose) {   // the weights by slot are complete: codes, then the versions at them
+        g->pool_top = 0;   // the rows are rebuilt below
+        FGI_TRY(part_codes_choose(g, p->weight));
+        hipLaunchKernelGGL(k_versions_local, dim3((nl + 255) / 256), dim3(256), 0, s, nl, base, seed,
+                           reinterpret_cast<unsigned long long*>(g->node), (const uint32_t*)g->pg_ig);
+        hipLaunchKernelGGL(k_versions_all, dim3((N + 255) / 256), dim3(256), 0, s, N, seed, p->v.ver_all,
+                           (const uint32_t*)g->pg_ig);
+    } else if (g->lbl_perm) {   // the weights by slot into code order
+        Tmp tw2;
+        uint32_t* w2;
+        FGI_TRY(tmalloc(g, tw2, &w2, N));
+        FGI_HIP(g, hipMemcpyAsync(w2, p->weight, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
+        // the weights only: ver_all was written at the codes above
+        hipLaunchKernelGGL(k_pc_move_global, dim3(nblk(N)), dim3(256), 0, s, N, (const uint32_t*)g->pg_gc,
+                           (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)w2, p->weight);
+        FGI_HIP(g, hipGetLastError());
+    }
+    std::vector<unsigned long long> hc(2 * kGenBlocks), ho(2 * kGenBlocks);
+    FGI_HIP(g, hipMemcpyAsync(hc.data(), cnt, hc.size() * 8, hipMemcpyDeviceToHost, s));
+    FGI_HIP(g, hipStreamSynchronize(s));
+    uint64_t tot[2] = {0, 0};
+    for (int c = 0; c < 2; ++c)
+        for (uint32_t b = 0; b < kGenBlocks; ++b) {
+            ho[c * kGenBlocks + b] = tot[c];
+            tot[c] += hc[c * kGenBlocks + b];
         }
-        hipLaunchKernelGGL(k_rmat_part, dim3(kGenBlocks), dim3(256), 0, s, m, per, scale, seed, base, nl, stale_pct,
-                           stale_seed, 0, cnt, (const unsigned long long*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr,
-                           p->weight, (const uint32_t*)nullptr, (uint64_t*)nullptr);
-        if (choose) {   // the weights by slot are complete: codes, then the versions at them
-            g->pool_top = 0;   // the rows are rebuilt below
-            st = part_codes_choose(g, p->weight);
-            if (st != FGI_OK) break;
-            hipLaunchKernelGGL(k_versions_local, dim3((nl + 255) / 256), dim3(256), 0, s, nl, base, seed,
-                               reinterpret_cast<unsigned long long*>(g->node), (const uint32_t*)g->pg_ig);
-            hipLaunchKernelGGL(k_versions_all, dim3((N + 255) / 256), dim3(256), 0, s, N, seed, p->v.ver_all,
-                               (const uint32_t*)g->pg_ig);
-        } else if (g->lbl_perm) {   // the weights by slot into code order
-            uint32_t* w2 = nullptr;
-            if (hipMalloc(&w2, (size_t)N * 4) != hipSuccess) {
-                st = set_err(g, FGI_ENOMEM, "weights");
-                break;
-            }
-            hipError_t e = hipMemcpyAsync(w2, p->weight, (size_t)N * 4, hipMemcpyDeviceToDevice, s);
-            // the weights only: ver_all was written at the codes above
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_pc_move_global, dim3(nblk(N)), dim3(256), 0, s, N, (const uint32_t*)g->pg_gc,
-                                   (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)w2, p->weight);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            hipFree(w2);
-            if (e != hipSuccess) {
-                st = hip_check(g, e, "weights into code order");
-                break;
-            }
-        }
-        std::vector<unsigned long long> hc(2 * kGenBlocks), ho(2 * kGenBlocks);
-        if (hipMemcpyAsync(hc.data(), cnt, hc.size() * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            st = set_err(g, FGI_EDEVICE, "generator count pass");
-            break;
-        }
-        uint64_t tot[2] = {0, 0};
-        for (int c = 0; c < 2; ++c)
-            for (uint32_t b = 0; b < kGenBlocks; ++b) {
-                ho[c * kGenBlocks + b] = tot[c];
-                tot[c] += hc[c * kGenBlocks + b];
-            }
-        const uint64_t mo = tot[0], mi = tot[1];
-        if (hipMalloc(&rows, std::max<uint64_t>(mo, 1) * 8) != hipSuccess ||
-            hipMalloc(&ins, std::max<uint64_t>(mi, 1) * 8) != hipSuccess ||
-            hipMalloc(&tags, std::max<uint64_t>(mi, 1) * 8) != hipSuccess ||
-            (g->lbl_perm && hipMalloc(&rtags, std::max<uint64_t>(mo, 1) * 8) != hipSuccess)) {
-            st = set_err(g, FGI_ENOMEM, "owned edges");
-            break;
-        }
-        FGI_HIP(g, hipMemcpyAsync(off, ho.data(), ho.size() * 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_rmat_part, dim3(kGenBlocks), dim3(256), 0, s, m, per, scale, seed, base, nl, stale_pct,
-                           stale_seed, 1, cnt, (const unsigned long long*)off, rows, ins, (uint32_t*)nullptr,
-                           g->lbl_perm ? (const uint32_t*)g->pg_gc : (const uint32_t*)nullptr, rtags);
-        if (mi)
-            hipLaunchKernelGGL(k_in_tags_synth, dim3(nblk(mi)), dim3(256), 0, s, mi, ins, base, seed, tags,
-                               g->lbl_perm ? (const uint32_t*)g->pg_ig : (const uint32_t*)nullptr);
-        if (hipStreamSynchronize(s) != hipSuccess) {
-            st = set_err(g, FGI_EDEVICE, "generator fill pass");
-            break;
-        }
-        hipFree(cnt);
-        hipFree(off);
-        cnt = off = nullptr;
-        // rows: (owned used << 32 | global dependant), tags synthesised from global ids (with codes: from the
-        // slot ids, by the generator)
-        st = build_rows_from_keys(g, mo, rows, rtags, seed, stale_pct, stale_seed, base, base);
-        if (st != FGI_OK) break;
-        hipFree(rows);
-        rows = nullptr;
-        st = part_store_in(g, ins, tags, mi);
-        if (st != FGI_OK) break;
-        st = part_rebuild_lists(g);
-    } while (0);
-    cleanup();
-    return st == FGI_OK ? view_rebuild(g) : st;   // a new node table: the state view's full build
+    const uint64_t mo = tot[0], mi = tot[1];
+    FGI_TRY(tmalloc(g, trows, &rows, mo));
+    FGI_TRY(tmalloc(g, tins, &ins, mi));
+    FGI_TRY(tmalloc(g, ttags, &tags, mi));
+    if (g->lbl_perm) FGI_TRY(tmalloc(g, trtags, &rtags, mo));
+    FGI_HIP(g, hipMemcpyAsync(off, ho.data(), ho.size() * 8, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_rmat_part, dim3(kGenBlocks), dim3(256), 0, s, m, per, scale, seed, base, nl, stale_pct,
+                       stale_seed, 1, cnt, (const unsigned long long*)off, rows, ins, (uint32_t*)nullptr,
+                       g->lbl_perm ? (const uint32_t*)g->pg_gc : (const uint32_t*)nullptr, rtags);
+    if (mi)
+        hipLaunchKernelGGL(k_in_tags_synth, dim3(nblk(mi)), dim3(256), 0, s, mi, ins, base, seed, tags,
+                           g->lbl_perm ? (const uint32_t*)g->pg_ig : (const uint32_t*)nullptr);
+    FGI_HIP(g, hipStreamSynchronize(s));
+    tcnt.reset();
+    toff.reset();
+    // rows: (owned used << 32 | global dependant), tags synthesised from global ids (with codes: from the
+    // slot ids, by the generator)
+    FGI_TRY(build_rows_from_keys(g, mo, rows, rtags, seed, stale_pct, stale_seed, base, base));
+    trows.reset();   // before the store grows
+    trtags.reset();
+    FGI_TRY(part_store_in(g, ins, tags, mi));
+    FGI_TRY(part_rebuild_lists(g));
+    return view_rebuild(g);   // a new node table: the state view's full build
 }
 
 fgi_status fgi_part_register_nodes(fgi_graph* g, uint32_t n, const uint32_t* slot, const uint64_t* version,
@@ -1958,30 +1875,29 @@ fgi_status fgi_part_register_nodes(fgi_graph* g, uint32_t n, const uint32_t* slo
     hipSetDevice(g->device);
     hipStream_t s = g->stream;
     FGI_TRY(fold(g));
-    uint32_t *ds = nullptr, *df = nullptr;
-    uint64_t* dv = nullptr;
-    fgi_status st = FGI_OK;
-    if (hipMalloc(&ds, (size_t)n * 4) != hipSuccess || hipMalloc(&dv, (size_t)n * 8) != hipSuccess ||
-        (state_flags && hipMalloc(&df, (size_t)n * 4) != hipSuccess)) {
-        st = set_err(g, FGI_ENOMEM, "register buffers");
-    } else {
-        hipMemcpyAsync(ds, slot, (size_t)n * 4, hipMemcpyHostToDevice, s);
-        hipMemcpyAsync(dv, version, (size_t)n * 8, hipMemcpyHostToDevice, s);
-        if (df) hipMemcpyAsync(df, state_flags, (size_t)n * 4, hipMemcpyHostToDevice, s);
-        hipMemsetAsync(p->scalar, 0, 8, s);
+    Tmp ts, tv, tf;
+    uint32_t *ds, *df = nullptr;
+    uint64_t* dv;
+    FGI_TRY(tmalloc(g, ts, &ds, n));
+    FGI_TRY(tmalloc(g, tv, &dv, n));
+    if (state_flags) FGI_TRY(tmalloc(g, tf, &df, n));
+    touch(g);          // versions change: the pull lists are rebuilt before the next wave
+    note_words(g);
+    unsigned long long bad = 0;
+    hipError_t e = hipMemcpyAsync(ds, slot, (size_t)n * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dv, version, (size_t)n * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && df) e = hipMemcpyAsync(df, state_flags, (size_t)n * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(p->scalar, 0, 8, s);
+    if (e == hipSuccess) {
         hipLaunchKernelGGL(k_part_register, dim3(nblk(n)), dim3(256), 0, s, n, ds, dv, df, p->v.base, p->v.n_local,
                            p->v.ver_all, reinterpret_cast<unsigned long long*>(g->node), g->row_len, p->scalar);
-        unsigned long long bad = 0;
-        hipMemcpyAsync(&bad, p->scalar, 8, hipMemcpyDeviceToHost, s);
-        if (hipStreamSynchronize(s) != hipSuccess) st = set_err(g, FGI_EDEVICE, "register");
-        else if (bad) st = set_err(g, FGI_ESTATE, "%llu owned slots already had a current node", bad);
+        e = hipMemcpyAsync(&bad, p->scalar, 8, hipMemcpyDeviceToHost, s);
     }
-    hipFree(ds);
-    hipFree(dv);
-    hipFree(df);
-    touch(g);          // versions changed: the pull lists are rebuilt before the next wave
-    note_words(g);
-    return st == FGI_OK ? view_rebuild(g) : st;   // a bulk import: the state view's full build
+    const hipError_t es = hipStreamSynchronize(s);   // whatever was queued reads the caller's arrays
+    FGI_HIP(g, e);
+    FGI_HIP(g, es);
+    if (bad) return set_err(g, FGI_ESTATE, "%llu owned slots already had a current node", bad);
+    return view_rebuild(g);   // a bulk import: the state view's full build
 }
 
 fgi_status fgi_part_load_edges(fgi_graph* g, uint64_t m, const uint32_t* used, const uint32_t* dependant,
@@ -2006,20 +1922,18 @@ fgi_status fgi_part_load_edges(fgi_graph* g, uint64_t m, const uint32_t* used, c
     }
     if (m) {
         hipStream_t s = g->stream;
-        uint32_t* dd = nullptr;
-        uint64_t* dt = nullptr;
-        fgi_status st = FGI_OK;
-        if (hipMalloc(&dd, m * 4) != hipSuccess || hipMalloc(&dt, m * 8) != hipSuccess) {
-            st = set_err(g, FGI_ENOMEM, "weight buffers");
-        } else {
-            hipMemcpyAsync(dd, dependant, m * 4, hipMemcpyHostToDevice, s);
-            hipMemcpyAsync(dt, tag, m * 8, hipMemcpyHostToDevice, s);
+        Tmp td, tt;
+        uint32_t* dd;
+        uint64_t* dt;
+        FGI_TRY(tmalloc(g, td, &dd, m));
+        FGI_TRY(tmalloc(g, tt, &dt, m));
+        hipError_t e = hipMemcpyAsync(dd, dependant, m * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(dt, tag, m * 8, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess)
             hipLaunchKernelGGL(k_part_weight, dim3(nblk(m)), dim3(256), 0, s, m, dd, dt, p->v.ver_all, p->weight);
-            if (hipStreamSynchronize(s) != hipSuccess) st = set_err(g, FGI_EDEVICE, "weights");
-        }
-        hipFree(dd);
-        hipFree(dt);
-        FGI_TRY(st);
+        const hipError_t es = hipStreamSynchronize(s);   // whatever was queued reads the caller's arrays
+        FGI_HIP(g, e);
+        FGI_HIP(g, es);
     }
     if (choose) {
         FGI_TRY(part_codes_choose(g, p->weight));
@@ -2049,13 +1963,7 @@ fgi_status fgi_part_invalidate(fgi_graph* g, uint32_t n_roots, const uint32_t* r
     hipSetDevice(g->device);
     if (g->lbl_perm && n_roots) {   // the roots' codes (the caller's buffer stays as it is)
         PartState* p = ps(g);
-        if (p->roots_cap < n_roots) {
-            hipFree(p->roots_codes);
-            p->roots_codes = nullptr;
-            p->roots_cap = 0;
-            FGI_HIP(g, hipMalloc(&p->roots_codes, (size_t)n_roots * 4));
-            p->roots_cap = n_roots;
-        }
+        FGI_TRY(grow(g, &p->roots_codes, &p->roots_cap, n_roots, "the roots' codes"));
         FGI_HIP(g, hipMemcpyAsync(p->roots_codes, roots_dev, (size_t)n_roots * 4, hipMemcpyDeviceToDevice, g->stream));
         hipLaunchKernelGGL(k_pc_global, dim3(std::min<uint32_t>(nblk(n_roots), 4096)), dim3(256), 0, g->stream,
                            (uint64_t)n_roots, p->roots_codes, (const uint32_t*)g->pg_gc, p->v.n_global);

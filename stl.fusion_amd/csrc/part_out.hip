@@ -155,20 +155,6 @@ PartOut* pout_of(fgi_graph* g) {
     return g->pout;
 }
 
-template <class T>
-fgi_status grow(fgi_graph* g, T** p, uint64_t* cap, uint64_t need, const char* what) {
-    if (*cap >= need && *p) return FGI_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T)) != hipSuccess) {
-        *p = nullptr;
-        return set_err(g, FGI_ENOMEM, "a partitioned wave's %s (%llu entries)", what, (unsigned long long)need);
-    }
-    *cap = need;
-    return FGI_OK;
-}
-
 }  // namespace
 
 fgi_status part_out_stage_roots(fgi_graph* g, uint32_t n, const uint32_t* roots, const uint8_t* imm, uint32_t** roots_dev,
@@ -176,33 +162,8 @@ fgi_status part_out_stage_roots(fgi_graph* g, uint32_t n, const uint32_t* roots,
     *roots_dev = nullptr;
     *imm_dev = nullptr;
     if (!n) return FGI_OK;
-    PartOut* o = pout_of(g);
-    if (o->roots_cap < n) {
-        if (o->stage_h) (void)hipHostFree(o->stage_h);
-        if (o->roots_d) (void)hipFree(o->roots_d);
-        if (o->imm_d) (void)hipFree(o->imm_d);
-        o->stage_h = nullptr;
-        o->roots_d = nullptr;
-        o->imm_d = nullptr;
-        o->roots_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(n, 4096);
-        if (hipHostMalloc(reinterpret_cast<void**>(&o->stage_h), cap * 5, hipHostMallocDefault) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&o->roots_d), cap * 4) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&o->imm_d), cap) != hipSuccess)
-            return set_err(g, FGI_ENOMEM, "the staging of %u host roots", n);
-        o->roots_cap = cap;
-    }
     // (the previous call's copies are complete: its wave waited for the stream)
-    memcpy(o->stage_h, roots, (size_t)n * 4);
-    FGI_HIP(g, hipMemcpyAsync(o->roots_d, o->stage_h, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-    *roots_dev = o->roots_d;
-    if (imm) {
-        char* ih = o->stage_h + o->roots_cap * 4;
-        memcpy(ih, imm, n);
-        FGI_HIP(g, hipMemcpyAsync(o->imm_d, ih, n, hipMemcpyHostToDevice, g->stream));
-        *imm_dev = o->imm_d;
-    }
-    return FGI_OK;
+    return pout_of(g)->roots.stage(g, n, roots, imm, roots_dev, imm_dev);
 }
 
 fgi_status part_out_bits(fgi_graph* g, const unsigned long long** bits_dev, uint64_t* words_out) {
@@ -212,7 +173,7 @@ fgi_status part_out_bits(fgi_graph* g, const unsigned long long** bits_dev, uint
     const uint64_t words = ((uint64_t)g->ext_handles + 63) / 64;
     *words_out = words;
     if (!o->bits_valid) {
-        FGI_TRY(grow(g, &o->bits, &o->bits_cap, words, "bitmap"));
+        FGI_TRY(grow(g, &o->bits, &o->bits_cap, words, "a partitioned wave's bitmap"));
         hipStream_t s = g->stream;
         const auto* inv64 = reinterpret_cast<const unsigned long long*>(g->inv_bm);
         const uint64_t n = g->last_wave_n;
@@ -249,8 +210,8 @@ fgi_status part_out_ids(fgi_graph* g, const uint32_t** ids_dev, uint32_t* host_c
         FGI_TRY(part_out_bits(g, &bits, &words));
         const uint64_t n = g->last_wave_n;
         const uint32_t nb = (uint32_t)((words + kOBlock - 1) / kOBlock);
-        FGI_TRY(grow(g, &o->bsum, &o->bsum_cap, (uint64_t)nb + 1, "block counts"));
-        FGI_TRY(grow(g, &o->ids, &o->ids_cap, std::max<uint64_t>(n, 1), "id list"));
+        FGI_TRY(grow(g, &o->bsum, &o->bsum_cap, (uint64_t)nb + 1, "a partitioned wave's block counts"));
+        FGI_TRY(grow(g, &o->ids, &o->ids_cap, std::max<uint64_t>(n, 1), "a partitioned wave's id list"));
         hipStream_t s = g->stream;
         hipLaunchKernelGGL(k_pout_count, dim3(nb), dim3(kOBlock), 0, s, bits, words, o->bsum);
         hipLaunchKernelGGL(k_pout_scan, dim3(1), dim3(kOBlock), 0, s, o->bsum, nb);
@@ -277,12 +238,10 @@ fgi_status part_out_ids(fgi_graph* g, const uint32_t** ids_dev, uint32_t* host_c
 void part_out_destroy(fgi_graph* g) {
     PartOut* o = g->pout;
     if (!o) return;
-    if (o->bits) (void)hipFree(o->bits);
-    if (o->ids) (void)hipFree(o->ids);
-    if (o->bsum) (void)hipFree(o->bsum);
-    if (o->stage_h) (void)hipHostFree(o->stage_h);
-    if (o->roots_d) (void)hipFree(o->roots_d);
-    if (o->imm_d) (void)hipFree(o->imm_d);
+    dfree(o->bits);
+    dfree(o->ids);
+    dfree(o->bsum);
+    o->roots.release();
     delete o;
     g->pout = nullptr;
 }

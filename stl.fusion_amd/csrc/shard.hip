@@ -197,28 +197,6 @@ __global__ void k_shard_register(uint64_t n, const uint4* __restrict__ rec, cons
     row_len[h] = 0;
 }
 
-// frees its device pointers when the call leaves
-struct DevFree {
-    std::vector<void*> p;
-    ~DevFree() {
-        for (void* q : p)
-            if (q) hipFree(q);
-    }
-    template <class T>
-    bool alloc(T** out, uint64_t count) {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<uint64_t>(count, 1) * sizeof(T)) != hipSuccess) return false;
-        p.push_back(q);
-        *out = static_cast<T*>(q);
-        return true;
-    }
-    void release(void* q) {
-        for (void*& x : p)
-            if (x == q) x = nullptr;
-        hipFree(q);
-    }
-};
-
 fgi_status shard_enter(fgi_graph* g, const char* what) {
     if (!g->part) return set_err(g, FGI_ESTATE, "%s: partition not initialised", what);
     if (g->failed)
@@ -285,11 +263,12 @@ fgi_status fgi_part_register_shard(fgi_graph* g, uint32_t n, const uint32_t* slo
     if (total == 0) return FGI_OK;
     hipStream_t s = g->stream;
     FGI_TRY(fold(g));
-    DevFree df;
-    uint4 *rec_mine = nullptr, *rec_all = nullptr;
-    unsigned long long* err = nullptr;
-    if (!df.alloc(&rec_mine, n) || !df.alloc(&rec_all, total) || !df.alloc(&err, 1))
-        return set_err(g, FGI_ENOMEM, "register buffers");
+    Tmp tmine, tall, terr;
+    uint4 *rec_mine, *rec_all;
+    unsigned long long* err;
+    FGI_TRY(tmalloc(g, tmine, &rec_mine, n));
+    FGI_TRY(tmalloc(g, tall, &rec_all, total));
+    FGI_TRY(tmalloc(g, terr, &err, 1));
     std::vector<uint4> rec(n);
     for (uint32_t i = 0; i < n; ++i)
         rec[i] = make_uint4(slot[i], state_flags ? state_flags[i] : (uint32_t)FGI_CONSISTENT, (uint32_t)version[i],
@@ -320,7 +299,7 @@ fgi_status fgi_part_load_edges_shard(fgi_graph* g, uint64_t m, const uint32_t* u
     const uint32_t W = pv.world, R = pv.rank, N = pv.n_global, B = pv.block, base = pv.base;
     hipStream_t s = g->stream;
     const bool null_arg = m && (!used || !dependant || !tag);
-    DevFree df;
+    Tmp tdu, tdd, tdt, tctr, tblk, tsk, tst, trk, trt, tik, tit;
     uint32_t *du = nullptr, *dd = nullptr, *blk_cnt = nullptr;
     uint64_t* dt = nullptr;
     unsigned long long* ctr = nullptr;   // [kBins] counts, [kBins] scatter cursors, the first bad edge
@@ -334,9 +313,11 @@ fgi_status fgi_part_load_edges_shard(fgi_graph* g, uint64_t m, const uint32_t* u
         mine[kBins] = 1;
         mine[kBins + 1] = 3;
     } else if (m) {
-        if (!df.alloc(&du, m) || !df.alloc(&dd, m) || !df.alloc(&dt, m) || !df.alloc(&ctr, 2 * kBins + 1) ||
-            !df.alloc(&blk_cnt, (uint64_t)grid * kBins))
-            return set_err(g, FGI_ENOMEM, "shard buffers");
+        FGI_TRY(tmalloc(g, tdu, &du, m));
+        FGI_TRY(tmalloc(g, tdd, &dd, m));
+        FGI_TRY(tmalloc(g, tdt, &dt, m));
+        FGI_TRY(tmalloc(g, tctr, &ctr, 2 * kBins + 1));
+        FGI_TRY(tmalloc(g, tblk, &blk_cnt, (uint64_t)grid * kBins));
         FGI_HIP(g, hipMemcpyAsync(du, used, m * 4, hipMemcpyHostToDevice, s));
         FGI_HIP(g, hipMemcpyAsync(dd, dependant, m * 4, hipMemcpyHostToDevice, s));
         FGI_HIP(g, hipMemcpyAsync(dt, tag, m * 8, hipMemcpyHostToDevice, s));
@@ -387,10 +368,14 @@ fgi_status fgi_part_load_edges_shard(fgi_graph* g, uint64_t m, const uint32_t* u
         n_row += a[R];
         n_in += a[8 + R];
     }
-    uint64_t *sk = nullptr, *st = nullptr, *rk = nullptr, *rt = nullptr, *ik = nullptr, *it = nullptr;
-    if (!df.alloc(&sk, at) || !df.alloc(&st, at) || !df.alloc(&rk, n_row) || !df.alloc(&rt, n_row) || !df.alloc(&ik, n_in) ||
-        !df.alloc(&it, n_in))
-        return set_err(g, FGI_ENOMEM, "shard staging (32 bytes per edge of the shard, 16 per record received)");
+    // staging: 32 bytes per edge of the shard, 16 per record received
+    uint64_t *sk, *st, *rk, *rt, *ik, *it;
+    FGI_TRY(tmalloc(g, tsk, &sk, at));
+    FGI_TRY(tmalloc(g, tst, &st, at));
+    FGI_TRY(tmalloc(g, trk, &rk, n_row));
+    FGI_TRY(tmalloc(g, trt, &rt, n_row));
+    FGI_TRY(tmalloc(g, tik, &ik, n_in));
+    FGI_TRY(tmalloc(g, tit, &it, n_in));
     if (m) {
         hipLaunchKernelGGL(k_shard_scatter, dim3(grid), dim3(kShardThreads), 0, s, m, per, (const uint32_t*)du,
                            (const uint32_t*)dd, (const uint64_t*)dt, N, B, W, (const uint32_t*)blk_cnt, bases, ctr + kBins, sk,
@@ -403,8 +388,9 @@ fgi_status fgi_part_load_edges_shard(fgi_graph* g, uint64_t m, const uint32_t* u
         FGI_TRY(part_alltoallv(g, sk, soff_i, sb_i, ik, roff_i, rb_i));
         FGI_TRY(part_alltoallv(g, st, soff_i, sb_i, it, roff_i, rb_i));
     }
-    for (void* q : {(void*)du, (void*)dd, (void*)dt, (void*)sk, (void*)st, (void*)blk_cnt, (void*)ctr})
-        if (q) df.release(q);
+    // the shard and what it sent are done with (every exchange returned with its data in place; a rank whose
+    // scatter alone is queued reuses these on the same stream)
+    for (Tmp* t : {&tdu, &tdd, &tdt, &tsk, &tst, &tblk, &tctr}) t->reset();
     // The receiver: what fgi_part_load_edges does with the whole batch, from the records of its own slots.
     // With codes already chosen the keys take them first (the replica and the weights are in code order).
     if (g->lbl_perm) {
@@ -413,8 +399,10 @@ fgi_status fgi_part_load_edges_shard(fgi_graph* g, uint64_t m, const uint32_t* u
     }
     if (total_m) {
         // list weights: every rank counts its own dependants' live entries, the blocks are all-gathered
-        uint32_t *inc = nullptr, *inc_all = nullptr;
-        if (!df.alloc(&inc, B) || !df.alloc(&inc_all, (uint64_t)W * B)) return set_err(g, FGI_ENOMEM, "weight increments");
+        Tmp tinc, tinc_all;
+        uint32_t *inc, *inc_all;
+        FGI_TRY(tmalloc(g, tinc, &inc, B));
+        FGI_TRY(tmalloc(g, tinc_all, &inc_all, (uint64_t)W * B));
         FGI_HIP(g, hipMemsetAsync(inc, 0, (size_t)B * 4, s));
         if (n_in)
             hipLaunchKernelGGL(k_shard_weight, dim3(std::min<uint32_t>(nblk(n_in), 8192)), dim3(256), 0, s, n_in,
@@ -426,8 +414,8 @@ fgi_status fgi_part_load_edges_shard(fgi_graph* g, uint64_t m, const uint32_t* u
         hipLaunchKernelGGL(k_shard_weight_add, dim3(nblk(N)), dim3(256), 0, s, N, (const uint32_t*)inc_all, part_weight(g));
         FGI_HIP(g, hipGetLastError());
         FGI_HIP(g, hipStreamSynchronize(s));
-        df.release(inc);
-        df.release(inc_all);
+        tinc.reset();
+        tinc_all.reset();
         // the first bulk load of a partition that wants codes: every rank holds the same global weights
         if (part_codes_now(g)) {
             FGI_TRY(part_codes_choose(g, part_weight(g)));

@@ -129,44 +129,43 @@ static fgi_status exp_relabel(fgi_graph* g, uint32_t n, uint64_t* keys, uint64_t
     const char* o = getenv("FGI_EXP_RELABEL_ORDER");
     const uint32_t slot_order = o ? (uint32_t)atoi(o) : 0u;
     hipStream_t s = g->stream;
+    Tmp tcnt, thot, tcold, tpos, tperm, tk0, tk1, ttmp, tstmp;
     uint32_t *cnt, *hot, *cold, *pos, *perm;
     uint64_t *k0, *k1;
-    FGI_HIP(g, hipMalloc(&cnt, (size_t)n * 4));
-    FGI_HIP(g, hipMalloc(&hot, (size_t)n * 4));
-    FGI_HIP(g, hipMalloc(&cold, (size_t)n * 4));
-    FGI_HIP(g, hipMalloc(&pos, (size_t)n * 4));
-    FGI_HIP(g, hipMalloc(&perm, (size_t)n * 4));
-    FGI_HIP(g, hipMalloc(&k0, (size_t)n * 8));
-    FGI_HIP(g, hipMalloc(&k1, (size_t)n * 8));
+    FGI_TRY(tmalloc(g, tcnt, &cnt, n));
+    FGI_TRY(tmalloc(g, thot, &hot, n));
+    FGI_TRY(tmalloc(g, tcold, &cold, n));
+    FGI_TRY(tmalloc(g, tpos, &pos, n));
+    FGI_TRY(tmalloc(g, tperm, &perm, n));
+    FGI_TRY(tmalloc(g, tk0, &k0, n));
+    FGI_TRY(tmalloc(g, tk1, &k1, n));
     FGI_HIP(g, hipMemsetAsync(cnt, 0, (size_t)n * 4, s));
     FGI_HIP(g, hipMemsetAsync(hot, 0, (size_t)n * 4, s));
     hipLaunchKernelGGL(kx_deg, dim3(8192), dim3(256), 0, s, m, keys, which, cnt);
     hipLaunchKernelGGL(kx_sortkey, dim3((n + 255) / 256), dim3(256), 0, s, n, cnt, slot_order, k0);
     size_t tb = 0;
     FGI_HIP(g, rocprim::radix_sort_keys_desc(nullptr, tb, k0, k1, (size_t)n, 0, 64, s));
-    void* tmp;
-    FGI_HIP(g, hipMalloc(&tmp, tb));
+    char* tmp;
+    FGI_TRY(tmalloc(g, ttmp, &tmp, tb));
     FGI_HIP(g, rocprim::radix_sort_keys_desc(tmp, tb, k0, k1, (size_t)n, 0, 64, s));
     hipLaunchKernelGGL(kx_hot, dim3((uint32_t)((K + 255) / 256)), dim3(256), 0, s, n, (uint32_t)K, k1, hot);
     hipLaunchKernelGGL(kx_cold, dim3((n + 255) / 256), dim3(256), 0, s, n, hot, cold);
     size_t sb = 0;
     FGI_HIP(g, rocprim::exclusive_scan(nullptr, sb, cold, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
-    void* stmp;
-    FGI_HIP(g, hipMalloc(&stmp, sb));
+    char* stmp;
+    FGI_TRY(tmalloc(g, tstmp, &stmp, sb));
     FGI_HIP(g, rocprim::exclusive_scan(stmp, sb, cold, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
     hipLaunchKernelGGL(kx_perm, dim3((n + 255) / 256), dim3(256), 0, s, n, (uint32_t)K, hot, pos, slot_order, perm);
     hipLaunchKernelGGL(kx_apply, dim3(8192), dim3(256), 0, s, m, perm, keys);
     FGI_HIP(g, hipStreamSynchronize(s));
-    for (void* p : {(void*)cnt, (void*)hot, (void*)cold, (void*)pos, (void*)perm, (void*)k0, (void*)k1, tmp, stmp})
-        hipFree(p);
     fprintf(stderr, "[fgi] FGI_EXP_RELABEL: %lld heaviest of %u slots (weight %u) relabelled first (slot order %u)\n", K, n, which, slot_order);
     return FGI_OK;
 }
 
-fgi_status synth_rmat_keys(fgi_graph* g, uint32_t scale, uint32_t edge_factor, uint64_t seed, uint64_t** keys,
-                           uint64_t* m) {
+static fgi_status synth_rmat_keys(fgi_graph* g, uint32_t scale, uint32_t edge_factor, uint64_t seed, Tmp& tk, uint64_t** keys,
+                                  uint64_t* m) {
     *m = (uint64_t)edge_factor << scale;
-    FGI_HIP(g, hipMalloc(reinterpret_cast<void**>(keys), *m * sizeof(uint64_t)));
+    FGI_TRY(tmalloc(g, tk, keys, *m));
     hipLaunchKernelGGL(k_gen_rmat, dim3(8192), dim3(256), 0, g->stream, *m, scale, seed, *keys);
     FGI_HIP(g, hipGetLastError());
     return FGI_OK;
@@ -176,15 +175,14 @@ fgi_status synth_rmat_keys(fgi_graph* g, uint32_t scale, uint32_t edge_factor, u
 // slots first, then the first load chooses the labels and the keys become labels
 static fgi_status synth_rows(fgi_graph* g, uint64_t m, uint64_t* keys, uint64_t seed, uint32_t stale_pct, uint64_t stale_seed) {
     if (!g->lbl_K) return build_rows_from_keys(g, m, keys, nullptr, seed, stale_pct, stale_seed);
-    uint64_t* tags = nullptr;
-    FGI_HIP(g, hipMalloc(reinterpret_cast<void**>(&tags), std::max<uint64_t>(m, 1) * sizeof(uint64_t)));
+    Tmp tt;
+    uint64_t* tags;
+    FGI_TRY(tmalloc(g, tt, &tags, m));
     hipLaunchKernelGGL(k_synth_tags, dim3(8192), dim3(256), 0, g->stream, m, keys, seed, stale_pct, stale_seed, tags);
-    fgi_status st = hipGetLastError() == hipSuccess ? FGI_OK : FGI_EDEVICE;
-    if (st == FGI_OK) st = labels_choose(g, keys, m);
-    if (st == FGI_OK) st = labels_map_keys(g, keys, m);
-    if (st == FGI_OK) st = build_rows_from_keys(g, m, keys, tags, seed, stale_pct, stale_seed);
-    hipFree(tags);
-    return st;
+    FGI_HIP(g, hipGetLastError());
+    FGI_TRY(labels_choose(g, keys, m));
+    FGI_TRY(labels_map_keys(g, keys, m));
+    return build_rows_from_keys(g, m, keys, tags, seed, stale_pct, stale_seed);
 }
 
 fgi_status synth_versions(fgi_graph* g, uint32_t n, uint64_t seed) {
@@ -212,14 +210,15 @@ fgi_status fgi_synth_layered(fgi_graph* g, uint32_t levels, uint32_t width, uint
     hipSetDevice(g->device);
     FGI_TRY(synth_versions(g, (uint32_t)n, seed));
     const uint64_t m = (uint64_t)(levels - 1) * width * fanout;
-    uint64_t* keys = nullptr;
-    FGI_HIP(g, hipMalloc(reinterpret_cast<void**>(&keys), m * sizeof(uint64_t)));
+    Tmp tk;
+    uint64_t* keys;
+    FGI_TRY(tmalloc(g, tk, &keys, m));
     const uint64_t threads = (uint64_t)(levels - 1) * width;
     hipLaunchKernelGGL(k_gen_layered, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, g->stream, levels, width,
                        fanout, seed, keys);
-    fgi_status st = hipGetLastError() == hipSuccess ? synth_rows(g, m, keys, seed, 0, 0) : FGI_EDEVICE;
-    hipFree(keys);
-    return st == FGI_OK ? view_rebuild(g) : st;   // a new node table: the state view's full build
+    FGI_HIP(g, hipGetLastError());
+    FGI_TRY(synth_rows(g, m, keys, seed, 0, 0));
+    return view_rebuild(g);   // a new node table: the state view's full build
 }
 
 fgi_status fgi_synth_rmat(fgi_graph* g, uint32_t scale, uint32_t edge_factor, uint64_t seed, uint32_t stale_pct,
@@ -228,13 +227,13 @@ fgi_status fgi_synth_rmat(fgi_graph* g, uint32_t scale, uint32_t edge_factor, ui
     if ((1ull << scale) > g->ext_slots) return set_err(g, FGI_EINVAL, "graph needs 2^%u slots", scale);
     hipSetDevice(g->device);
     FGI_TRY(synth_versions(g, 1u << scale, seed));
+    Tmp tk;
     uint64_t* keys = nullptr;
     uint64_t m = 0;
-    FGI_TRY(synth_rmat_keys(g, scale, edge_factor, seed, &keys, &m));
+    FGI_TRY(synth_rmat_keys(g, scale, edge_factor, seed, tk, &keys, &m));
     if (!g->lbl_K) FGI_TRY(exp_relabel(g, 1u << scale, keys, m));
-    fgi_status st = synth_rows(g, m, keys, seed, stale_pct, stale_seed);
-    hipFree(keys);
-    return st == FGI_OK ? view_rebuild(g) : st;
+    FGI_TRY(synth_rows(g, m, keys, seed, stale_pct, stale_seed));
+    return view_rebuild(g);
 }
 
 }  // extern "C"

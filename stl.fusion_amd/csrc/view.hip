@@ -338,13 +338,13 @@ fgi_status view_refresh(fgi_graph* g, int kind, const void* list_dev, uint64_t n
 
 fgi_status view_refresh_host(fgi_graph* g, const uint32_t* handles, uint64_t n) {
     if (!view_on(g) || !n) return FGI_OK;
-    uint32_t* d = nullptr;
-    FGI_HIP(g, hipMalloc(reinterpret_cast<void**>(&d), n * 4));
-    fgi_status st = hip_check(g, hipMemcpyAsync(d, handles, n * 4, hipMemcpyHostToDevice, g->stream), "view: handle upload");
-    if (st == FGI_OK) st = view_refresh(g, kViewHandles, d, n);
-    if (st == FGI_OK) st = hip_check(g, hipStreamSynchronize(g->stream), "view: handle refresh");
-    (void)hipFree(d);
-    return st;
+    Tmp td;
+    uint32_t* d;
+    FGI_TRY(tmalloc(g, td, &d, n));
+    FGI_HIP(g, hipMemcpyAsync(d, handles, n * 4, hipMemcpyHostToDevice, g->stream));
+    FGI_TRY(view_refresh(g, kViewHandles, d, n));
+    FGI_HIP(g, hipStreamSynchronize(g->stream));   // the caller's array is pageable
+    return FGI_OK;
 }
 
 fgi_status view_flush(fgi_graph* g) {

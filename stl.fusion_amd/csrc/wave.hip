@@ -4274,30 +4274,10 @@ fgi_status run_wave_async_host(fgi_graph* g, uint32_t n_roots, const uint32_t* r
     const int k = (int)(t & 1);
     fgi_graph::AsyncWave& a = g->aw[k];
     if (a.busy) FGI_TRY(wave_wait(g, a.ticket, nullptr, nullptr, nullptr));   // its staged roots are consumed
-    const uint64_t need = std::max<uint64_t>(n_roots, 1);
-    if (g->ar_cap[k] < need) {
-        if (g->ar_h[k]) (void)hipHostFree(g->ar_h[k]);
-        if (g->ar_d[k]) (void)hipFree(g->ar_d[k]);
-        g->ar_h[k] = g->ar_d[k] = nullptr;
-        g->ar_cap[k] = 0;
-        const uint64_t cap = std::max<uint64_t>(need, 4096);
-        // roots (4 B each) then the immediately flags (1 B each), in one pinned and one device buffer
-        if (hipHostMalloc(reinterpret_cast<void**>(&g->ar_h[k]), cap * 5, hipHostMallocDefault) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&g->ar_d[k]), cap * 5) != hipSuccess)
-            return set_err(g, FGI_ENOMEM, "async wave: root staging");
-        g->ar_cap[k] = cap;
-    }
-    uint8_t* imm_h = reinterpret_cast<uint8_t*>(g->ar_h[k] + g->ar_cap[k]);
-    uint8_t* imm_d = reinterpret_cast<uint8_t*>(g->ar_d[k] + g->ar_cap[k]);
-    if (n_roots) {
-        memcpy(g->ar_h[k], roots, (size_t)n_roots * 4);
-        FGI_HIP(g, hipMemcpyAsync(g->ar_d[k], g->ar_h[k], (size_t)n_roots * 4, hipMemcpyHostToDevice, g->stream));
-        if (imm) {
-            memcpy(imm_h, imm, n_roots);
-            FGI_HIP(g, hipMemcpyAsync(imm_d, imm_h, n_roots, hipMemcpyHostToDevice, g->stream));
-        }
-    }
-    return run_wave_async(g, n_roots, g->ar_d[k], imm && n_roots ? imm_d : nullptr, ticket);
+    uint32_t* roots_d = nullptr;
+    uint8_t* imm_d = nullptr;
+    FGI_TRY(g->ar[k].stage(g, n_roots, roots, imm, &roots_d, &imm_d));
+    return run_wave_async(g, n_roots, roots_d, imm_d, ticket);
 }
 
 fgi_status wave_wait(fgi_graph* g, uint64_t ticket, uint64_t* out_n, const uint32_t** ids_dev, fgi_wave_stats* stats) {
@@ -4475,7 +4455,7 @@ static fgi_status launch_part_level(fgi_graph* g, const PartView& pv, const Part
 static fgi_status launch_part_flagged(fgi_graph* g, const PartView& pv) {
     hipStream_t s = g->stream;
     const uint64_t k = g->pflg_runs.size();
-    if (!g->prec || !g->pcur || k >= g->pcur_cap)
+    if (!g->prec || !g->pcur || 1 + k >= g->pcur_cap)
         return set_err(g, FGI_ESTATE, "a partitioned cascade's flagged records were not opened (%llu runs)", (unsigned long long)k);
     const uint64_t words = ((uint64_t)pv.n_local + 63) / 64;
     const FlagArgs a{reinterpret_cast<unsigned long long*>(g->flg_bm),
@@ -4525,21 +4505,9 @@ fgi_status part_flagged_begin(fgi_graph* g, uint64_t cascades, uint64_t extra) {
     // node's life and every record reports such a change; a call holds at most the nodes of this rank's
     // handles plus one new node per begin_compute entry it owns
     const uint64_t need = 2 * ((uint64_t)g->n_handles + extra);
-    if (g->prec_cap < need) {   // before anything is queued: the previous call's records are forgotten
-        if (g->prec) FGI_HIP(g, hipFree(g->prec));
-        g->prec = nullptr;
-        g->prec_cap = 0;
-        FGI_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->prec), need * sizeof(unsigned long long)));
-        g->prec_cap = need;
-    }
-    if (g->pcur_cap < cascades) {
-        if (g->pcur) FGI_HIP(g, hipFree(g->pcur));
-        g->pcur = nullptr;
-        g->pcur_cap = 0;
-        const uint64_t c = std::max<uint64_t>(cascades, 16);
-        FGI_HIP(g, hipMalloc(reinterpret_cast<void**>(&g->pcur), (1 + c) * sizeof(unsigned long long)));
-        g->pcur_cap = c;
-    }
+    // before anything is queued: the previous call's records are forgotten
+    FGI_TRY(grow(g, &g->prec, &g->prec_cap, need, "a partitioned call's flagged records"));
+    FGI_TRY(grow(g, &g->pcur, &g->pcur_cap, 1 + std::max<uint64_t>(cascades, 16), "a partitioned call's cascade marks"));
     FGI_HIP(g, hipMemsetAsync(g->pcur, 0, sizeof(unsigned long long), g->stream));
     return FGI_OK;
 }
