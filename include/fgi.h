@@ -517,6 +517,74 @@ fgi_status fgi_part_fanout_detached(fgi_graph* g, uint64_t n, const uint32_t* ha
                                uint64_t* call_ids, uint32_t* handles_out, uint64_t cap, uint64_t* out_n);
 fgi_status fgi_part_unsubscribe_peer(fgi_graph* g, uint32_t peer, uint64_t* out_dropped /*nullable*/);
 
+/* ---- delayed invalidation: timers in device memory (C-ABI 0.11; timers.hip) ---------- */
+/* A Consistent node with an InvalidationDelay that a cascade reaches only gets InvalidationDelayStarted
+ * (Computed.cs:183-197) and then schedules its own timer, which later calls Invalidate(true)
+ * (ComputedExt.cs:10-45, the Timeouts.Invalidate timer set). The engine keeps that timer set in device memory:
+ * at most one entry (handle, version, due) per boundary handle, armed by kernels queued behind the calls that
+ * flag nodes, fired by one call per clock tick. Single-device graphs only, off until fgi_timers_open; a graph
+ * that never opens timers allocates and launches nothing for any of this.
+ * Clock: uint64_t ticks in a unit the host chooses; the engine only adds and compares. The graph holds `now`;
+ * fgi_timers_set_now and fgi_timers_run_due advance it, a value below the current one is FGI_EINVAL and
+ * changes nothing.
+ * Delay (ComputedOptions.InvalidationDelay): a property of the handle, set by fgi_timers_set_delay, sticky for
+ * a slot across recomputations. 0: the graph's default_delay. FGI_TIMER_NEVER: TimeSpan.MaxValue, the node is
+ * flagged and no entry is ever stored (ComputedExt.cs:12). An effective delay of 0 stores nothing either. A
+ * detached handle fgi_begin_compute (or a batch's BEGIN_COMPUTE step) hands out takes a copy of its slot's delay.
+ * Arm rule, for a candidate handle h: the node now at h, its visit bit folded in as fgi_subscribe reads it, is
+ * Consistent with InvalidationDelayStarted, and no entry (h, its version) exists: store (h, version,
+ * due = now + delay(h)), saturating at FGI_TIMER_NEVER - 1. An entry of another version at h is overwritten
+ * (counted as dropped and as armed); one of the same version keeps its earlier due time
+ * (ConcurrentTimerSet.AddOrUpdateToEarlier). Candidates: the records of every flagged-set post-pass
+ * (fgi_last_wave_flagged, fgi_wave_wait_flagged: armed by a kernel queued behind the post-pass, no wait, no
+ * copy); the records of a batch's cascades, armed once behind the batch from the states the batch left; every
+ * detached handle handed out.
+ * Move: when a displaced node survives to detached handle d, an entry (slot, its version) moves to d with its
+ * due time unchanged; without one the arm rule runs on d. A batch applies its moves behind itself, in step
+ * order, before it arms its records.
+ * Fire: fgi_timers_run_due(now) sets the clock, removes every entry with due <= now, and fires those whose
+ * node still has the entry's version and is Consistent with InvalidationDelayStarted (the others are stale:
+ * counted in dropped). The fired handles, ascending, are the roots of ONE wave with immediately = 1, run as
+ * fgi_invalidate_dev runs one: fgi_last_wave_ids, fgi_wave_ids_dev, fgi_last_wave_flagged, fgi_last_wave_fanout,
+ * the state view and the statistics follow it, and its own flagged set arms at `now`. out_ids / cap / out_n
+ * follow fgi_invalidate's contract: a short cap returns FGI_ECAPACITY with *out_n set; the wave has run and
+ * fgi_last_wave_ids returns its ids. *out_fired (nullable): entries fired. Nothing due: no wave, 0 ids, and the
+ * last wave's results stay as they are.
+ * Lazy removal: the entry of a node invalidated before its due time stays until it comes due or is
+ * overwritten, so `stored` may include stale entries. fgi_release of a detached handle drops its entry;
+ * fgi_restore drops all entries and keeps the clock and the delays; fgi_timers_open on a populated graph arms
+ * every node already Consistent with InvalidationDelayStarted.
+ * fgi_timers_next_due: the smallest due time stored (FGI_TIMER_NONE without entries), a reduction over the
+ * entries. fgi_timers_list (diagnostics, tests): the stored entries ascending by handle; a short cap returns
+ * FGI_ECAPACITY with *out_n set.
+ * Counter identity, over a graph's life since fgi_timers_open: armed == fired + dropped + stored. `moved`
+ * counts entries that changed handle (a move neither arms nor drops). runs: fgi_timers_run_due calls that
+ * launched a wave. last_kernel_ms: device time of the last fgi_timers_run_due's own kernels (HIP events).
+ * Memory: 8 bytes per handle (a delay code and an entry index) plus 48 bytes per possible entry: handles with
+ * a delay of their own and detached handles, or every handle when default_delay is set.
+ * Before fgi_timers_open every other call here returns FGI_ESTATE and fgi_timers_stats_get returns zeros; on a
+ * poisoned graph FGI_ESTATE; fgi_timers_open on a partitioned graph FGI_ENOTSUP. */
+#define FGI_TIMER_NEVER 0xFFFFFFFFFFFFFFFFull
+#define FGI_TIMER_NONE 0xFFFFFFFFFFFFFFFFull /* fgi_timers_next_due: nothing stored */
+typedef struct fgi_timers_config {
+    uint32_t struct_size, reserved;
+    uint64_t default_delay, now;
+} fgi_timers_config;
+typedef struct fgi_timer_stats {
+    uint64_t stored, armed, fired, dropped, moved, runs;
+    double last_kernel_ms;
+} fgi_timer_stats;
+fgi_status fgi_timers_open(fgi_graph* g, const fgi_timers_config* cfg);
+fgi_status fgi_timers_close(fgi_graph* g);
+fgi_status fgi_timers_set_delay(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint64_t* delay);
+fgi_status fgi_timers_set_now(fgi_graph* g, uint64_t now);
+fgi_status fgi_timers_run_due(fgi_graph* g, uint64_t now, uint32_t* out_ids /*nullable*/, uint64_t cap,
+                              uint64_t* out_n, uint64_t* out_fired /*nullable*/, fgi_wave_stats* stats /*nullable*/);
+fgi_status fgi_timers_next_due(fgi_graph* g, uint64_t* out_due, uint64_t* out_stored /*nullable*/);
+fgi_status fgi_timers_stats_get(fgi_graph* g, fgi_timer_stats* out);
+fgi_status fgi_timers_list(fgi_graph* g, uint32_t* handle, uint64_t* version, uint64_t* due, uint64_t cap,
+                           uint64_t* out_n);
+
 /* ---- streaming batches (BASELINE.json configs[4]) ------------------------------- */
 /* One step of a batch: the arguments of the matching single call. */
 #define FGI_STEP_INVALIDATE 1     /* fgi_invalidate: handles, flags = immediately (nullable) */

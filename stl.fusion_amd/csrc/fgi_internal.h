@@ -476,6 +476,8 @@ struct Fanout {
     double last_ms = 0;
 };
 
+struct Timers;   // the delay timers in device memory (timers.hip)
+
 }  // namespace fgi
 
 struct fgi_graph {
@@ -821,6 +823,7 @@ struct fgi_graph {
     int casc_kind = 0;
     int opt_fanout_path = 0;           // FGI_OPT_FANOUT_PATH: 0 by what the wave left, 1 id list, 2 bitmap, 3 (measurement) a rank's bitmap renumbered whole
     bool tmp_poison = false;           // FGI_TMP_POISON=1: every temporary is handed out filled with 0xA5
+    fgi::Timers* tim = nullptr;        // the delay timers (timers.hip), null until fgi_timers_open
 };
 
 // ---- internal entry points shared between translation units ----------------------------------
@@ -1100,6 +1103,21 @@ fgi_status fanout_move(fgi_graph* g, uint32_t n, const uint32_t* from, const uin
 // the entries of the listed boundary handles (host array) are dropped
 fgi_status fanout_drop_handles(fgi_graph* g, uint32_t n, const uint32_t* handles);
 void fanout_destroy(fgi_graph* g);
+// ---- delay timers (timers.hip) ----
+// whether the graph's timers are open (everything below is a no-op returning FGI_OK otherwise)
+inline bool timers_on(const fgi_graph* g) { return g->tim != nullptr; }
+// the arm rule over flagged records (boundary handle << 32 | flags) on the device: n_max of them, or *n_dev
+// if that is less (n_dev nullable). Queued on the graph's stream; nothing waits.
+fgi_status timers_arm_records(fgi_graph* g, const unsigned long long* rec, uint64_t n_max, const unsigned long long* n_dev);
+// displaced nodes: the entry (from[i], the version of the node now at to[i]) moves to to[i], else the arm
+// rule runs on to[i]; to[i] takes from[i]'s delay (boundary handles, host arrays, from[] distinct; to[i] ==
+// FGI_NONE: nothing happens)
+fgi_status timers_move(fgi_graph* g, uint32_t n, const uint32_t* from, const uint32_t* to);
+// the entries of the listed boundary handles (host array) are dropped
+fgi_status timers_drop_handles(fgi_graph* g, uint32_t n, const uint32_t* handles);
+// fgi_restore: every entry is dropped; the clock and the delays stay
+fgi_status timers_restore(fgi_graph* g);
+void timers_destroy(fgi_graph* g);
 // ---- sharded loads (shard.hip) ----
 // Their collectives, over the partition's transport (part.hip, PartComm): host words (at most kShardWords
 // per rank) all-gathered on the host; device byte ranges with per-peer counts, all-gathered (src[0,

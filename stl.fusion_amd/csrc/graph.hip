@@ -1872,7 +1872,9 @@ fgi_status fgi_version(uint32_t* major, uint32_t* minor) {
     //      fgi_unsubscribe_peer, fgi_sub_stats_get)
     // 0.10: the same per rank of a partition (fgi_part_subscribe, fgi_part_last_wave_fanout, fgi_part_fanout_ids,
     //      fgi_part_fanout_detached, fgi_part_unsubscribe_peer)
-    if (minor) *minor = 10;
+    // 0.11: the delay timers in device memory (fgi_timers_open / _close / _set_delay / _set_now / _run_due /
+    //      _next_due / _stats_get / _list)
+    if (minor) *minor = 11;
     return FGI_OK;
 }
 
@@ -1962,6 +1964,7 @@ fgi_status fgi_destroy(fgi_graph* g) {
     hipSetDevice(g->device);
     if (g->stream) hipStreamSynchronize(g->stream);
     fgi::fanout_destroy(g);
+    fgi::timers_destroy(g);
     fgi::part_out_destroy(g);
     fgi::part_destroy(g);
     fgi::view_destroy(g);
@@ -2416,6 +2419,7 @@ fgi_status fgi_restore(fgi_graph* g) {
     g->flg_valid = false;
     g->flag_gate = g->snap_flag_gate;
     fanout_note(g, kCascNone);   // no wave's fan-out is left to make (the subscriptions themselves stay)
+    if (timers_on(g)) FGI_TRY(timers_restore(g));   // the delay timers' entries go; the clock and the delays stay
     g->flg_last = -1;
     g->flg_drop.clear();
     g->pflg_runs.clear();   // a partition's records too (fgi_part_last_flagged: 0 records)
@@ -2927,6 +2931,8 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
     if (out_detached) std::memcpy(out_detached, od.data(), n * sizeof(uint32_t));
     // subscriptions follow the node: a displaced node that lives on takes its entries to its detached handle
     if (fanout_live(g)) FGI_TRY(fanout_move(g, n, slot, od.data()));
+    // and so does its delay timer; a displaced node without one is armed under its detached handle
+    if (timers_on(g)) FGI_TRY(timers_move(g, n, slot, od.data()));
     return FGI_OK;
 }
 
@@ -3071,7 +3077,7 @@ struct Batch {
     fgi_status check_kinds(), ensure_capacities(), lay_out(const uint32_t* out_ids, uint64_t cap), stage(), alloc_temps();
     fgi_status launch(bool timed, const RecSink* sink), run(bool timed, uint32_t* applied);
     void note_runs(uint32_t end);
-    fgi_status view_sync(), sub_moves(uint32_t end), unpack(uint32_t* out_ids, uint64_t cap, uint64_t* out_n);
+    fgi_status view_sync(), sub_moves(uint32_t end), timer_moves(uint32_t end), unpack(uint32_t* out_ids, uint64_t cap, uint64_t* out_n);
     void report(fgi_batch_stats* stats);
 };
 
@@ -3315,7 +3321,10 @@ fgi_status Batch::stage() {
             bs[k].flags = reinterpret_cast<const uint8_t*>(D + in_off[4 * k + 3]);
         }
     }
-    if (n_take) std::memcpy(H, g->free_detached.data() + (g->free_detached.size() - n_take), n_take * 4);
+    // the free list's top first: the install kernels take entries 0, 1, ... of this list, and the host pops as
+    // many as they took off the top afterwards (a batch usually takes fewer than its begin_compute items)
+    for (uint64_t k = 0; k < n_take; ++k)
+        reinterpret_cast<uint32_t*>(H)[k] = g->free_detached[g->free_detached.size() - 1 - k];
     t_stage = clk::now();
     // the scratch words zeroed, then one upload of them and every input; the steps' handles as labels
     std::memset(scr_h, 0, scr_words * 8);
@@ -3421,6 +3430,38 @@ fgi_status Batch::sub_moves(uint32_t end) {
     }
     for (const uint32_t x : src) seen[x] = 0;
     return fanout_move(g, (uint32_t)src.size(), src.data(), dst.data());
+}
+
+// The delay timers follow the node too (timers.hip): behind the batch, the BEGIN_COMPUTE steps [0, end) move a
+// displaced node's timer to its detached handle or arm it there, in step order: a launch takes a slot once,
+// so a slot the batch displaced k times has its moves in k launches. Then the arm rule runs once over the
+// records of the batch's cascades, on the states the batch left.
+fgi_status Batch::timer_moves(uint32_t end) {
+    if (!timers_on(g)) return FGI_OK;
+    std::vector<std::vector<uint32_t>> src, dst;
+    std::vector<uint8_t>& seen = seen_scratch(g, g->ext_slots);   // a slot's moves so far; cleared again below
+    for (uint32_t k = 0; k < end && n_begin; ++k) {
+        const fgi_step& sp = steps[k];
+        if (sp.kind != FGI_STEP_BEGIN_COMPUTE) continue;
+        const uint32_t* o = reinterpret_cast<const uint32_t*>(H + res_off + bs[k].out_off);
+        for (uint32_t i = 0; i < sp.n; ++i) {
+            if (o[i] == FGI_NONE) continue;
+            const uint32_t round = seen[sp.handles[i]];
+            if (round == 255) return set_err(g, FGI_ENOTSUP, "a batch displaced slot %u more than 255 times with timers open", sp.handles[i]);
+            ++seen[sp.handles[i]];
+            if (src.size() <= round) {
+                src.resize(round + 1);
+                dst.resize(round + 1);
+            }
+            src[round].push_back(sp.handles[i]);
+            dst[round].push_back(o[i] - g->lbl_K);
+        }
+    }
+    for (const auto& v : src)
+        for (const uint32_t x : v) seen[x] = 0;
+    for (size_t r = 0; r < src.size(); ++r) FGI_TRY(timers_move(g, (uint32_t)src[r].size(), src[r].data(), dst[r].data()));
+    if (rec_on) FGI_TRY(timers_arm_records(g, g->brec, std::min<uint64_t>(scr_h[rcur_word], g->brec_cap), nullptr));
+    return FGI_OK;
 }
 
 // Launch the steps and wait, once: the counters, the pool top and every step's output come back in one copy,
@@ -3577,6 +3618,7 @@ fgi_status fgi_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* steps, 
     g->free_detached.resize(g->free_detached.size() - (size_t)b.scr_h[2]);
     FGI_TRY(b.view_sync());
     FGI_TRY(b.sub_moves(applied));
+    FGI_TRY(b.timer_moves(applied));
     if (applied < n_steps)
         return set_err(g, FGI_ECAPACITY, "step %u: out of detached handles (%zu free)", applied, g->free_detached.size());
 #if FGI_PROBE
@@ -3826,6 +3868,10 @@ fgi_status fgi_release(fgi_graph* g, uint32_t n, const uint32_t* handle) {
         if (fanout_live(g)) {   // a released handle's subscriptions go with it (fgi_sub_stats.dropped)
             const fgi_status fs = fanout_drop_handles(g, released, handle);
             if (st == FGI_OK) st = fs;
+        }
+        if (timers_on(g)) {   // and its delay timer (fgi_timer_stats.dropped)
+            const fgi_status ts = timers_drop_handles(g, released, handle);
+            if (st == FGI_OK) st = ts;
         }
         if (!view_on(g)) return st;
         fgi_status vs = view_refresh_host(g, handle, released);

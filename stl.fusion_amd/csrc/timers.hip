@@ -1,0 +1,679 @@
+// timers.hip — the delay timers in device memory (C-ABI 0.11): fgi_timers_open, _close,
+// _set_delay, _set_now, _run_due, _next_due, _stats_get, _list, and the hooks the wave and mutation entry
+// points call (timers_arm_records, timers_move, timers_drop_handles, timers_restore).
+//
+// Per boundary handle: a delay code (dly: 0 the graph's default, kCodeNever, else 1 + an index into the table
+// of distinct delays, dtab) and the index of the handle's entry in the record pool (ent, FGI_NONE without one).
+// The pool is a dense run [0, top) of 24-byte records {due, version, handle}; a dropped entry stays as a
+// tombstone (handle FGI_NONE) until the next compaction. The pool exists twice: the due pass reads one copy
+// and writes the entries it keeps into the other.
+//   k_tm_arm    the arm rule over candidates (flagged records, or every handle): a candidate's node word is
+//               read with its visit bit folded in; new entries take pool places with one atomic per wavefront
+//               (ballot + rank among the lanes). ent[h] doubles as the handle's lock within a launch, so a
+//               handle listed twice is armed once.
+//   k_tm_due    one pass over the pool: entries not yet due are compacted into the other copy, due ones
+//               leave; a due entry whose node still has its version and is Consistent with DelayStarted
+//               goes to the fired list. The list is sorted on the device and becomes the roots of one wave.
+//   k_tm_move   one lane per (slot, detached handle) pair of a displacement.
+//   k_tm_min    the smallest due time of the pool.
+// The pool never grows behind a wave: its capacity covers every handle that can hold an entry (those with a
+// delay of their own and the detached ones, or all of them with a default delay) plus the tombstones, and is
+// brought up to that by the calls that change the bound, all of which wait for the device anyway.
+// Everything is allocated by fgi_timers_open; a graph that never opens timers launches nothing here.
+#include "fgi_internal.h"
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <algorithm>
+#include <cstring>
+#include <unordered_map>
+
+namespace fgi {
+
+struct TimerRec {
+    unsigned long long due, version;
+    uint32_t handle, pad;
+};
+
+struct Timers {
+    uint64_t now = 0, default_delay = 0;
+    uint32_t* dly = nullptr;               // [ext_handles] delay codes
+    uint32_t* ent = nullptr;               // [ext_handles] pool index of the handle's entry
+    TimerRec* rec[2] = {nullptr, nullptr}; // [cap] the pool (rec[0]) and the due pass's destination
+    uint64_t cap = 0;
+    unsigned long long* dtab = nullptr;    // [dtab_cap] distinct delays; code c > 0 names dtab[c - 1]
+    uint64_t dtab_cap = 0;
+    std::vector<uint64_t> dtab_h;
+    std::unordered_map<uint64_t, uint32_t> dcode;
+    unsigned long long* ctr = nullptr;     // device counters (kT*), ctr_h: their pinned copy as of the last wait
+    unsigned long long* ctr_h = nullptr;
+    uint32_t* fired = nullptr;             // [fired_cap] the due pass's fired handles, then sorted: [fired_cap, 2 fired_cap)
+    uint64_t fired_cap = 0;
+    uint8_t* imm = nullptr;                // [imm_cap] ones: the fired roots' `immediately`
+    uint64_t imm_cap = 0;
+    uint32_t* up = nullptr;                // uploads of the host-array calls
+    uint64_t up_cap = 0;
+    uint64_t n_coded = 0;                  // handles with a delay code of their own (the most there were)
+    uint64_t tomb_ub = 0;                  // tombstones the pool may hold
+    uint64_t runs = 0;
+    double last_ms = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+namespace {
+
+constexpr int kTBlock = 256;
+constexpr uint32_t kCodeNever = 0xFFFFFFFFu;
+constexpr uint32_t kClaim = 0xFFFFFFFEu;   // ent[h] while a lane of the running launch works on h
+// device counters
+enum { kTTop = 0, kTArmed, kTFired, kTDropped, kTMoved, kTTomb, kTFail, kTNewTop, kTFiredN, kTCoded, kTMin, kTWords = 16 };
+
+// what every kernel reads a node and the table through
+struct TmTab {
+    const unsigned long long* node;
+    const uint32_t* vis;        // null: no unfolded visits
+    const uint32_t* s2l;        // null: no hot labels
+    uint32_t ext_slots, K, n_handles;
+    uint32_t* dly;
+    uint32_t* ent;
+    TimerRec* rec;
+    uint64_t cap;
+    const unsigned long long* dtab;
+    uint32_t n_dtab;
+    unsigned long long* ctr;
+    unsigned long long now, default_delay;
+};
+
+// the node word of boundary handle h, its visit bit folded in (fanout.hip's k_sub_insert reads it the same way)
+__device__ inline unsigned long long tm_word(const TmTab& a, uint32_t h) {
+    uint32_t l = h + a.K;
+    if (a.s2l && h < a.ext_slots) {
+        const uint32_t hot = a.s2l[h];
+        if (hot != FGI_NONE) l = hot;
+    }
+    unsigned long long w = a.node[l];
+    if (a.vis && ((a.vis[l >> 5] >> (l & 31)) & 1u)) w = visited_word(w);
+    return w;
+}
+__device__ inline bool tm_waiting(unsigned long long w) {
+    return (w & kVMask) != 0 && word_state(w) == FGI_CONSISTENT && (w & kW_DS) != 0;
+}
+__device__ inline unsigned long long tm_delay(const TmTab& a, uint32_t h) {
+    const uint32_t c = a.dly[h];
+    if (c == 0) return a.default_delay;
+    if (c == kCodeNever || c - 1 >= a.n_dtab) return FGI_TIMER_NEVER;
+    return a.dtab[c - 1];
+}
+
+// The arm rule on candidate h of every lane for which cand holds. Called by whole wavefronts.
+__device__ inline void tm_arm(const TmTab& a, bool cand, uint32_t h, uint32_t lane) {
+    bool fresh = false;
+    unsigned long long v = 0, due = 0;
+    if (cand && h < a.n_handles) {
+        const unsigned long long w = tm_word(a, h);
+        const unsigned long long d = tm_waiting(w) ? tm_delay(a, h) : 0ull;
+        if (d != 0 && d != FGI_TIMER_NEVER) {
+            v = w & kVMask;
+            due = a.now + d;
+            if (due < a.now || due == FGI_TIMER_NEVER) due = FGI_TIMER_NEVER - 1;
+            const uint32_t e = __hip_atomic_exchange(a.ent + h, kClaim, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+            if (e == FGI_NONE) {
+                fresh = true;
+            } else if (e != kClaim) {   // (kClaim: another lane of this launch has h, and will leave the same entry)
+                if (e < a.cap && a.rec[e].version != v) {   // another version's entry: overwritten
+                    a.rec[e].version = v;
+                    a.rec[e].due = due;
+                    atomicAdd(a.ctr + kTArmed, 1ull);
+                    atomicAdd(a.ctr + kTDropped, 1ull);
+                }
+                __hip_atomic_store(a.ent + h, e, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+    const unsigned long long m = __ballot(fresh);
+    if (!m) return;
+    const int leader = __ffsll((long long)m) - 1;
+    unsigned long long base = 0;
+    if ((int)lane == leader) base = atomicAdd(a.ctr + kTTop, (unsigned long long)__popcll(m));
+    base = __shfl(base, leader);
+    bool stored = false;
+    if (fresh) {
+        const unsigned long long idx = base + __popcll(m & ((1ull << lane) - 1));
+        if (idx < a.cap) {
+            a.rec[idx] = TimerRec{due, v, h, 0u};
+            __hip_atomic_store(a.ent + h, (uint32_t)idx, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            stored = true;
+        } else {   // never with the host's capacity bound: the call that reads the counters next fails
+            __hip_atomic_store(a.ent + h, FGI_NONE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            atomicAdd(a.ctr + kTFail, 1ull);
+        }
+    }
+    const unsigned long long ms = __ballot(stored);
+    if ((int)lane == leader && ms) atomicAdd(a.ctr + kTArmed, (unsigned long long)__popcll(ms));
+}
+
+// Candidates: flagged records (rec != null: boundary handle << 32 | flags), else every handle below n_max.
+// n = min(n_max, *n_dev). Wavefronts stride over runs of 64 candidates (wave-uniform trip count).
+__global__ __launch_bounds__(kTBlock) void k_tm_arm(TmTab a, const unsigned long long* rec, uint64_t n_max,
+                                                    const unsigned long long* n_dev) {
+    uint64_t n = n_max;
+    if (n_dev) {
+        const unsigned long long c = *n_dev;
+        if (c < n) n = c;
+    }
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t base = (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64; base < n; base += nwaves * 64) {
+        const uint64_t i = base + lane;
+        const bool cand = i < n;
+        const uint32_t h = !cand ? 0u : rec ? (uint32_t)(rec[i] >> 32) : (uint32_t)i;
+        tm_arm(a, cand, h, lane);
+    }
+}
+
+// The due pass over the pool [0, top) (top = min(ctr[kTTop], cap)): see the file comment. dst: the other copy.
+__global__ __launch_bounds__(kTBlock) void k_tm_due(TmTab a, TimerRec* dst, uint32_t* fired, uint64_t fired_cap) {
+    const unsigned long long t = a.ctr[kTTop];
+    const uint64_t top = t < a.cap ? t : a.cap;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t base = (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64; base < top; base += nwaves * 64) {
+        const uint64_t i = base + lane;
+        TimerRec r{0, 0, FGI_NONE, 0};
+        if (i < top) r = a.rec[i];
+        const bool live = r.handle < a.n_handles;
+        const bool is_due = live && r.due <= a.now;
+        const bool keep = live && !is_due;
+        bool fire = false;
+        if (is_due) {
+            const unsigned long long w = tm_word(a, r.handle);
+            fire = tm_waiting(w) && (w & kVMask) == r.version;
+            a.ent[r.handle] = FGI_NONE;
+        }
+        const unsigned long long mk = __ballot(keep), mf = __ballot(fire), md = __ballot(is_due && !fire);
+        unsigned long long bk = 0, bf = 0;
+        if (lane == 0) {
+            if (mk) bk = atomicAdd(a.ctr + kTNewTop, (unsigned long long)__popcll(mk));
+            if (mf) {
+                bf = atomicAdd(a.ctr + kTFiredN, (unsigned long long)__popcll(mf));
+                atomicAdd(a.ctr + kTFired, (unsigned long long)__popcll(mf));
+            }
+            if (md) atomicAdd(a.ctr + kTDropped, (unsigned long long)__popcll(md));
+        }
+        bk = __shfl(bk, 0);
+        bf = __shfl(bf, 0);
+        const unsigned long long below = (1ull << lane) - 1;
+        if (keep) {
+            const unsigned long long idx = bk + __popcll(mk & below);   // < top <= cap
+            dst[idx] = r;
+            a.ent[r.handle] = (uint32_t)idx;
+        }
+        if (fire) {
+            const unsigned long long idx = bf + __popcll(mf & below);
+            if (idx < fired_cap) fired[idx] = r.handle;
+            else atomicAdd(a.ctr + kTFail, 1ull);
+        }
+    }
+}
+
+// behind the due pass: the compacted copy is the pool
+__global__ void k_tm_commit(unsigned long long* ctr) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        ctr[kTTop] = ctr[kTNewTop];
+        ctr[kTTomb] = 0;
+    }
+}
+
+// pair i: the node that left slot from[i] lives on at to[i]. to[i] takes the slot's delay; the slot's entry
+// moves with it if it is the node's (same version), else the arm rule runs on to[i]. from[] distinct.
+__global__ __launch_bounds__(kTBlock) void k_tm_move(TmTab a, uint32_t n, const uint32_t* from, const uint32_t* to) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63;
+    bool arm = false;
+    uint32_t d = 0;
+    if (i < n) {
+        const uint32_t f = from[i];
+        d = to[i];
+        if (d != FGI_NONE && f != d && f < a.n_handles && d < a.n_handles) {
+            a.dly[d] = a.dly[f];
+            const unsigned long long w = tm_word(a, d);
+            const uint32_t e = a.ent[f];
+            if (e != FGI_NONE && e < a.cap && (w & kVMask) != 0 && a.rec[e].version == (w & kVMask)) {
+                const uint32_t old = a.ent[d];   // a detached handle handed out anew has none: released ones drop theirs
+                if (old != FGI_NONE && old < a.cap) {
+                    a.rec[old].handle = FGI_NONE;
+                    atomicAdd(a.ctr + kTTomb, 1ull);
+                    atomicAdd(a.ctr + kTDropped, 1ull);
+                }
+                a.rec[e].handle = d;
+                a.ent[d] = e;
+                a.ent[f] = FGI_NONE;
+                atomicAdd(a.ctr + kTMoved, 1ull);
+            } else {
+                arm = true;
+            }
+        }
+    }
+    tm_arm(a, arm, d, lane);
+}
+
+__global__ __launch_bounds__(kTBlock) void k_tm_drop(TmTab a, uint32_t n, const uint32_t* handles) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t h = handles[i];
+    if (h >= a.n_handles) return;
+    const uint32_t e = atomicExch(a.ent + h, FGI_NONE);   // a handle listed twice is dropped once
+    if (e == FGI_NONE || e >= a.cap) return;
+    a.rec[e].handle = FGI_NONE;
+    atomicAdd(a.ctr + kTTomb, 1ull);
+    atomicAdd(a.ctr + kTDropped, 1ull);
+}
+
+// handle[i] takes code[i]; ctr[kTCoded] gains the handles that got a code of their own less those that lost
+// theirs (handles distinct within a launch)
+__global__ __launch_bounds__(kTBlock) void k_tm_set_delay(uint32_t* dly, uint32_t n, const uint32_t* handle, const uint32_t* code,
+                                                          unsigned long long* ctr) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t old = dly[handle[i]], c = code[i];
+    dly[handle[i]] = c;
+    if (!old && c) atomicAdd(ctr + kTCoded, 1ull);
+    if (old && !c) atomicAdd(ctr + kTCoded, ~0ull);   // - 1
+}
+
+// ctr[kTMin] (set to FGI_TIMER_NONE first) = the smallest due time of the pool's entries
+__global__ __launch_bounds__(kTBlock) void k_tm_min(const TimerRec* rec, uint64_t cap, uint32_t n_handles, unsigned long long* ctr) {
+    const unsigned long long t = ctr[kTTop];
+    const uint64_t top = t < cap ? t : cap;
+    const uint64_t nthr = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long m = FGI_TIMER_NONE;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < top; i += nthr) {
+        const TimerRec r = rec[i];
+        if (r.handle < n_handles && r.due < m) m = r.due;
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long o = __shfl_xor(m, d);
+        if (o < m) m = o;
+    }
+    if ((threadIdx.x & 63) == 0 && m != FGI_TIMER_NONE) atomicMin(ctr + kTMin, m);
+}
+
+inline uint32_t tgrid(uint64_t n) { return (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, (n + kTBlock - 1) / kTBlock)); }
+
+TmTab tm_tab(const fgi_graph* g) {
+    const Timers* t = g->tim;
+    TmTab a{};
+    a.node = reinterpret_cast<const unsigned long long*>(g->node);
+    a.vis = g->v_dirty && !g->vis_stale ? g->vis_bm : nullptr;
+    a.s2l = g->lbl_hot ? g->s2l : nullptr;
+    a.ext_slots = g->ext_slots;
+    a.K = g->lbl_K;
+    a.n_handles = g->ext_handles;
+    a.dly = t->dly;
+    a.ent = t->ent;
+    a.rec = t->rec[0];
+    a.cap = t->cap;
+    a.dtab = t->dtab;
+    a.n_dtab = (uint32_t)t->dtab_h.size();
+    a.ctr = t->ctr;
+    a.now = t->now;
+    a.default_delay = t->default_delay;
+    return a;
+}
+
+// the counters back on the host (one wait). A pool that overflowed lost entries: the host's bound was wrong.
+fgi_status tm_sync(fgi_graph* g, const char* what) {
+    Timers* t = g->tim;
+    FGI_HIP(g, hipGetLastError());
+    FGI_HIP(g, hipMemcpyAsync(t->ctr_h, t->ctr, kTWords * 8, hipMemcpyDeviceToHost, g->stream));
+    FGI_HIP(g, hipStreamSynchronize(g->stream));
+    if (t->ctr_h[kTFail])
+        return set_err(g, FGI_ESTATE, "%s: the timer pool of %llu records overflowed (%llu entries lost)", what,
+                       (unsigned long long)t->cap, (unsigned long long)t->ctr_h[kTFail]);
+    return FGI_OK;
+}
+inline uint64_t tm_top(const Timers* t) { return std::min<uint64_t>(t->ctr_h[kTTop], t->cap); }
+inline uint64_t tm_stored(const Timers* t) { return tm_top(t) - std::min<uint64_t>(t->ctr_h[kTTomb], tm_top(t)); }
+
+// The pool's capacity covers every entry and tombstone it can come to hold before a call that waits next looks
+// (the file comment). Grows by copying; the caller's next kernel arguments are built afterwards.
+fgi_status tm_reserve(fgi_graph* g) {
+    Timers* t = g->tim;
+    const bool every = t->default_delay != 0 && t->default_delay != FGI_TIMER_NEVER;
+    const uint64_t holders = every ? g->ext_handles : std::min<uint64_t>(g->ext_handles, t->n_coded + g->n_detached);
+    const uint64_t need = holders + t->tomb_ub;
+    if (t->cap >= need && t->rec[0]) return FGI_OK;
+    const uint64_t want = std::max<uint64_t>({need, 2 * t->cap, 1024});
+    if (want >= kClaim) return set_err(g, FGI_ENOMEM, "the timer pool holds at most 2^32 - 3 records");
+    DevOwn<TimerRec> r0, r1;   // until they are installed
+    if (hipMalloc(reinterpret_cast<void**>(&r0.p), want * sizeof(TimerRec)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&r1.p), want * sizeof(TimerRec)) != hipSuccess)
+        return set_err(g, FGI_ENOMEM, "a timer pool of %llu records", (unsigned long long)want);
+    if (t->rec[0]) {
+        FGI_TRY(tm_sync(g, "growing the timer pool"));
+        const uint64_t top = tm_top(t);
+        if (top) FGI_HIP(g, hipMemcpyAsync(r0.p, t->rec[0], top * sizeof(TimerRec), hipMemcpyDeviceToDevice, g->stream));
+        FGI_HIP(g, hipStreamSynchronize(g->stream));
+    }
+    dfree(t->rec[0]);
+    dfree(t->rec[1]);
+    t->rec[0] = r0.release();
+    t->rec[1] = r1.release();
+    t->cap = want;
+    return FGI_OK;
+}
+
+// host words to the upload buffer (several arrays of n u32 each, back to back)
+fgi_status tm_upload(fgi_graph* g, uint64_t arrays, uint64_t n) {
+    Timers* t = g->tim;
+    return grow(g, &t->up, &t->up_cap, std::max<uint64_t>(arrays * n, 4096), "the timers' upload");
+}
+
+// what every entry point of the section but open and stats checks first
+fgi_status tm_usable(fgi_graph* g, const char* what) {
+    if (g->failed) return set_err(g, FGI_ESTATE, "%s: the graph is poisoned; fgi_restore or fgi_destroy", what);
+    if (!g->tim) return set_err(g, FGI_ESTATE, "%s: the graph's timers are not open (fgi_timers_open)", what);
+    hipSetDevice(g->device);
+    if (g->aw[0].busy || g->aw[1].busy) FGI_TRY(drain_async(g));
+    return FGI_OK;
+}
+
+}  // namespace
+
+fgi_status timers_arm_records(fgi_graph* g, const unsigned long long* rec, uint64_t n_max, const unsigned long long* n_dev) {
+    if (!timers_on(g) || !n_max) return FGI_OK;
+    hipLaunchKernelGGL(k_tm_arm, dim3(tgrid(n_max)), dim3(kTBlock), 0, g->stream, tm_tab(g), rec, n_max, n_dev);
+    FGI_HIP(g, hipGetLastError());
+    return FGI_OK;
+}
+
+fgi_status timers_move(fgi_graph* g, uint32_t n, const uint32_t* from, const uint32_t* to) {
+    if (!timers_on(g) || !n) return FGI_OK;
+    Timers* t = g->tim;
+    hipStream_t s = g->stream;
+    FGI_TRY(flush_vis(g));
+    FGI_TRY(tm_upload(g, 2, n));
+    FGI_HIP(g, hipMemcpyAsync(t->up, from, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    FGI_HIP(g, hipMemcpyAsync(t->up + n, to, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_tm_move, dim3((n + kTBlock - 1) / kTBlock), dim3(kTBlock), 0, s, tm_tab(g), n,
+                       (const uint32_t*)t->up, (const uint32_t*)(t->up + n));
+    // a moved entry may have overwritten a tombstone-to-be; the host arrays are the caller's: consumed when this returns
+    t->tomb_ub += n;
+    FGI_TRY(tm_sync(g, "moving a displaced node's timer"));
+    t->tomb_ub = t->ctr_h[kTTomb];
+    return tm_reserve(g);
+}
+
+fgi_status timers_drop_handles(fgi_graph* g, uint32_t n, const uint32_t* handles) {
+    if (!timers_on(g) || !n) return FGI_OK;
+    Timers* t = g->tim;
+    hipStream_t s = g->stream;
+    FGI_TRY(tm_upload(g, 1, n));
+    FGI_HIP(g, hipMemcpyAsync(t->up, handles, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_tm_drop, dim3((n + kTBlock - 1) / kTBlock), dim3(kTBlock), 0, s, tm_tab(g), n, (const uint32_t*)t->up);
+    FGI_TRY(tm_sync(g, "dropping a released handle's timer"));
+    t->tomb_ub = t->ctr_h[kTTomb];
+    return tm_reserve(g);
+}
+
+fgi_status timers_restore(fgi_graph* g) {
+    if (!timers_on(g)) return FGI_OK;
+    Timers* t = g->tim;
+    hipStream_t s = g->stream;
+    hipSetDevice(g->device);
+    FGI_HIP(g, hipMemcpyAsync(t->ctr_h, t->ctr, kTWords * 8, hipMemcpyDeviceToHost, s));
+    FGI_HIP(g, hipStreamSynchronize(s));
+    t->ctr_h[kTDropped] += tm_stored(t);   // every entry is dropped
+    t->ctr_h[kTTop] = t->ctr_h[kTTomb] = t->ctr_h[kTFail] = 0;
+    t->tomb_ub = 0;
+    FGI_HIP(g, hipMemcpyAsync(t->ctr, t->ctr_h, kTWords * 8, hipMemcpyHostToDevice, s));
+    FGI_HIP(g, hipMemsetAsync(t->ent, 0xFF, (size_t)g->ext_handles * 4, s));
+    FGI_HIP(g, hipStreamSynchronize(s));
+    return FGI_OK;
+}
+
+void timers_destroy(fgi_graph* g) {
+    Timers* t = g->tim;
+    if (!t) return;
+    void* dev[] = {t->dly, t->ent, t->rec[0], t->rec[1], t->dtab, t->ctr, t->fired, t->imm, t->up};
+    for (void* p : dev)
+        if (p) (void)hipFree(p);
+    if (t->ctr_h) (void)hipHostFree(t->ctr_h);
+    for (hipEvent_t e : t->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete t;
+    g->tim = nullptr;
+}
+
+}  // namespace fgi
+
+using namespace fgi;
+
+extern "C" {
+
+fgi_status fgi_timers_open(fgi_graph* g, const fgi_timers_config* cfg) {
+    if (!g || !cfg || cfg->struct_size < sizeof(fgi_timers_config)) return FGI_EINVAL;
+    if (g->failed) return set_err(g, FGI_ESTATE, "fgi_timers_open: the graph is poisoned; fgi_restore or fgi_destroy");
+    if (g->part || g->world > 1)
+        return set_err(g, FGI_ENOTSUP, "fgi_timers_open: the delay timers serve a single device, not a partition");
+    if (g->tim) return set_err(g, FGI_ESTATE, "fgi_timers_open: the graph's timers are open");
+    hipSetDevice(g->device);
+    if (g->aw[0].busy || g->aw[1].busy) FGI_TRY(drain_async(g));
+    Timers* t = new Timers();
+    g->tim = t;
+    t->now = cfg->now;
+    t->default_delay = cfg->default_delay;
+    hipStream_t s = g->stream;
+    if (hipMalloc(reinterpret_cast<void**>(&t->dly), (size_t)g->ext_handles * 4) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&t->ent), (size_t)g->ext_handles * 4) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&t->ctr), kTWords * 8) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&t->ctr_h), kTWords * 8, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreate(&t->ev[0]) != hipSuccess || hipEventCreate(&t->ev[1]) != hipSuccess) {
+        timers_destroy(g);
+        return set_err(g, FGI_ENOMEM, "the timer table of %u handles", g->ext_handles);
+    }
+    memset(t->ctr_h, 0, kTWords * 8);
+    fgi_status st = hip_check(g, hipMemsetAsync(t->dly, 0, (size_t)g->ext_handles * 4, s), "hipMemsetAsync");
+    if (st == FGI_OK) st = hip_check(g, hipMemsetAsync(t->ent, 0xFF, (size_t)g->ext_handles * 4, s), "hipMemsetAsync");
+    if (st == FGI_OK) st = hip_check(g, hipMemsetAsync(t->ctr, 0, kTWords * 8, s), "hipMemsetAsync");
+    if (st == FGI_OK) st = tm_reserve(g);
+    if (st == FGI_OK) st = flush_vis(g);
+    // a populated graph: every node already Consistent with DelayStarted, in one pass over the handles
+    if (st == FGI_OK && g->nodes_written) {
+        hipLaunchKernelGGL(k_tm_arm, dim3(tgrid(g->ext_handles)), dim3(kTBlock), 0, s, tm_tab(g), (const unsigned long long*)nullptr,
+                           (uint64_t)g->ext_handles, (const unsigned long long*)nullptr);
+        st = tm_sync(g, "fgi_timers_open");
+    }
+    if (st != FGI_OK) timers_destroy(g);
+    return st;
+}
+
+fgi_status fgi_timers_close(fgi_graph* g) {
+    if (!g) return FGI_EINVAL;
+    FGI_TRY(tm_usable(g, "fgi_timers_close"));
+    FGI_HIP(g, hipStreamSynchronize(g->stream));
+    timers_destroy(g);
+    return FGI_OK;
+}
+
+fgi_status fgi_timers_set_delay(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint64_t* delay) {
+    if (!g || (n && (!handle || !delay))) return FGI_EINVAL;
+    FGI_TRY(tm_usable(g, "fgi_timers_set_delay"));
+    Timers* t = g->tim;
+    for (uint32_t i = 0; i < n; ++i)
+        if (handle[i] >= g->ext_handles)
+            return set_err(g, FGI_EINVAL, "fgi_timers_set_delay: handle %u out of range at %u", handle[i], i);
+    if (!n) return FGI_OK;
+    {
+        std::vector<uint32_t> sorted(handle, handle + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) return set_err(g, FGI_EINVAL, "fgi_timers_set_delay: handle %u listed twice", *dup);
+    }
+    std::vector<uint32_t> code(n);
+    const size_t known = t->dtab_h.size();
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t d = delay[i];
+        if (d == 0 || d == FGI_TIMER_NEVER) {
+            code[i] = d ? kCodeNever : 0u;
+            continue;
+        }
+        auto it = t->dcode.find(d);
+        if (it == t->dcode.end()) {
+            if (t->dtab_h.size() + 2 >= kClaim) return set_err(g, FGI_ENOMEM, "fgi_timers_set_delay: too many distinct delays");
+            t->dtab_h.push_back(d);
+            it = t->dcode.emplace(d, (uint32_t)t->dtab_h.size()).first;
+        }
+        code[i] = it->second;
+    }
+    hipStream_t s = g->stream;
+    if (t->dtab_h.size() != known) {   // the table of distinct delays, whole (it is short: one entry per compute method)
+        if (t->dtab_cap < t->dtab_h.size()) FGI_HIP(g, hipStreamSynchronize(s));   // its readers are done before it is replaced
+        FGI_TRY(grow(g, &t->dtab, &t->dtab_cap, std::max<uint64_t>(2 * t->dtab_h.size(), 64), "the timers' delay table"));
+        FGI_HIP(g, hipMemcpyAsync(t->dtab, t->dtab_h.data(), t->dtab_h.size() * 8, hipMemcpyHostToDevice, s));
+    }
+    FGI_TRY(tm_upload(g, 2, n));
+    FGI_HIP(g, hipMemcpyAsync(t->up, handle, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    FGI_HIP(g, hipMemcpyAsync(t->up + n, code.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_tm_set_delay, dim3((n + kTBlock - 1) / kTBlock), dim3(kTBlock), 0, s, t->dly, n, (const uint32_t*)t->up,
+                       (const uint32_t*)(t->up + n), t->ctr);
+    FGI_TRY(tm_sync(g, "fgi_timers_set_delay"));
+    // (the most there ever were: a handle that lost its code may still hold an entry)
+    t->n_coded = std::max<uint64_t>(t->n_coded, (uint64_t)std::max<int64_t>(0, (int64_t)t->ctr_h[kTCoded]));
+    return tm_reserve(g);
+}
+
+fgi_status fgi_timers_set_now(fgi_graph* g, uint64_t now) {
+    if (!g) return FGI_EINVAL;
+    FGI_TRY(tm_usable(g, "fgi_timers_set_now"));
+    if (now < g->tim->now)
+        return set_err(g, FGI_EINVAL, "fgi_timers_set_now: %llu is before the clock (%llu)", (unsigned long long)now,
+                       (unsigned long long)g->tim->now);
+    g->tim->now = now;
+    return FGI_OK;
+}
+
+fgi_status fgi_timers_run_due(fgi_graph* g, uint64_t now, uint32_t* out_ids, uint64_t cap, uint64_t* out_n, uint64_t* out_fired,
+                              fgi_wave_stats* stats) {
+    if (!g) return FGI_EINVAL;
+    if (out_n) *out_n = 0;
+    if (out_fired) *out_fired = 0;
+    FGI_TRY(tm_usable(g, "fgi_timers_run_due"));
+    Timers* t = g->tim;
+    if (now < t->now)
+        return set_err(g, FGI_EINVAL, "fgi_timers_run_due: %llu is before the clock (%llu)", (unsigned long long)now,
+                       (unsigned long long)t->now);
+    FGI_TRY(tm_sync(g, "fgi_timers_run_due"));
+    t->now = now;
+    const uint64_t top = tm_top(t);
+    if (!top) return FGI_OK;
+    hipStream_t s = g->stream;
+    FGI_TRY(flush_vis(g));
+    if (t->fired_cap < top) {
+        dfree(t->fired);
+        t->fired_cap = 0;
+        FGI_TRY(dmalloc(g, &t->fired, 2 * t->cap));
+        t->fired_cap = t->cap;
+    }
+    FGI_HIP(g, hipMemsetAsync(t->ctr + kTNewTop, 0, 2 * 8, s));   // kTNewTop, kTFiredN
+    FGI_HIP(g, hipEventRecord(t->ev[0], s));
+    hipLaunchKernelGGL(k_tm_due, dim3(tgrid(top)), dim3(kTBlock), 0, s, tm_tab(g), t->rec[1], t->fired, t->fired_cap);
+    hipLaunchKernelGGL(k_tm_commit, dim3(1), dim3(64), 0, s, t->ctr);
+    FGI_HIP(g, hipEventRecord(t->ev[1], s));
+    std::swap(t->rec[0], t->rec[1]);
+    t->tomb_ub = 0;
+    FGI_TRY(tm_sync(g, "fgi_timers_run_due"));
+    float ms = 0;
+    t->last_ms = hipEventElapsedTime(&ms, t->ev[0], t->ev[1]) == hipSuccess ? ms : 0.0;
+    const uint64_t n_fired = std::min<uint64_t>(t->ctr_h[kTFiredN], t->fired_cap);
+    if (out_fired) *out_fired = n_fired;
+    if (!n_fired) return FGI_OK;
+    if (n_fired > 0xFFFFFFFFull) return set_err(g, FGI_ECAPACITY, "fgi_timers_run_due: %llu roots", (unsigned long long)n_fired);
+    // the fired handles ascending: the roots of one wave, every one `immediately`
+    uint32_t* roots = t->fired + t->fired_cap;
+    {
+        Tmp tt;
+        size_t tb = 0;
+        FGI_HIP(g, rocprim::radix_sort_keys(nullptr, tb, t->fired, roots, (size_t)n_fired, 0, 32, s));
+        void* tmp;
+        FGI_TRY(tmalloc(g, tt, reinterpret_cast<char**>(&tmp), tb));
+        FGI_HIP(g, rocprim::radix_sort_keys(tmp, tb, t->fired, roots, (size_t)n_fired, 0, 32, s));
+    }
+    if (t->imm_cap < n_fired) {
+        FGI_TRY(grow(g, &t->imm, &t->imm_cap, std::max<uint64_t>(n_fired, 4096), "the fired roots' flags"));
+        FGI_HIP(g, hipMemsetAsync(t->imm, 1, t->imm_cap, s));
+    }
+    ++t->runs;
+    FGI_TRY(run_wave(g, (uint32_t)n_fired, roots, t->imm, stats, true, out_ids ? WaveOut::kIds : WaveOut::kCount));
+    const uint64_t n = g->last_wave_n;
+    if (out_n) *out_n = n;
+    if (!out_ids) return FGI_OK;
+    if (n > cap) return FGI_ECAPACITY;   // the wave has run: fgi_last_wave_ids
+    FGI_TRY(ensure_ids(g));
+    if (n) FGI_HIP(g, hipMemcpyAsync(out_ids, g->inv_cur ? g->inv_cur : g->inv, n * 4, hipMemcpyDeviceToHost, s));
+    FGI_HIP(g, hipStreamSynchronize(s));
+    return FGI_OK;
+}
+
+fgi_status fgi_timers_next_due(fgi_graph* g, uint64_t* out_due, uint64_t* out_stored) {
+    if (!g || !out_due) return FGI_EINVAL;
+    *out_due = FGI_TIMER_NONE;
+    if (out_stored) *out_stored = 0;
+    FGI_TRY(tm_usable(g, "fgi_timers_next_due"));
+    Timers* t = g->tim;
+    hipStream_t s = g->stream;
+    FGI_HIP(g, hipMemsetAsync(t->ctr + kTMin, 0xFF, 8, s));
+    // (the grid follows the capacity: the count is on the device)
+    hipLaunchKernelGGL(k_tm_min, dim3(tgrid(std::min<uint64_t>(t->cap, 1ull << 16))), dim3(kTBlock), 0, s,
+                       (const TimerRec*)t->rec[0], t->cap, g->ext_handles, t->ctr);
+    FGI_TRY(tm_sync(g, "fgi_timers_next_due"));
+    *out_due = t->ctr_h[kTMin];
+    if (out_stored) *out_stored = tm_stored(t);
+    return FGI_OK;
+}
+
+fgi_status fgi_timers_stats_get(fgi_graph* g, fgi_timer_stats* out) {
+    if (!g || !out) return FGI_EINVAL;
+    memset(out, 0, sizeof(*out));
+    if (!g->tim) return FGI_OK;
+    FGI_TRY(tm_usable(g, "fgi_timers_stats_get"));
+    FGI_TRY(tm_sync(g, "fgi_timers_stats_get"));
+    const Timers* t = g->tim;
+    out->stored = tm_stored(t);
+    out->armed = t->ctr_h[kTArmed];
+    out->fired = t->ctr_h[kTFired];
+    out->dropped = t->ctr_h[kTDropped];
+    out->moved = t->ctr_h[kTMoved];
+    out->runs = t->runs;
+    out->last_kernel_ms = t->last_ms;
+    return FGI_OK;
+}
+
+fgi_status fgi_timers_list(fgi_graph* g, uint32_t* handle, uint64_t* version, uint64_t* due, uint64_t cap, uint64_t* out_n) {
+    if (!g) return FGI_EINVAL;
+    if (out_n) *out_n = 0;
+    FGI_TRY(tm_usable(g, "fgi_timers_list"));
+    FGI_TRY(tm_sync(g, "fgi_timers_list"));
+    const Timers* t = g->tim;
+    const uint64_t top = tm_top(t);
+    std::vector<TimerRec> recs(top);
+    if (top) {
+        FGI_HIP(g, hipMemcpyAsync(recs.data(), t->rec[0], top * sizeof(TimerRec), hipMemcpyDeviceToHost, g->stream));
+        FGI_HIP(g, hipStreamSynchronize(g->stream));
+    }
+    recs.erase(std::remove_if(recs.begin(), recs.end(), [&](const TimerRec& r) { return r.handle >= g->ext_handles; }), recs.end());
+    std::sort(recs.begin(), recs.end(), [](const TimerRec& a, const TimerRec& b) { return a.handle < b.handle; });
+    if (out_n) *out_n = recs.size();
+    if (!handle && !version && !due) return FGI_OK;
+    if (recs.size() > cap)
+        return set_err(g, FGI_ECAPACITY, "fgi_timers_list: %llu entries, the buffers hold %llu", (unsigned long long)recs.size(),
+                       (unsigned long long)cap);
+    for (size_t i = 0; i < recs.size(); ++i) {
+        if (handle) handle[i] = recs[i].handle;
+        if (version) version[i] = recs[i].version;
+        if (due) due[i] = recs[i].due;
+    }
+    return FGI_OK;
+}
+
+}  // extern "C"

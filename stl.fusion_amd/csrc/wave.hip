@@ -3915,6 +3915,8 @@ static fgi_status launch_flagged(fgi_graph* g, int k) {
     const uint32_t grid = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, (words + kBlock - 1) / kBlock));
     hipLaunchKernelGGL(k_flag_list, dim3(grid), dim3(kBlock), 0, s, a);
     FGI_HIP(g, hipGetLastError());
+    // the delay timers of what the wave flagged, armed on the device from the records (timers.hip)
+    if (timers_on(g)) FGI_TRY(timers_arm_records(g, g->flg_out[k], g->n_handles, g->flg_cnt + k));
     return FGI_OK;
 }
 

@@ -125,6 +125,21 @@ class SubStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TimersConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("default_delay", C.c_uint64),
+                ("now", C.c_uint64)]
+
+
+class TimerStats(C.Structure):
+    """fgi_timer_stats: the delay timers in device memory (armed == fired + dropped + stored)."""
+    _fields_ = [("stored", C.c_uint64), ("armed", C.c_uint64), ("fired", C.c_uint64), ("dropped", C.c_uint64),
+                ("moved", C.c_uint64), ("runs", C.c_uint64), ("last_kernel_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+TIMER_NEVER = TIMER_NONE = 0xFFFFFFFFFFFFFFFF
 VIEW_PLANES = ("registered", "consistent", "computing", "ioso", "delay_started", "has_delay")
 
 
@@ -261,6 +276,14 @@ SIGNATURES = {
     "fgi_part_fanout_ids": [_G, C.c_uint64, _u32p, C.c_uint32, _u64p, _u64p, _u32p, C.c_uint64, _u64p],
     "fgi_part_fanout_detached": [_G, C.c_uint64, _u32p, C.c_uint32, _u64p, _u64p, _u32p, C.c_uint64, _u64p],
     "fgi_part_unsubscribe_peer": [_G, C.c_uint32, _u64p],
+    "fgi_timers_open": [_G, C.POINTER(TimersConfig)],
+    "fgi_timers_close": [_G],
+    "fgi_timers_set_delay": [_G, C.c_uint32, _u32p, _u64p],
+    "fgi_timers_set_now": [_G, C.c_uint64],
+    "fgi_timers_run_due": [_G, C.c_uint64, _u32p, C.c_uint64, _u64p, _u64p, C.POINTER(WaveStats)],
+    "fgi_timers_next_due": [_G, _u64p, _u64p],
+    "fgi_timers_stats_get": [_G, C.POINTER(TimerStats)],
+    "fgi_timers_list": [_G, _u32p, _u64p, _u64p, C.c_uint64, _u64p],
 }
 
 _lib = None
@@ -690,6 +713,54 @@ class Graph:
         st = SubStats()
         self._check(self.lib.fgi_sub_stats_get(self.h, C.byref(st)), "sub_stats")
         return st.as_dict()
+
+    # ---- delay timers in device memory (C-ABI 0.11) ----
+    def timers_open(self, default_delay: int = 0, now: int = 0):
+        """fgi_timers_open: the graph keeps its delayed invalidations' timers on the device from here on."""
+        cfg = TimersConfig(C.sizeof(TimersConfig), 0, default_delay, now)
+        self._check(self.lib.fgi_timers_open(self.h, C.byref(cfg)), "timers_open")
+
+    def timers_close(self):
+        self._check(self.lib.fgi_timers_close(self.h), "timers_close")
+
+    def timers_set_delay(self, handles, delays):
+        """fgi_timers_set_delay: per handle, 0 = the default delay, TIMER_NEVER = never store an entry."""
+        h, d = _u32(handles), _u64(delays)
+        if len(h) != len(d):
+            raise ValueError("timers_set_delay: handles and delays differ in length")
+        self._check(self.lib.fgi_timers_set_delay(self.h, len(h), _ptr(h, C.c_uint32), _ptr(d, C.c_uint64)),
+                    "timers_set_delay")
+
+    def timers_set_now(self, now: int):
+        self._check(self.lib.fgi_timers_set_now(self.h, now), "timers_set_now")
+
+    def timers_run_due(self, now: int, stats: Optional[WaveStats] = None) -> Tuple[np.ndarray, int]:
+        """fgi_timers_run_due: (ids the fired timers' wave invalidated, entries fired)."""
+        ids = np.zeros(self.n_handles, np.uint32)
+        n, fired = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.fgi_timers_run_due(self.h, now, _ptr(ids, C.c_uint32), len(ids), C.byref(n), C.byref(fired),
+                                                C.byref(stats) if stats is not None else None), "timers_run_due")
+        return ids[:n.value].copy(), int(fired.value)
+
+    def timers_next_due(self) -> Tuple[int, int]:
+        """fgi_timers_next_due: (smallest due time stored or TIMER_NONE, entries stored)."""
+        due, stored = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.fgi_timers_next_due(self.h, C.byref(due), C.byref(stored)), "timers_next_due")
+        return int(due.value), int(stored.value)
+
+    def timers_stats(self) -> dict:
+        st = TimerStats()
+        self._check(self.lib.fgi_timers_stats_get(self.h, C.byref(st)), "timers_stats")
+        return st.as_dict()
+
+    def timers_list(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """fgi_timers_list: (handles, versions, due times) of the stored entries, ascending by handle."""
+        n = C.c_uint64()
+        self._check(self.lib.fgi_timers_list(self.h, None, None, None, 0, C.byref(n)), "timers_list")
+        h, v, d = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint64)
+        self._check(self.lib.fgi_timers_list(self.h, _ptr(h, C.c_uint32), _ptr(v, C.c_uint64), _ptr(d, C.c_uint64),
+                                             len(h), C.byref(n)), "timers_list")
+        return h, v, d
 
     def last_wave_flagged(self) -> Tuple[np.ndarray, np.ndarray]:
         """fgi_last_wave_flagged: (handles, state_flags) of the nodes the last call's cascade flagged

@@ -133,6 +133,11 @@ void ComputedRegistry::MoveSubs(uint32_t from, uint32_t to) {
 }
 
 std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& input, bool has_delay) {
+    return BeginComputeImpl(input, has_delay, std::chrono::nanoseconds::zero());
+}
+
+std::shared_ptr<Computed> ComputedRegistry::BeginComputeImpl(const std::string& input, bool has_delay,
+                                                             std::chrono::nanoseconds delay) {
     Sync();
     const uint32_t s = SlotOf(input, true);
     auto c = std::make_shared<Computed>();
@@ -141,11 +146,23 @@ std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& inpu
     c->slot_ = s;
     c->handle_ = s;
     c->version_ = NextVersion(current_[s] ? current_[s]->version_ : 0);
+    c->delay_ = delay;
     const uint8_t hd = has_delay ? 1 : 0;
     uint32_t detached = FGI_NONE;
     fgi_wave_stats ws{};
     Check(FGI_CALL(fgi_begin_compute, g_, 1, &s, &c->version_, &hd, &detached, &ws), "fgi_begin_compute");
     StartTimers(0);   // the delayed nodes the displacement cascade reached
+    if (dev_timers_) {
+        // the engine moved or armed the displaced node's timer and gave its detached handle the slot's delay;
+        // the slot's delay is the new node's from here on (one call, and only when it changes)
+        using ns = std::chrono::nanoseconds;
+        const uint64_t d = delay == ns::max() ? FGI_TIMER_NEVER : delay <= ns::zero() ? 0ull : (uint64_t)delay.count();
+        if (slot_delay_[s] != d) {
+            Check(FGI_CALL(fgi_timers_set_delay, g_, 1, &s, &d), "fgi_timers_set_delay");
+            slot_delay_[s] = d;
+        }
+        if (detached != FGI_NONE) maybe_armed_ = true;
+    }
     auto old = current_[s];
     if (detached != FGI_NONE) {   // displaced but alive (Computing / delayed): its handle moves
         if (old) {
@@ -156,7 +173,9 @@ std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& inpu
             // set does not list its slot, which names the new node now): its timer starts here, or follows
             // it if it was already running
             auto it = timers_.find(s);
-            if (it != timers_.end() && it->second.version == old->version_) {
+            if (dev_timers_) {
+                // (the engine's move kernel did the same on its table)
+            } else if (it != timers_.end() && it->second.version == old->version_) {
                 timers_[detached] = it->second;
                 timers_.erase(s);
             } else {
@@ -184,9 +203,7 @@ std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& inpu
 }
 
 std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& input, std::chrono::nanoseconds delay) {
-    auto c = BeginCompute(input, delay != std::chrono::nanoseconds::zero());
-    c->delay_ = delay;
-    return c;
+    return BeginComputeImpl(input, delay != std::chrono::nanoseconds::zero(), delay);
 }
 
 uint32_t ComputedRegistry::AddUsed(Computed& dependant, Computed& used) {
@@ -613,6 +630,72 @@ void ComputedRegistry::Sync() {
     RunDueTimers();
 }
 
+// DeviceTimers: the engine's timer set opens with the first registry call that needs the registry current
+void ComputedRegistry::EnsureTimers() {
+    if (dev_timers_ || !DeviceTimers) return;
+    using ns = std::chrono::nanoseconds;
+    fgi_timers_config cfg{};
+    cfg.struct_size = sizeof(cfg);
+    cfg.default_delay = DefaultInvalidationDelay > ns::zero() && DefaultInvalidationDelay != ns::max()
+                            ? (uint64_t)DefaultInvalidationDelay.count() : 0ull;
+    cfg.now = 0;
+    Check(FGI_CALL(fgi_timers_open, g_, &cfg), "fgi_timers_open");
+    epoch_ = Clock();
+    slot_delay_.assign(n_slots_, 0);
+    dev_timers_ = true;
+}
+
+// Clock in the engine's ticks: nanoseconds since the timers opened, never running backwards
+uint64_t ComputedRegistry::NowTicks() {
+    const auto d = std::chrono::duration_cast<std::chrono::nanoseconds>(Clock() - epoch_).count();
+    return std::max<uint64_t>(ticks_, d > 0 ? (uint64_t)d : 0ull);
+}
+
+size_t ComputedRegistry::PendingTimers() const {
+    if (!dev_timers_) return timers_.size();
+    fgi_timer_stats st{};
+    Check(FGI_CALL(fgi_timers_stats_get, g_, &st), "fgi_timers_stats_get");
+    return (size_t)st.stored;
+}
+
+// One engine call per clock tick that can fire something. While no wave or displacement has run since the
+// last look (maybe_armed_) and the clock is short of the engine's next due time, the tick costs the engine
+// nothing but its clock (fgi_timers_set_now: no device work), which the next wave arms by.
+size_t ComputedRegistry::RunDueTimersDevice() {
+    if (in_timers_) return 0;
+    CompletePending();
+    const uint64_t now = NowTicks();
+    if (!maybe_armed_ && now < next_due_) {
+        if (now > ticks_) {
+            Check(FGI_CALL(fgi_timers_set_now, g_, now), "fgi_timers_set_now");
+            ticks_ = now;
+        }
+        return 0;
+    }
+    maybe_armed_ = false;   // before the fan-out: its callbacks may run waves of their own
+    fgi_wave_stats ws{};
+    uint64_t n = 0, fired = 0;
+    uint32_t* ids = IdsBuffer(1024);
+    fgi_status s = FGI_CALL(fgi_timers_run_due, g_, now, ids, ids_cap_, &n, &fired, &ws);
+    if (s == FGI_ECAPACITY) {   // the wave itself completed; fetch the ids with the right size
+        ids = IdsBuffer(n);
+        s = FGI_CALL(fgi_last_wave_ids, g_, ids, n, &n);
+    }
+    Check(s, "fgi_timers_run_due");
+    ticks_ = now;
+    Check(FGI_CALL(fgi_timers_next_due, g_, &next_due_, nullptr), "fgi_timers_next_due");   // the fired wave's own flagged set included
+    if (!fired) return 0;
+    last_ = ws;
+    pred_v_ = n;
+    struct Guard {
+        bool& b;
+        ~Guard() { b = false; }
+    } guard{in_timers_};
+    in_timers_ = true;
+    Dispatch(ids, n);   // exactly as RunWave fans out
+    return (size_t)fired;
+}
+
 void ComputedRegistry::StartTimer(uint32_t handle, LTag version, std::chrono::nanoseconds delay) {
     using ns = std::chrono::nanoseconds;
     if (delay == ns::zero()) delay = DefaultInvalidationDelay;
@@ -625,6 +708,10 @@ void ComputedRegistry::StartTimer(uint32_t handle, LTag version, std::chrono::na
 }
 
 void ComputedRegistry::StartTimers(uint64_t ticket) {
+    if (dev_timers_) {   // the engine armed them behind the wave; the next tick asks it what is due
+        maybe_armed_ = true;
+        return;
+    }
     auto read = [&](uint32_t* ids, uint32_t* flags, uint64_t cap, uint64_t* n) {
         return ticket ? FGI_CALL(fgi_wave_wait_flagged, g_, ticket, ids, flags, cap, n) : FGI_CALL(fgi_last_wave_flagged, g_, ids, flags, cap, n);
     };
@@ -656,7 +743,7 @@ void ComputedRegistry::StartTimers(uint64_t ticket) {
 }
 
 void ComputedRegistry::DropTimers(const uint32_t* ids, const uint64_t* bits, uint64_t words, uint64_t n) {
-    if (timers_.empty() || n == 0) return;
+    if (dev_timers_ || timers_.empty() || n == 0) return;   // (the engine removes a stale entry when it comes due)
     for (auto it = timers_.begin(); it != timers_.end();) {
         const uint32_t h = it->first;
         const bool hit = bits ? ((uint64_t)(h >> 6) < words && ((bits[h >> 6] >> (h & 63)) & 1ull))
@@ -666,6 +753,8 @@ void ComputedRegistry::DropTimers(const uint32_t* ids, const uint64_t* bits, uin
 }
 
 size_t ComputedRegistry::RunDueTimers() {
+    EnsureTimers();
+    if (dev_timers_) return RunDueTimersDevice();
     if (in_timers_ || timers_.empty()) return 0;
     CompletePending();   // a wave in flight may have invalidated a due node: its fan-out removes the entry
     const TimePoint now = Clock();

@@ -231,7 +231,14 @@ class ComputedRegistry {
     std::function<TimePoint()> Clock = [] { return std::chrono::steady_clock::now(); };
     std::chrono::nanoseconds DefaultInvalidationDelay{0};
     size_t RunDueTimers();
-    size_t PendingTimers() const { return timers_.size(); }
+    size_t PendingTimers() const;
+    // The timers live in the engine (fgi_timers_*, fgi.h): its kernels arm them behind every wave from the
+    // flagged records and fgi_timers_run_due fires them, so the registry neither downloads a flagged set nor
+    // keeps an entry per node. Set before the first BeginCompute (with DefaultInvalidationDelay, which the
+    // engine takes when the timers open) and left alone afterwards. Clock maps to ticks: nanoseconds since the
+    // timers opened. BeginCompute(input, delay) sets the slot's delay. PendingTimers() is the engine's stored
+    // count, which keeps the entry of a node invalidated before its due time until that time comes.
+    bool DeviceTimers = false;
     // `_ = svc.Get(input)` inside a scope: TryUseExisting's Invalidate branch (ComputedExt.cs:29-35)
     void InvalidateInput(const std::string& input);
     // Slot-level roots (inputs already resolved by the host, e.g. bulk-registered nodes)
@@ -248,8 +255,8 @@ class ComputedRegistry {
     // The subscriptions live in the engine (fgi_subscribe) and a wave's per-peer lists come from its join on
     // the device (fgi_last_wave_fanout; fgi_fanout_ids for an asynchronous ticket's ids) instead of the gather
     // over sub_head_. Set before the first Subscribe and left alone afterwards; at most FGI_MAX_PEERS peers.
-    // Subscribing to a node that is Invalidated already delivers its call id at once. Handler objects and
-    // delay timers keep their host path.
+    // Subscribing to a node that is Invalidated already delivers its call id at once. Handler objects keep
+    // their host path; the delay timers have a switch of their own (DeviceTimers).
     bool DeviceFanout = false;
     uint32_t FanoutThreads = 0;   // 0: hardware concurrency, capped at 16
 
@@ -319,6 +326,17 @@ class ComputedRegistry {
     };
     std::unordered_map<uint32_t, Timer> timers_;   // handle -> its pending delayed invalidation
     bool in_timers_ = false;                 // RunDueTimers is running (its own wave does not re-enter it)
+    // DeviceTimers: opened by the first registry call; the engine's clock as last set; a lower bound of its next
+    // due time, void (maybe_armed_) once a wave or a displacement may have armed an entry; each slot's delay
+    // as the engine holds it
+    std::shared_ptr<Computed> BeginComputeImpl(const std::string& input, bool has_delay, std::chrono::nanoseconds delay);
+    void EnsureTimers();
+    uint64_t NowTicks();
+    size_t RunDueTimersDevice();
+    bool dev_timers_ = false, maybe_armed_ = false;
+    TimePoint epoch_{};
+    uint64_t ticks_ = 0, next_due_ = ~0ull;
+    std::vector<uint64_t> slot_delay_;
     std::deque<uint64_t> pending_;           // asynchronous waves queued, not yet completed (ticket order)
     uint64_t last_ticket_ = 0;
     LTag ltag_ = 0x100000;
