@@ -560,8 +560,10 @@ fgi_status fgi_part_unsubscribe_peer(fgi_graph* g, uint32_t peer, uint64_t* out_
  * Counter identity, over a graph's life since fgi_timers_open: armed == fired + dropped + stored. `moved`
  * counts entries that changed handle (a move neither arms nor drops). runs: fgi_timers_run_due calls that
  * launched a wave. last_kernel_ms: device time of the last fgi_timers_run_due's own kernels (HIP events).
- * Memory: 8 bytes per handle (a delay code and an entry index) plus 48 bytes per possible entry: handles with
- * a delay of their own and detached handles, or every handle when default_delay is set.
+ * Memory: 8 bytes per handle (a delay code and an entry index) plus 48 bytes per possible entry: the entries
+ * stored when fgi_timers_set_delay was last called (a slot set back to delay 0 keeps its entry until that
+ * comes due), the slots with a delay of their own and the detached handles, at most every handle; or every
+ * handle when default_delay is set. The pool does not shrink.
  * Before fgi_timers_open every other call here returns FGI_ESTATE and fgi_timers_stats_get returns zeros; on a
  * poisoned graph FGI_ESTATE; fgi_timers_open on a partitioned graph FGI_ENOTSUP. */
 #define FGI_TIMER_NEVER 0xFFFFFFFFFFFFFFFFull

@@ -16,9 +16,10 @@
 //               goes to the fired list. The list is sorted on the device and becomes the roots of one wave.
 //   k_tm_move   one lane per (slot, detached handle) pair of a displacement.
 //   k_tm_min    the smallest due time of the pool.
-// The pool never grows behind a wave: its capacity covers every handle that can hold an entry (those with a
-// delay of their own and the detached ones, or all of them with a default delay) plus the tombstones, and is
-// brought up to that by the calls that change the bound, all of which wait for the device anyway.
+// The pool never grows behind a wave: its capacity covers every handle that holds an entry or can come to hold
+// one (the entries stored, the slots with a delay of their own and the detached handles, or every handle with a
+// default delay) plus the tombstones, and is brought up to that by the calls that change the bound, all of
+// which wait for the device anyway (tm_reserve).
 // Everything is allocated by fgi_timers_open; a graph that never opens timers launches nothing here.
 #include "fgi_internal.h"
 
@@ -53,7 +54,7 @@ struct Timers {
     uint64_t imm_cap = 0;
     uint32_t* up = nullptr;                // uploads of the host-array calls
     uint64_t up_cap = 0;
-    uint64_t n_coded = 0;                  // handles with a delay code of their own (the most there were)
+    uint64_t holders = 0;                  // handles that hold an entry or can gain one (tm_reserve; never lowered)
     uint64_t tomb_ub = 0;                  // tombstones the pool may hold
     uint64_t runs = 0;
     double last_ms = 0;
@@ -269,14 +270,16 @@ __global__ __launch_bounds__(kTBlock) void k_tm_drop(TmTab a, uint32_t n, const 
     atomicAdd(a.ctr + kTDropped, 1ull);
 }
 
-// handle[i] takes code[i]; ctr[kTCoded] gains the handles that got a code of their own less those that lost
-// theirs (handles distinct within a launch)
+// handle[i] takes code[i]; ctr[kTCoded] gains the slots that got a code of their own less those that lost
+// theirs (handles distinct within a launch). Detached handles are not counted: a move copies a code onto one
+// without this kernel, and tm_reserve counts every one of them anyway.
 __global__ __launch_bounds__(kTBlock) void k_tm_set_delay(uint32_t* dly, uint32_t n, const uint32_t* handle, const uint32_t* code,
-                                                          unsigned long long* ctr) {
+                                                          uint32_t ext_slots, unsigned long long* ctr) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t old = dly[handle[i]], c = code[i];
     dly[handle[i]] = c;
+    if (handle[i] >= ext_slots) return;
     if (!old && c) atomicAdd(ctr + kTCoded, 1ull);
     if (old && !c) atomicAdd(ctr + kTCoded, ~0ull);   // - 1
 }
@@ -336,11 +339,22 @@ inline uint64_t tm_top(const Timers* t) { return std::min<uint64_t>(t->ctr_h[kTT
 inline uint64_t tm_stored(const Timers* t) { return tm_top(t) - std::min<uint64_t>(t->ctr_h[kTTomb], tm_top(t)); }
 
 // The pool's capacity covers every entry and tombstone it can come to hold before a call that waits next looks
-// (the file comment). Grows by copying; the caller's next kernel arguments are built afterwards.
+// (the file comment): cap >= holders + tomb_ub. The pool's places [0, top) are its entries and its tombstones:
+// an entry takes a new place only when its handle had none (an overwrite and a move reuse the place), a dropped
+// one leaves a tombstone (at most tomb_ub), and places come back only in a due pass, which leaves the entries
+// alone. A handle holds at most one entry, so the entries never outnumber P = the handles that hold one now or
+// can gain one: with a default delay any handle, else the slots with a delay code of their own and the
+// detached handles (a move copies the slot's code onto one). A slot that lost its code keeps its entry until
+// that comes due, so it stays in P by its entry, not by its code; the most codes there ever were is no bound
+// once codes pass from one set of slots to another. Without a default delay P gains members only in
+// fgi_timers_set_delay, whose last wait knows |P| <= stored + coded slots + detached handles; everything else
+// (waves, moves, releases, due passes, fgi_restore) only moves entries within P or takes members out.
+// `holders` is the largest such value seen, so it is never lowered between two due passes.
+// Grows by copying; the caller's next kernel arguments are built afterwards.
 fgi_status tm_reserve(fgi_graph* g) {
     Timers* t = g->tim;
     const bool every = t->default_delay != 0 && t->default_delay != FGI_TIMER_NEVER;
-    const uint64_t holders = every ? g->ext_handles : std::min<uint64_t>(g->ext_handles, t->n_coded + g->n_detached);
+    const uint64_t holders = every ? g->ext_handles : std::min<uint64_t>(g->ext_handles, t->holders);
     const uint64_t need = holders + t->tomb_ub;
     if (t->cap >= need && t->rec[0]) return FGI_OK;
     const uint64_t want = std::max<uint64_t>({need, 2 * t->cap, 1024});
@@ -536,10 +550,10 @@ fgi_status fgi_timers_set_delay(fgi_graph* g, uint32_t n, const uint32_t* handle
     FGI_HIP(g, hipMemcpyAsync(t->up, handle, (size_t)n * 4, hipMemcpyHostToDevice, s));
     FGI_HIP(g, hipMemcpyAsync(t->up + n, code.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_tm_set_delay, dim3((n + kTBlock - 1) / kTBlock), dim3(kTBlock), 0, s, t->dly, n, (const uint32_t*)t->up,
-                       (const uint32_t*)(t->up + n), t->ctr);
+                       (const uint32_t*)(t->up + n), g->ext_slots, t->ctr);
     FGI_TRY(tm_sync(g, "fgi_timers_set_delay"));
-    // (the most there ever were: a handle that lost its code may still hold an entry)
-    t->n_coded = std::max<uint64_t>(t->n_coded, (uint64_t)std::max<int64_t>(0, (int64_t)t->ctr_h[kTCoded]));
+    // the entries stored now (a slot that lost its code may hold one), the coded slots, the detached handles
+    t->holders = std::max<uint64_t>(t->holders, tm_stored(t) + t->ctr_h[kTCoded] + g->n_detached);
     return tm_reserve(g);
 }
 

@@ -65,6 +65,60 @@ def test_open_on_a_populated_graph(pkg, gpu_available):
     M.scn_open_populated(_maker(pkg))
 
 
+def _runs_match(drv):
+    assert drv.g.timers_stats()["runs"] == drv.c["runs"]
+
+
+@pytest.mark.parametrize("labels", [-1, 1])
+def test_past_one_grid(pkg, gpu_available, labels):
+    """Every grid-stride loop of timers.hip on its second trip (test_past_one_grid_model states the sizes)."""
+    drv = M.scn_past_one_grid(_maker(pkg, labels))
+    _runs_match(drv)
+    assert drv.c["runs"] == 5 and drv.seen["stale"] == 3000
+
+
+def test_past_one_grid_capacity(pkg, gpu_available):
+    """fgi_timers_run_due with a short id buffer at the large size: the scenario's first steps on an engine
+    alone, then its tick(2) through the raw call. What it must return is taken from the scenario's plan
+    (test_past_one_grid_model checks that against the model)."""
+    fgi = pkg.fgi
+    arrays, _, _, _, leaves, delays, one = M._grid_plan()
+    want = M.grid_tick2_ids()
+    g = _engine(pkg, len(arrays[0]), *arrays, n_detached=M.GRID_DET)
+    g.timers_open(default_delay=7)
+    g.timers_set_delay(leaves, delays)
+    g.invalidate([0])
+    g.invalidate([1])
+    ids, fired = g.timers_run_due(1)
+    assert list(ids) == [one] and fired == 1
+    ids, n, fired = np.zeros(4096, np.uint32), C.c_uint64(), C.c_uint64()
+    st = g.lib.fgi_timers_run_due(g.h, 2, ids.ctypes.data_as(C.POINTER(C.c_uint32)), len(ids), C.byref(n), C.byref(fired), None)
+    assert st == fgi.ECAPACITY and n.value == len(want) == 5642 and fired.value == 5642
+    assert np.array_equal(g.last_wave_ids(), want)
+    assert g.timers_stats()["runs"] == 2 and g.timers_next_due() == (4, 278_491 - 1 - 5642)
+
+
+def test_pool_growth(pkg, gpu_available):
+    drv = M.scn_pool_growth(_maker(pkg))
+    _runs_match(drv)
+    assert drv.c["moved"] == 450 and drv.c["dropped"] == 150 and drv.c["fired"] == 3750
+
+
+def test_delay_churn(pkg, gpu_available):
+    """Entries that outlive their handle's delay code count towards the pool's capacity (timers.hip,
+    tm_reserve): with a bound of the most codes there ever were, the second wave overflows the pool and every
+    later call returns FGI_ESTATE."""
+    drv = M.scn_delay_churn(_maker(pkg))
+    _runs_match(drv)
+    assert drv.c == dict(armed=4000, fired=4000, dropped=0, moved=0, runs=2)
+
+
+def test_saturation(pkg, gpu_available):
+    drv = M.scn_saturation(_maker(pkg))
+    _runs_match(drv)
+    assert drv.g.timers_next_due() == (pkg.fgi.TIMER_NONE, 0)
+
+
 def test_batches_hand_out_each_detached_handle_once(pkg, gpu_available):
     """Two batches whose BEGIN_COMPUTE steps displace fewer live nodes than they have items (1 of 6, then 2 of
     6): nothing is released, so the three detached handles differ and the first still names its node. (A timer

@@ -38,6 +38,10 @@ class Driver:
         self.now, self.default = now, default_delay
         self.c = dict(armed=0, fired=0, dropped=0, moved=0, runs=0)
         self.seen = dict(never=0, overwrites=0, stale=0, displaced_armed=0)
+        # what the steps were made of, for the model-alone tests: ("wave", nodes flagged), ("tick", entries stored
+        # going in, entries fired), ("move", pairs of one displacement), ("release", entries dropped), and what a
+        # scenario adds itself
+        self.trace = []
 
     # ---- the rules of fgi.h ----
     def states(self):
@@ -122,8 +126,10 @@ class Driver:
         before = self.states()
         self._oracle_wave(roots, imm)
         after = self.states()
-        for h in expected_flagged(before, after)[0]:
+        flagged = expected_flagged(before, after)[0]
+        for h in flagged:
             self._arm(h, after)
+        self.trace.append(("wave", len(flagged)))
         want = self._invalidated(before, after)
         if self.g:
             if direction is not None:
@@ -142,6 +148,7 @@ class Driver:
         self.now = now
         st = self.states()
         due = sorted(h for h, (_, t) in self.entries.items() if t <= now)
+        stored = len(self.entries)
         fire = []
         for h in due:
             v, _ = self.entries.pop(h)
@@ -151,6 +158,7 @@ class Driver:
                 self.c["dropped"] += 1
                 self.seen["stale"] += 1
         self.c["fired"] += len(fire)
+        self.trace.append(("tick", stored, len(fire)))
         want = np.zeros(0, np.uint32)
         if fire:
             self.c["runs"] += 1
@@ -195,6 +203,7 @@ class Driver:
             self._arm(h, after)
         for s, d in moves:
             self._move(s, d, after)
+        self.trace.append(("move", len(moves)))
         self.check()
         return [d for _, d in moves]
 
@@ -220,11 +229,13 @@ class Driver:
         self.check()
 
     def release(self, handles):
+        dropped = self.c["dropped"]
         for h in _u32(handles):
             del self.det[int(h)]
             self.free.append(int(h))
             if self.entries.pop(int(h), None) is not None:
                 self.c["dropped"] += 1
+        self.trace.append(("release", self.c["dropped"] - dropped))
         if self.g:
             self.g.release(_u32(handles))
         self.check()
@@ -526,6 +537,144 @@ def scn_open_populated(make):
     return drv
 
 
+def hub_arrays(sizes, seed, started=()):
+    """One hub per entry of sizes (handles 0 .. len(sizes) - 1), hub k -> sizes[k] leaves, hub after hub; every
+    leaf has an InvalidationDelay, the listed ones DelayStarted already. Returns (arrays, the hubs' leaves)."""
+    H, n = len(sizes), len(sizes) + int(sum(sizes))
+    versions = O.version_of(seed, np.arange(n, dtype=np.uint64)).copy()
+    flags = np.full(n, CONSISTENT, np.uint32)
+    flags[H:] |= F_HD
+    flags[np.asarray(started, np.int64)] |= F_DS
+    leaf = np.arange(H, n, dtype=np.uint32)
+    src = np.repeat(np.arange(H, dtype=np.uint32), sizes)
+    bounds = H + np.concatenate([[0], np.cumsum(sizes)])
+    return (versions, flags, src, leaf, versions[leaf]), [leaf[a - H:b - H] for a, b in zip(bounds[:-1], bounds[1:])]
+
+
+GRID_A, GRID_B, GRID_DET = 280_000, 4_096 + 37, 64
+
+
+@functools.lru_cache(maxsize=None)
+def _grid_plan():
+    """scn_past_one_grid's graph and delays (computed once, read-only afterwards): the arrays, the leaves of
+    hub 0 and of hub 1, the leaves already started, the delay of every leaf, and the one leaf with delay 1."""
+    n = 2 + GRID_A + GRID_B
+    a0 = np.arange(2, 2 + GRID_A, dtype=np.uint32)
+    started = np.concatenate([a0[::131][:2000], np.arange(n - 37, n, dtype=np.uint32)])
+    arrays, (A, B) = hub_arrays([GRID_A, GRID_B], 31, started)
+    leaves = np.concatenate([A, B])
+    delays = np.full(len(leaves), 100, np.uint64)
+    for r, d in ((3, 2), (7, 4), (11, 0), (13, NEVER)):
+        delays[leaves % 50 == r] = d
+    one = int(B[5])
+    delays[one - 2] = 1
+    assert len(started) == 2037 and one not in set(started.tolist())
+    for a in arrays + (A, B, started, leaves, delays):
+        a.setflags(write=False)
+    return arrays, A, B, started, leaves, delays, one
+
+
+def scn_past_one_grid(make, until=None):
+    """Two hubs over 280,000 and 4,133 leaves, every leaf delayed, default delay 7: every grid-stride loop of
+    the timer kernels makes a second trip (the arm kernel over every handle at open and over 278,000 records, the
+    due pass over more than 262,144 entries three times, the min-reduction over more than 65,536), the last
+    wavefront of the last trip is partial, and ticks fire more than 4,096 entries. until: stop after that many
+    ticks."""
+    arrays, A, B, started, leaves, delays, one = _grid_plan()
+    drv = make(arrays, GRID_DET, default_delay=7)
+    drv.open()                         # 2,000 started leaves spread over A and the last 37 handles of the graph
+    assert sorted(drv.entries) == sorted(started.tolist())
+    drv.set_delay(leaves, delays)
+    assert list(drv.invalidate([0])) == [0]
+    before = len(drv.entries)
+    assert one not in drv.entries
+    assert list(drv.invalidate([1])) == [1]
+    # the unique smallest due time belongs to an entry armed behind `before` others (nothing has left the pool)
+    assert [h for h, (_, t) in drv.entries.items() if t == 1] == [one] and min(t for _, t in drv.entries.values()) == 1
+    drv.trace.append(("min_after", before))
+    ticks = 0
+    for now in (1, 2, 4, 7, 100):
+        if until is not None and ticks == until:
+            return drv
+        if now == 4:   # entries of nodes that go before their due time: stale when they come due (at 4, 7, 100)
+            stale = np.array(sorted(drv.entries)[::90][:3000], np.uint32)
+            assert len(stale) == 3000
+            assert np.array_equal(drv.invalidate(stale, np.ones(len(stale), np.uint8)), stale)
+        drv.tick(now)
+        ticks += 1
+    assert not drv.entries
+    return drv
+
+
+def scn_pool_growth(make):
+    """Hub 0 -> 900 leaves A, hub 1 -> 3,000 leaves B, 512 detached handles, no default delay: the pool grows
+    while it holds 600 entries, the fired list is reallocated behind it, the delay table passes 64 delays, two
+    displacements of 300 and 150 stored nodes around a release of 150 detached handles with entries."""
+    arrays, (A, B) = hub_arrays([900, 3000], 33)
+    drv = make(arrays, 512)
+    drv.open()
+    drv.set_delay(A, np.where(np.arange(len(A)) % 3 == 0, 3, 50).astype(np.uint64))
+    drv.invalidate([0])
+    assert len(drv.entries) == 900
+    assert drv.tick(3)[1] == 300
+    drv.trace.append(("delays", len(set(drv.delay.values())), len(drv.entries)))
+    drv.set_delay(B, (20 + np.arange(len(B)) % 200).astype(np.uint64))
+    drv.trace.append(("delays", len(set(drv.delay.values())), len(drv.entries)))
+    drv.invalidate([1])
+    assert len(drv.entries) == 3600
+    held = np.array(sorted(drv.entries), np.uint32)
+    first = np.concatenate([held[held < B[0]][:100], held[held >= B[0]][:200]])
+    v = drv.states()[0]
+    d1 = drv.begin_compute(first, v[first] + np.uint64(10), np.ones(len(first), np.uint8))
+    assert len(d1) == 300 and drv.c["moved"] == 300
+    drv.release(d1[::2])
+    assert drv.c["dropped"] == 150 and len(drv.entries) == 3450
+    second = held[held >= B[0]][200:350]
+    d2 = drv.begin_compute(second, v[second] + np.uint64(10), np.ones(len(second), np.uint8))
+    assert len(d2) == 150 and drv.c["moved"] == 450
+    assert len(set(d2) & set(d1[::2])) >= 100      # released handles handed out again
+    assert drv.tick(30)[1] >= 100 and len(drv.entries) >= 3000
+    drv.tick(400)
+    assert not drv.entries
+    return drv
+
+
+def scn_delay_churn(make):
+    """Delay codes pass from the leaves of hub 0 to those of hub 1 while the first ones' entries are still
+    stored: the pool holds the old entries and the new ones together."""
+    arrays, (A, B) = hub_arrays([2000, 2000], 35)
+    drv = make(arrays, 0)
+    drv.open()
+    drv.set_delay(A, np.full(len(A), 5, np.uint64))
+    drv.invalidate([0])
+    drv.set_delay(A, np.zeros(len(A), np.uint64))      # by fgi.h the entries stay
+    assert len(drv.entries) == 2000
+    drv.set_delay(B, np.full(len(B), 5, np.uint64))
+    drv.set_now(1)
+    drv.invalidate([1])
+    drv.trace.append(("churn", len(drv.entries), len(A)))
+    assert drv.tick(5)[1] == 2000
+    assert drv.tick(6)[1] == 2000
+    return drv
+
+
+def scn_saturation(make):
+    """scn_chain's graph at now = 2^64 - 10: a + b -> c -> d (delay 100: now + delay wraps), f (never) and
+    g (delay 9: now + delay == FGI_TIMER_NEVER) hang off c. Both due times are FGI_TIMER_NEVER - 1."""
+    now = 2**64 - 10
+    drv = make(chain_arrays(7, [(0, 1), (1, 2), (2, 3), (3, 4), (2, 5), (2, 6)], delayed=[3, 5, 6]), 0, now=now)
+    drv.open()
+    drv.set_delay([3, 5, 6], [100, NEVER, 9])
+    assert list(drv.invalidate([0])) == [0, 1, 2]
+    v = drv.states()[0]
+    assert drv.entries == {3: (int(v[3]), NEVER - 1), 6: (int(v[6]), NEVER - 1)} and drv.seen["never"] == 1
+    ids, fired = drv.tick(NEVER - 2)
+    assert len(ids) == 0 and fired == 0 and len(drv.entries) == 2
+    ids, fired = drv.tick(NEVER - 1)
+    assert list(ids) == [3, 4, 6] and fired == 2 and not drv.entries
+    return drv
+
+
 def _alone(arrays, n_det, **kw):
     return Driver(arrays, n_det, **kw)
 
@@ -567,3 +716,75 @@ def test_batch_model():
 def test_async_and_open_model():
     scn_async(_alone)
     scn_open_populated(_alone)
+
+
+# ---- the large scenarios against the sizes timers.hip's kernels and buffers are written for -------------------
+GRID_LANES = 1024 * 256    # tgrid(): at most 1,024 blocks of kTBlock = 256 lanes; k_tm_arm and k_tm_due stride past it
+MIN_THREADS = 1 << 16      # fgi_timers_next_due launches k_tm_min over at most 2^16 threads
+IMM_FIRST = 4096           # fgi_timers_run_due: the fired roots' flags (imm) start at 4,096 bytes
+DTAB_FIRST = 64            # fgi_timers_set_delay: the delay table (dtab) starts at 64 delays
+POOL_FIRST = 1024          # tm_reserve: the pool's smallest capacity
+MOVE_BLOCK = 256           # timers_move launches k_tm_move with kTBlock = 256 pairs per block
+
+
+def _traced(drv, kind):
+    return [t[1:] for t in drv.trace if t[0] == kind]
+
+
+def test_past_one_grid_model():
+    drv = scn_past_one_grid(_alone)
+    _, A, B, started, leaves, delays, one = _grid_plan()
+    assert drv.n + drv.n_det > GRID_LANES and (drv.n + drv.n_det) % 64 != 0      # the pass over every handle at open
+    assert started.max() >= GRID_LANES and started.max() == drv.n - 1
+    waves, ticks = _traced(drv, "wave"), _traced(drv, "tick")
+    assert waves[0][0] == 278_000 and waves[0][0] > GRID_LANES                   # records of one arm launch
+    assert waves[1][0] == len(B) - 37 == 4096
+    assert [t[0] for t in ticks[:2]] == [278_491, 278_490]
+    assert sum(t[0] > GRID_LANES for t in ticks) >= 2, ticks                     # due passes with a second trip
+    assert [t[0] > GRID_LANES for t in ticks] == [True, True, True, True, False], ticks
+    assert any(t[0] > GRID_LANES and t[0] % 64 != 0 for t in ticks)              # ... whose last wavefront is partial
+    assert ticks[0][1] == 1 and ticks[1][1] == 5642
+    assert sum(t[1] > IMM_FIRST for t in ticks) >= 2, ticks
+    assert _traced(drv, "min_after")[0][0] > MIN_THREADS
+    assert drv.seen["stale"] == 3000 and drv.seen["never"] >= 5000
+    assert drv.c["armed"] == drv.c["fired"] + drv.c["dropped"] == 278_491 and drv.c["runs"] == 5
+    # what test_gpu_timers.py's capacity case expects of tick(2), from the plan alone
+    short = scn_past_one_grid(_alone, until=1)
+    want, fired = short.tick(2)
+    assert fired == 5642 and np.array_equal(want, grid_tick2_ids())
+
+
+def grid_tick2_ids():
+    """The handles scn_past_one_grid's tick(2) invalidates: the leaves with delay 2 that the waves started."""
+    _, _, _, started, leaves, delays, _ = _grid_plan()
+    return np.setdiff1d(leaves[delays == 2], started).astype(np.uint32)
+
+
+def test_pool_growth_model():
+    drv = scn_pool_growth(_alone)
+    (d0, held0), (d1, held1) = _traced(drv, "delays")
+    assert d0 <= DTAB_FIRST < d1 and d1 == 201                 # the table is regrown by the second set_delay
+    assert held0 == held1 == 600                               # ... and so is the pool, holding entries:
+    assert POOL_FIRST < held1 + len(drv.delay) + drv.n_det     # the bound passes the capacity the pool has then
+    moves = [m[0] for m in _traced(drv, "move")]
+    assert moves == [300, 150] and moves[0] > MOVE_BLOCK
+    assert _traced(drv, "release") == [(150,)] and 150 >= 100  # tombstones going into the next due pass
+    ticks = _traced(drv, "tick")
+    assert ticks[0] == (900, 300)
+    assert ticks[1][0] == 3450 and ticks[1][0] + 150 > 2 * POOL_FIRST   # the pool passed the fired list made at tick(3)
+    assert drv.c == dict(armed=3900, fired=3750, dropped=150, moved=450, runs=3)
+
+
+def test_delay_churn_model():
+    drv = scn_delay_churn(_alone)
+    (stored, a), = _traced(drv, "churn")
+    # A bound of "the most delay codes there ever were" (|A|) gives a pool of max(|A|, 2 * 1,024) records: the
+    # pool starts at 1,024 and grows to the larger of the bound and its double. The scenario stores more than
+    # that, and reaches twice the larger of |A| and 1,024 (with 2 x 2,000 leaves it equals it: 4,000).
+    assert stored == 4000 and stored > max(a, 2 * POOL_FIRST) and stored >= 2 * max(a, POOL_FIRST)
+    assert drv.c == dict(armed=4000, fired=4000, dropped=0, moved=0, runs=2)
+
+
+def test_saturation_model():
+    drv = scn_saturation(_alone)
+    assert drv.c == dict(armed=2, fired=2, dropped=0, moved=0, runs=1)
