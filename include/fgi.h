@@ -522,8 +522,9 @@ fgi_status fgi_part_unsubscribe_peer(fgi_graph* g, uint32_t peer, uint64_t* out_
  * (Computed.cs:183-197) and then schedules its own timer, which later calls Invalidate(true)
  * (ComputedExt.cs:10-45, the Timeouts.Invalidate timer set). The engine keeps that timer set in device memory:
  * at most one entry (handle, version, due) per boundary handle, armed by kernels queued behind the calls that
- * flag nodes, fired by one call per clock tick. Single-device graphs only, off until fgi_timers_open; a graph
- * that never opens timers allocates and launches nothing for any of this.
+ * flag nodes, fired by one call per clock tick. This section serves single-device graphs (a rank of a partition:
+ * the next section), off until fgi_timers_open; a graph that never opens timers allocates and launches nothing
+ * for any of this.
  * Clock: uint64_t ticks in a unit the host chooses; the engine only adds and compares. The graph holds `now`;
  * fgi_timers_set_now and fgi_timers_run_due advance it, a value below the current one is FGI_EINVAL and
  * changes nothing.
@@ -565,7 +566,9 @@ fgi_status fgi_part_unsubscribe_peer(fgi_graph* g, uint32_t peer, uint64_t* out_
  * comes due), the slots with a delay of their own and the detached handles, at most every handle; or every
  * handle when default_delay is set. The pool does not shrink.
  * Before fgi_timers_open every other call here returns FGI_ESTATE and fgi_timers_stats_get returns zeros; on a
- * poisoned graph FGI_ESTATE; fgi_timers_open on a partitioned graph FGI_ENOTSUP. */
+ * poisoned graph FGI_ESTATE; fgi_timers_open on a partitioned graph FGI_ENOTSUP (fgi_part_timers_open), and so do
+ * fgi_timers_set_delay and fgi_timers_run_due there, whether or not the rank's timers are open (before 0.12 they
+ * returned FGI_ESTATE on a rank, whose timers could not be open). */
 #define FGI_TIMER_NEVER 0xFFFFFFFFFFFFFFFFull
 #define FGI_TIMER_NONE 0xFFFFFFFFFFFFFFFFull /* fgi_timers_next_due: nothing stored */
 typedef struct fgi_timers_config {
@@ -586,6 +589,75 @@ fgi_status fgi_timers_next_due(fgi_graph* g, uint64_t* out_due, uint64_t* out_st
 fgi_status fgi_timers_stats_get(fgi_graph* g, fgi_timer_stats* out);
 fgi_status fgi_timers_list(fgi_graph* g, uint32_t* handle, uint64_t* version, uint64_t* due, uint64_t cap,
                            uint64_t* out_n);
+
+/* ---- delay timers per rank of a partition (C-ABI 0.12; timers.hip) -------------------- */
+/* The same timers on a partitioned graph: each rank keeps the entries of its own local handles in its own
+ * device memory, arms them behind its own share of every cascade, and a clock tick is ONE collective call whose
+ * due entries, from all ranks, become the roots of one partitioned wave. A partition that never opens timers
+ * allocates and launches nothing for this. The contract is the section above's, per rank, with these differences.
+ * The table: a rank's table covers its local handles, addressed as fgi_dump_states and the rank's state view
+ * address them: h < n_slots is global slot rank * block + h in the host's numbering (partition codes are never
+ * visible), the rank's detached handles follow; the handles [n_local, n_slots) of a short last rank never hold
+ * a node and never an entry. The state read is the node word with the rank's visit bit folded in, as
+ * fgi_part_subscribe reads it: no fold, no pass over the graph.
+ * fgi_part_timers_open: rank-local, no collective. FGI_ENOTSUP on a graph that is not partitioned (use
+ * fgi_timers_open), FGI_ESTATE on a poisoned graph or with the timers already open. On a populated rank it arms
+ * every handle whose node is already Consistent with InvalidationDelayStarted.
+ * fgi_part_timers_set_delay: rank-local; slots are global ids. A slot >= n_global or a slot listed twice is
+ * FGI_EINVAL and nothing is stored. A slot the rank does not own is skipped, so a host may hand every rank the
+ * same list or each rank its share, as with fgi_part_subscribe. A detached handle takes its slot's delay by
+ * the move, as above.
+ * fgi_timers_close, fgi_timers_set_now, fgi_timers_next_due, fgi_timers_stats_get and fgi_timers_list take no
+ * slot arguments and serve a rank's table as they are (fgi_timers_list returns local handles; a host takes the
+ * minimum of the ranks' next_due). fgi_timers_set_delay and fgi_timers_run_due return FGI_ENOTSUP on a
+ * partitioned graph: use the calls of this section.
+ * Arming: every fgi_part_* call that runs cascades arms once, behind its last cascade and its moves, with a
+ * kernel queued on the rank's stream: fgi_part_invalidate, _host, _bits and _all, each rank of
+ * fgi_part_local_invalidate, fgi_part_begin_compute, fgi_part_set_output, and fgi_part_run_batch once for the
+ * whole batch (also when a later step is refused after earlier ones were applied). The candidates are the
+ * rank's records of the call (what fgi_part_last_flagged returns), counted on the device; the arm rule runs on
+ * the states the call left. Nothing waits and nothing is copied: a wave's host_syncs are what they are without
+ * timers. A call that runs no cascade arms nothing.
+ * Moves and drops: fgi_part_begin_compute, directly or as a batch's step, moves the entry of an owned slot to the
+ * detached handle it hands out (or arms it there), beside the subscriptions' move. fgi_release drops a detached
+ * handle's entry; fgi_restore drops every entry of the rank and keeps its clock and delays.
+ * Firing, fgi_part_timers_run_due(now): collective, every rank calls it with the same `now`.
+ *  - Agreement first. Each rank's verdict (timers open, graph not poisoned, now >= its clock) and its `now` travel
+ *    with the call's first collective. If any rank refuses or the `now` values differ, every rank returns the
+ *    same status, FGI_ESTATE for a refusing rank, FGI_EINVAL for a clock or `now` problem, fgi_last_error names
+ *    the rank, no rank removes an entry and nothing runs.
+ *  - The due pass runs on each rank's own pool (a rank with an empty pool launches nothing but joins the
+ *    collectives): it removes what is due, drops what went stale and separates the fired handles into owned
+ *    slots and detached handles.
+ *  - The fired slots of all ranks, as global ids, are gathered in rank order: the ascending root list, identical
+ *    on every rank. If it is empty no wave runs and every rank's last-wave results stay as they are. Otherwise
+ *    ONE partitioned wave runs with immediately = 1, driven as fgi_part_invalidate drives one:
+ *    fgi_part_last_wave_ids, _bits, fgi_part_wave_ids_dev, fgi_part_last_flagged, fgi_part_last_wave_fanout, the
+ *    rank's state view and the statistics follow it, and its own flagged set arms at `now`, so timers cascade.
+ *    out_ids / cap / out_n follow fgi_part_invalidate_host's contract (this rank's ids, ascending; a short cap:
+ *    FGI_ECAPACITY with *out_n set, the wave has run and fgi_part_last_wave_ids returns the list).
+ *  - *out_fired (nullable) counts this rank's fired entries, slots and detached handles. fgi_timer_stats.runs
+ *    counts the calls that launched a wave and is the same on every rank.
+ *  - Detached handles: no partitioned cascade reaches a detached node (the section on the fan-out per rank), so
+ *    a due entry on a detached handle that passes the fire test is removed, counted in `fired` and reported, not
+ *    cascaded; the engine does not change the node word. *out_fired_detached (nullable) is this rank's count and
+ *    fgi_part_timers_fired_detached returns them: this rank's local detached handles, ascending, valid until
+ *    the rank's next fgi_part_timers_run_due, fgi_restore or fgi_timers_close. A second call returns the same
+ *    list; a short cap returns FGI_ECAPACITY with *out_n set and loses nothing. The host ends that node itself,
+ *    as it does for the fan-out (fgi_part_fanout_detached, then fgi_release).
+ * fgi_part_local_timers_run_due runs the call on every rank of an in-process group, one host thread per rank
+ * (out_fired, out_fired_detached, stats: p entries each, nullable); ids are then read per rank with
+ * fgi_part_last_wave_ids. */
+fgi_status fgi_part_timers_open(fgi_graph* g, const fgi_timers_config* cfg);
+fgi_status fgi_part_timers_set_delay(fgi_graph* g, uint32_t n, const uint32_t* slot /*global*/, const uint64_t* delay);
+fgi_status fgi_part_timers_run_due(fgi_graph* g, uint64_t now, uint32_t* out_ids /*nullable*/, uint64_t cap,
+                                   uint64_t* out_n, uint64_t* out_fired /*nullable*/,
+                                   uint64_t* out_fired_detached /*nullable*/, fgi_wave_stats* stats /*nullable*/);
+fgi_status fgi_part_timers_fired_detached(fgi_graph* g, uint32_t* out_handles /*nullable*/, uint64_t cap,
+                                          uint64_t* out_n);
+fgi_status fgi_part_local_timers_run_due(fgi_graph* const* gs, uint32_t p, uint64_t now,
+                                         uint64_t* out_fired /*p, nullable*/, uint64_t* out_fired_detached /*p, nullable*/,
+                                         fgi_wave_stats* stats /*p, nullable*/);
 
 /* ---- streaming batches (BASELINE.json configs[4]) ------------------------------- */
 /* One step of a batch: the arguments of the matching single call. */

@@ -823,7 +823,7 @@ struct fgi_graph {
     int casc_kind = 0;
     int opt_fanout_path = 0;           // FGI_OPT_FANOUT_PATH: 0 by what the wave left, 1 id list, 2 bitmap, 3 (measurement) a rank's bitmap renumbered whole
     bool tmp_poison = false;           // FGI_TMP_POISON=1: every temporary is handed out filled with 0xA5
-    fgi::Timers* tim = nullptr;        // the delay timers (timers.hip), null until fgi_timers_open
+    fgi::Timers* tim = nullptr;        // the delay timers (timers.hip), null until fgi_timers_open / fgi_part_timers_open
 };
 
 // ---- internal entry points shared between translation units ----------------------------------
@@ -1109,6 +1109,11 @@ inline bool timers_on(const fgi_graph* g) { return g->tim != nullptr; }
 // the arm rule over flagged records (boundary handle << 32 | flags) on the device: n_max of them, or *n_dev
 // if that is less (n_dev nullable). Queued on the graph's stream; nothing waits.
 fgi_status timers_arm_records(fgi_graph* g, const unsigned long long* rec, uint64_t n_max, const unsigned long long* n_dev);
+// a rank of a partition (fgi_part_timers_open): the arm rule over the records the call's cascades left in prec,
+// counted by pcur[0] on the device, on the states the call left. Called once behind the call's last cascade and
+// its moves by every fgi_part_* entry point that runs cascades; queued on the rank's stream, nothing waits. A
+// no-op when the call ran no cascade or the rank cannot flag.
+fgi_status timers_arm_part(fgi_graph* g);
 // displaced nodes: the entry (from[i], the version of the node now at to[i]) moves to to[i], else the arm
 // rule runs on to[i]; to[i] takes from[i]'s delay (boundary handles, host arrays, from[] distinct; to[i] ==
 // FGI_NONE: nothing happens)

@@ -1874,7 +1874,9 @@ fgi_status fgi_version(uint32_t* major, uint32_t* minor) {
     //      fgi_part_fanout_detached, fgi_part_unsubscribe_peer)
     // 0.11: the delay timers in device memory (fgi_timers_open / _close / _set_delay / _set_now / _run_due /
     //      _next_due / _stats_get / _list)
-    if (minor) *minor = 11;
+    // 0.12: the same per rank of a partition (fgi_part_timers_open / _set_delay / _run_due / _fired_detached,
+    //      fgi_part_local_timers_run_due)
+    if (minor) *minor = 12;
     return FGI_OK;
 }
 
@@ -4059,10 +4061,11 @@ fgi_status part_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, co
         FGI_TRY(install_nodes(g, m, cnt[1], ds, dv, dd, dcls, dout, tf));
         FGI_TRY(d2h(g, od.data(), dout, m));
         g->free_detached.resize(g->free_detached.size() - (size_t)cnt[1]);
-        if (fanout_live(g)) {   // subscriptions follow the node (fanout.hip): the slot's handle is slot - base
-            std::vector<uint32_t> from(m);
+        if (fanout_live(g) || timers_on(g)) {   // subscriptions (fanout.hip) and delay timers (timers.hip) follow the node
+            std::vector<uint32_t> from(m);      // the slot's handle is slot - base
             for (uint32_t j = 0; j < m; ++j) from[j] = part_slot_of(g, ls[j] + pv.base) - pv.base;
             FGI_TRY(fanout_move(g, m, from.data(), od.data()));
+            FGI_TRY(timers_move(g, m, from.data(), od.data()));
         }
         if (view_on(g)) {   // the owned slots' new nodes and the detached handles handed out (the cascade's share is in)
             view_begin(g);
@@ -4256,6 +4259,7 @@ fgi_status fgi_part_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot
     std::vector<uint32_t> ids, ms;
     slot = part_codes_in(g, n, slot, ms);   // partition codes; outputs are slots again
     FGI_TRY(part_begin_compute(g, n, slot, version, has_delay, out_detached, stats, &ids));
+    FGI_TRY(timers_arm_part(g));   // behind the displacement cascade and the moves
     return part_copy_ids(ids, out_ids, cap, out_n);
 }
 
@@ -4272,6 +4276,7 @@ fgi_status fgi_part_set_output(fgi_graph* g, uint32_t n, const uint32_t* slot, u
     std::vector<uint32_t> ids, ms;
     slot = part_codes_in(g, n, slot, ms);
     FGI_TRY(part_set_output(g, n, slot, out_set, stats, &ids));
+    FGI_TRY(timers_arm_part(g));
     return part_copy_ids(ids, out_ids, cap, out_n);
 }
 
@@ -4280,6 +4285,7 @@ fgi_status fgi_part_invalidate_all(fgi_graph* g, uint32_t* out_ids, uint64_t cap
     if (!g) return FGI_EINVAL;
     std::vector<uint32_t> ids;
     FGI_TRY(part_invalidate_all(g, stats, &ids));
+    FGI_TRY(timers_arm_part(g));
     return part_copy_ids(ids, out_ids, cap, out_n);
 }
 
@@ -4363,6 +4369,18 @@ fgi_status fgi_part_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* st
         g->view->pending.clear();
         g->view->deferred = true;
     }
+    // The rank's delay timers (timers.hip): the steps apply their moves themselves; the arm rule runs once behind
+    // the batch over all its cascades' records, on the states the batch left, on every way out as the view's.
+    struct TimerScope {
+        fgi_graph* g;
+        bool on;
+        fgi_status arm() {
+            if (!on) return FGI_OK;
+            on = false;
+            return timers_arm_part(g);
+        }
+        ~TimerScope() { (void)arm(); }
+    } tscope{g, n_casc != 0 && timers_on(g)};
     std::vector<uint32_t> ids;
     fgi_wave_stats ws{};
     for (uint32_t k = 0; k < n_steps; ++k) {
@@ -4389,6 +4407,7 @@ fgi_status fgi_part_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* st
         if (stats && sp.kind != FGI_STEP_ADD_USED) stats->waves += 1;
     }
     FGI_TRY(vscope.sync());
+    FGI_TRY(tscope.arm());
     if (stats) {
         stats->levels += ws.levels;
         stats->v_inv += ws.v_inv;

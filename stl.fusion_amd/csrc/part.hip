@@ -1644,7 +1644,7 @@ fgi_status fgi_part_local_invalidate(fgi_graph* const* gs, uint32_t P, uint32_t 
                 }
                 FGI_TRY(run_part_wave(g, n_roots, rd, id, stats ? stats + r : nullptr));
                 part_out_mark(g, kPoutWave);
-                return FGI_OK;
+                return timers_arm_part(g);   // the rank's delay timers of what the wave flagged (timers.hip)
             };
             part_out_mark(g, kPoutOther);   // until the rank's wave stands
             st[r] = wave();
@@ -1973,7 +1973,7 @@ fgi_status fgi_part_invalidate(fgi_graph* g, uint32_t n_roots, const uint32_t* r
     FGI_TRY(run_part_wave(g, n_roots, roots_dev, imm_dev, stats));
     part_out_mark(g, kPoutWave);
     if (out_n) *out_n = g->last_wave_n;
-    return FGI_OK;
+    return timers_arm_part(g);   // the rank's delay timers of what the wave flagged (timers.hip)
 }
 
 // What fgi_part_invalidate_host and fgi_part_invalidate_bits share: the roots checked on the host (every
@@ -1999,7 +1999,7 @@ static fgi_status part_wave_from_host(fgi_graph* g, const char* what, uint32_t n
     part_out_mark(g, kPoutOther);   // until the wave stands
     FGI_TRY(run_part_wave(g, n_roots, rd, id, stats));
     part_out_mark(g, kPoutWave);
-    return FGI_OK;
+    return timers_arm_part(g);
 }
 
 fgi_status fgi_part_invalidate_host(fgi_graph* g, uint32_t n_roots, const uint32_t* roots, const uint8_t* immediately,

@@ -21,12 +21,27 @@
 // default delay) plus the tombstones, and is brought up to that by the calls that change the bound, all of
 // which wait for the device anyway (tm_reserve).
 // Everything is allocated by fgi_timers_open; a graph that never opens timers launches nothing here.
+//
+// Per rank of a partition (C-ABI 0.12: fgi_part_timers_open, _set_delay, _run_due, _fired_detached,
+// fgi_part_local_timers_run_due, and the hook timers_arm_part): the table covers the rank's local handles, as
+// fgi_dump_states and the rank's state view address them. Handle h < n_local is the host's slot base + h, whose
+// node sits at engine index gc[base + h] - base when the partition has codes, else at h (fanout.hip's
+// k_sub_insert, view.hip's view_label); the handles [n_local, ext_slots) of a short last rank never hold a node;
+// a detached handle is its own engine index. A partition has no hub-first labels (K = 0, no s2l), so the move,
+// drop, set-delay and min kernels, which touch a node only under a detached handle, serve a rank as they are.
+//   k_tm_arm_part   k_tm_arm over a call's records in prec (the host's global slot in the high half, counted by
+//                   pcur[0] on the device), or over every handle of the rank.
+//   k_tm_due_part   k_tm_due with two fired lists: owned slots as global ids (the roots of the partitioned
+//                   wave, after the ranks' lists are gathered) and detached handles (reported, not cascaded).
+// A tick is a collective (fgi_part_timers_run_due): the verdicts, the counts and the sorted lists of all ranks
+// travel through part_allgather_words and part_allgatherv, then one partitioned wave runs from all the roots.
 #include "fgi_internal.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <unordered_map>
 
 namespace fgi {
@@ -59,6 +74,11 @@ struct Timers {
     uint64_t runs = 0;
     double last_ms = 0;
     hipEvent_t ev[2] = {nullptr, nullptr};
+    // a partition rank's (the fired list then has a third part, [2 fired_cap, 3 fired_cap): the detached handles)
+    bool part = false;
+    uint32_t* groots = nullptr;            // [groots_cap] every rank's fired slots, gathered in rank order
+    uint64_t groots_cap = 0;
+    std::vector<uint32_t> fdet;            // the last tick's fired detached handles, ascending (fgi_part_timers_fired_detached)
 };
 
 namespace {
@@ -67,7 +87,7 @@ constexpr int kTBlock = 256;
 constexpr uint32_t kCodeNever = 0xFFFFFFFFu;
 constexpr uint32_t kClaim = 0xFFFFFFFEu;   // ent[h] while a lane of the running launch works on h
 // device counters
-enum { kTTop = 0, kTArmed, kTFired, kTDropped, kTMoved, kTTomb, kTFail, kTNewTop, kTFiredN, kTCoded, kTMin, kTWords = 16 };
+enum { kTTop = 0, kTArmed, kTFired, kTDropped, kTMoved, kTTomb, kTFail, kTNewTop, kTFiredN, kTCoded, kTMin, kTFiredD, kTWords = 16 };
 
 // what every kernel reads a node and the table through
 struct TmTab {
@@ -85,12 +105,34 @@ struct TmTab {
     unsigned long long now, default_delay;
 };
 
+// How a handle finds its node: on a single device through the table's own K and s2l (TmOne), on a rank of a
+// partition through the rank's range and the slot -> code table (TmPart; the file comment).
+struct TmOne {};
+struct TmPart {
+    uint32_t base, n_local;
+    const uint32_t* gc;         // null: no partition codes
+};
+
 // the node word of boundary handle h, its visit bit folded in (fanout.hip's k_sub_insert reads it the same way)
-__device__ inline unsigned long long tm_word(const TmTab& a, uint32_t h) {
+__device__ inline unsigned long long tm_word(const TmTab& a, const TmOne&, uint32_t h) {
     uint32_t l = h + a.K;
     if (a.s2l && h < a.ext_slots) {
         const uint32_t hot = a.s2l[h];
         if (hot != FGI_NONE) l = hot;
+    }
+    unsigned long long w = a.node[l];
+    if (a.vis && ((a.vis[l >> 5] >> (l & 31)) & 1u)) w = visited_word(w);
+    return w;
+}
+// a rank's local handle h < n_handles; 0 (no node) for the handles of a short last rank past its slots
+__device__ inline unsigned long long tm_word(const TmTab& a, const TmPart& p, uint32_t h) {
+    uint32_t l = h;
+    if (h < a.ext_slots) {
+        if (h >= p.n_local) return 0ull;
+        if (p.gc) {
+            l = p.gc[p.base + h] - p.base;
+            if (l >= p.n_local) return 0ull;   // a code stays in its owner's range (k_sub_insert checks the same)
+        }
     }
     unsigned long long w = a.node[l];
     if (a.vis && ((a.vis[l >> 5] >> (l & 31)) & 1u)) w = visited_word(w);
@@ -106,12 +148,17 @@ __device__ inline unsigned long long tm_delay(const TmTab& a, uint32_t h) {
     return a.dtab[c - 1];
 }
 
+// what a fired handle is called in the wave's root list
+__device__ inline uint32_t tm_root(const TmOne&, uint32_t h) { return h; }
+__device__ inline uint32_t tm_root(const TmPart& p, uint32_t h) { return p.base + h; }   // an owned slot: the host's global id
+
 // The arm rule on candidate h of every lane for which cand holds. Called by whole wavefronts.
-__device__ inline void tm_arm(const TmTab& a, bool cand, uint32_t h, uint32_t lane) {
+template <class M>
+__device__ inline void tm_arm(const TmTab& a, const M& map, bool cand, uint32_t h, uint32_t lane) {
     bool fresh = false;
     unsigned long long v = 0, due = 0;
     if (cand && h < a.n_handles) {
-        const unsigned long long w = tm_word(a, h);
+        const unsigned long long w = tm_word(a, map, h);
         const unsigned long long d = tm_waiting(w) ? tm_delay(a, h) : 0ull;
         if (d != 0 && d != FGI_TIMER_NEVER) {
             v = w & kVMask;
@@ -168,17 +215,19 @@ __global__ __launch_bounds__(kTBlock) void k_tm_arm(TmTab a, const unsigned long
         const uint64_t i = base + lane;
         const bool cand = i < n;
         const uint32_t h = !cand ? 0u : rec ? (uint32_t)(rec[i] >> 32) : (uint32_t)i;
-        tm_arm(a, cand, h, lane);
+        tm_arm(a, TmOne{}, cand, h, lane);
     }
 }
 
 // The due pass over the pool [0, top) (top = min(ctr[kTTop], cap)): see the file comment. dst: the other copy.
-__global__ __launch_bounds__(kTBlock) void k_tm_due(TmTab a, TimerRec* dst, uint32_t* fired, uint64_t fired_cap) {
-    const unsigned long long t = a.ctr[kTTop];
-    const uint64_t top = t < a.cap ? t : a.cap;
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    for (uint64_t base = (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64; base < top; base += nwaves * 64) {
+// On a rank of a partition (M = TmPart) a fired owned slot goes to `fired` as the host's global slot id and a
+// fired detached handle to fired_det (counted by ctr[kTFiredD]), both of fired_cap entries. top, first,
+// nwaves, lane: the pool's top, the wavefront's first run of 64 records, the launch's wavefronts and the lane.
+template <class M>
+__device__ __forceinline__ void tm_due(const TmTab& a, const M& m, TimerRec* dst, uint32_t* fired, uint32_t* fired_det,
+                                       uint64_t fired_cap, uint64_t top, uint64_t first, uint64_t nwaves, uint32_t lane) {
+    constexpr bool kPart = std::is_same<M, TmPart>::value;
+    for (uint64_t base = first; base < top; base += nwaves * 64) {
         const uint64_t i = base + lane;
         TimerRec r{0, 0, FGI_NONE, 0};
         if (i < top) r = a.rec[i];
@@ -187,22 +236,34 @@ __global__ __launch_bounds__(kTBlock) void k_tm_due(TmTab a, TimerRec* dst, uint
         const bool keep = live && !is_due;
         bool fire = false;
         if (is_due) {
-            const unsigned long long w = tm_word(a, r.handle);
+            const unsigned long long w = tm_word(a, m, r.handle);
             fire = tm_waiting(w) && (w & kVMask) == r.version;
             a.ent[r.handle] = FGI_NONE;
         }
-        const unsigned long long mk = __ballot(keep), mf = __ballot(fire), md = __ballot(is_due && !fire);
-        unsigned long long bk = 0, bf = 0;
+        bool fire_det = false;   // a rank's detached handle: no partitioned cascade reaches its node
+        if constexpr (kPart) {
+            fire_det = fire && r.handle >= a.ext_slots;
+            fire = fire && !fire_det;
+        }
+        const unsigned long long mk = __ballot(keep), mf = __ballot(fire), md = __ballot(is_due && !fire && !fire_det);
+        unsigned long long mt = 0;
+        if constexpr (kPart) mt = __ballot(fire_det);
+        unsigned long long bk = 0, bf = 0, bt = 0;
         if (lane == 0) {
             if (mk) bk = atomicAdd(a.ctr + kTNewTop, (unsigned long long)__popcll(mk));
             if (mf) {
                 bf = atomicAdd(a.ctr + kTFiredN, (unsigned long long)__popcll(mf));
                 atomicAdd(a.ctr + kTFired, (unsigned long long)__popcll(mf));
             }
+            if (mt) {
+                bt = atomicAdd(a.ctr + kTFiredD, (unsigned long long)__popcll(mt));
+                atomicAdd(a.ctr + kTFired, (unsigned long long)__popcll(mt));
+            }
             if (md) atomicAdd(a.ctr + kTDropped, (unsigned long long)__popcll(md));
         }
         bk = __shfl(bk, 0);
         bf = __shfl(bf, 0);
+        if constexpr (kPart) bt = __shfl(bt, 0);
         const unsigned long long below = (1ull << lane) - 1;
         if (keep) {
             const unsigned long long idx = bk + __popcll(mk & below);   // < top <= cap
@@ -211,10 +272,23 @@ __global__ __launch_bounds__(kTBlock) void k_tm_due(TmTab a, TimerRec* dst, uint
         }
         if (fire) {
             const unsigned long long idx = bf + __popcll(mf & below);
-            if (idx < fired_cap) fired[idx] = r.handle;
+            if (idx < fired_cap) fired[idx] = tm_root(m, r.handle);
+            else atomicAdd(a.ctr + kTFail, 1ull);
+        }
+        if (fire_det) {
+            const unsigned long long idx = bt + __popcll(mt & below);
+            if (idx < fired_cap) fired_det[idx] = r.handle;
             else atomicAdd(a.ctr + kTFail, 1ull);
         }
     }
+}
+
+__global__ __launch_bounds__(kTBlock) void k_tm_due(TmTab a, TimerRec* dst, uint32_t* fired, uint64_t fired_cap) {
+    const unsigned long long t = a.ctr[kTTop];
+    const uint64_t top = t < a.cap ? t : a.cap;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    tm_due(a, TmOne{}, dst, fired, nullptr, fired_cap, top, (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64, nwaves, lane);
 }
 
 // behind the due pass: the compacted copy is the pool
@@ -237,7 +311,7 @@ __global__ __launch_bounds__(kTBlock) void k_tm_move(TmTab a, uint32_t n, const 
         d = to[i];
         if (d != FGI_NONE && f != d && f < a.n_handles && d < a.n_handles) {
             a.dly[d] = a.dly[f];
-            const unsigned long long w = tm_word(a, d);
+            const unsigned long long w = tm_word(a, TmOne{}, d);
             const uint32_t e = a.ent[f];
             if (e != FGI_NONE && e < a.cap && (w & kVMask) != 0 && a.rec[e].version == (w & kVMask)) {
                 const uint32_t old = a.ent[d];   // a detached handle handed out anew has none: released ones drop theirs
@@ -255,7 +329,7 @@ __global__ __launch_bounds__(kTBlock) void k_tm_move(TmTab a, uint32_t n, const 
             }
         }
     }
-    tm_arm(a, arm, d, lane);
+    tm_arm(a, TmOne{}, arm, d, lane);
 }
 
 __global__ __launch_bounds__(kTBlock) void k_tm_drop(TmTab a, uint32_t n, const uint32_t* handles) {
@@ -301,6 +375,39 @@ __global__ __launch_bounds__(kTBlock) void k_tm_min(const TimerRec* rec, uint64_
     if ((threadIdx.x & 63) == 0 && m != FGI_TIMER_NONE) atomicMin(ctr + kTMin, m);
 }
 
+// ---- a rank of a partition: behind the single-device kernels, which keep their places -------------------------
+// k_tm_arm for a rank. Candidates: the call's flagged records (rec != null: the host's global slot << 32 | flags;
+// a slot outside [base, base + n_local) is not the rank's and is skipped), else every local handle below n_max.
+__global__ __launch_bounds__(kTBlock) void k_tm_arm_part(TmTab a, TmPart p, const unsigned long long* rec, uint64_t n_max,
+                                                         const unsigned long long* n_dev) {
+    uint64_t n = n_max;
+    if (n_dev) {
+        const unsigned long long c = *n_dev;
+        if (c < n) n = c;
+    }
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t base = (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64; base < n; base += nwaves * 64) {
+        const uint64_t i = base + lane;
+        bool cand = i < n;
+        uint32_t h = 0;
+        if (cand) {
+            h = rec ? (uint32_t)(rec[i] >> 32) - p.base : (uint32_t)i;   // (a slot below base wraps past n_local)
+            if (rec) cand = h < p.n_local;
+        }
+        tm_arm(a, p, cand, h, lane);
+    }
+}
+
+__global__ __launch_bounds__(kTBlock) void k_tm_due_part(TmTab a, TmPart p, TimerRec* dst, uint32_t* fired, uint32_t* fired_det,
+                                                         uint64_t fired_cap) {
+    const unsigned long long t = a.ctr[kTTop];
+    const uint64_t top = t < a.cap ? t : a.cap;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    tm_due(a, p, dst, fired, fired_det, fired_cap, top, (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64, nwaves, lane);
+}
+
 inline uint32_t tgrid(uint64_t n) { return (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, (n + kTBlock - 1) / kTBlock)); }
 
 TmTab tm_tab(const fgi_graph* g) {
@@ -322,6 +429,25 @@ TmTab tm_tab(const fgi_graph* g) {
     a.now = t->now;
     a.default_delay = t->default_delay;
     return a;
+}
+
+// a rank's handle map (the file comment)
+TmPart tm_part(fgi_graph* g) {
+    PartView pv{};
+    part_view(g, &pv);
+    return TmPart{pv.base, pv.n_local, g->lbl_perm ? (const uint32_t*)g->pg_gc : nullptr};
+}
+
+// the arm rule over every handle the graph holds (fgi_timers_open, fgi_part_timers_open on a populated graph)
+void tm_arm_all(fgi_graph* g) {
+    const Timers* t = g->tim;
+    const uint64_t n = g->ext_handles;
+    if (t->part)
+        hipLaunchKernelGGL(k_tm_arm_part, dim3(tgrid(n)), dim3(kTBlock), 0, g->stream, tm_tab(g), tm_part(g),
+                           (const unsigned long long*)nullptr, n, (const unsigned long long*)nullptr);
+    else
+        hipLaunchKernelGGL(k_tm_arm, dim3(tgrid(n)), dim3(kTBlock), 0, g->stream, tm_tab(g), (const unsigned long long*)nullptr, n,
+                           (const unsigned long long*)nullptr);
 }
 
 // the counters back on the host (one wait). A pool that overflowed lost entries: the host's bound was wrong.
@@ -350,6 +476,11 @@ inline uint64_t tm_stored(const Timers* t) { return tm_top(t) - std::min<uint64_
 // fgi_timers_set_delay, whose last wait knows |P| <= stored + coded slots + detached handles; everything else
 // (waves, moves, releases, due passes, fgi_restore) only moves entries within P or takes members out.
 // `holders` is the largest such value seen, so it is never lowered between two due passes.
+// On a rank of a partition every term is the rank's own: ext_handles and ext_slots are its local handles and
+// slots, n_detached its detached handles, and ctr[kTCoded] counts only slots the rank owns (fgi_part_timers_
+// set_delay uploads no other), so the argument holds per rank with no word from another rank. The tick's wave
+// arms behind a due pass that only took entries out, and the arm behind a batch runs after the batch's moves,
+// each of which ended in tm_reserve.
 // Grows by copying; the caller's next kernel arguments are built afterwards.
 fgi_status tm_reserve(fgi_graph* g) {
     Timers* t = g->tim;
@@ -401,6 +532,14 @@ fgi_status timers_arm_records(fgi_graph* g, const unsigned long long* rec, uint6
     return FGI_OK;
 }
 
+fgi_status timers_arm_part(fgi_graph* g) {
+    if (!timers_on(g) || !g->tim->part || !g->flag_gate || !g->prec || !g->pcur || g->pflg_runs.empty()) return FGI_OK;
+    hipLaunchKernelGGL(k_tm_arm_part, dim3(tgrid(g->prec_cap)), dim3(kTBlock), 0, g->stream, tm_tab(g), tm_part(g),
+                       (const unsigned long long*)g->prec, g->prec_cap, (const unsigned long long*)g->pcur);
+    FGI_HIP(g, hipGetLastError());
+    return FGI_OK;
+}
+
 fgi_status timers_move(fgi_graph* g, uint32_t n, const uint32_t* from, const uint32_t* to) {
     if (!timers_on(g) || !n) return FGI_OK;
     Timers* t = g->tim;
@@ -440,6 +579,7 @@ fgi_status timers_restore(fgi_graph* g) {
     t->ctr_h[kTDropped] += tm_stored(t);   // every entry is dropped
     t->ctr_h[kTTop] = t->ctr_h[kTTomb] = t->ctr_h[kTFail] = 0;
     t->tomb_ub = 0;
+    t->fdet.clear();
     FGI_HIP(g, hipMemcpyAsync(t->ctr, t->ctr_h, kTWords * 8, hipMemcpyHostToDevice, s));
     FGI_HIP(g, hipMemsetAsync(t->ent, 0xFF, (size_t)g->ext_handles * 4, s));
     FGI_HIP(g, hipStreamSynchronize(s));
@@ -449,7 +589,7 @@ fgi_status timers_restore(fgi_graph* g) {
 void timers_destroy(fgi_graph* g) {
     Timers* t = g->tim;
     if (!t) return;
-    void* dev[] = {t->dly, t->ent, t->rec[0], t->rec[1], t->dtab, t->ctr, t->fired, t->imm, t->up};
+    void* dev[] = {t->dly, t->ent, t->rec[0], t->rec[1], t->dtab, t->ctr, t->fired, t->imm, t->up, t->groots};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     if (t->ctr_h) (void)hipHostFree(t->ctr_h);
@@ -465,16 +605,21 @@ using namespace fgi;
 
 extern "C" {
 
-fgi_status fgi_timers_open(fgi_graph* g, const fgi_timers_config* cfg) {
+// fgi_timers_open and fgi_part_timers_open (part: a rank of a partition)
+static fgi_status tm_open(fgi_graph* g, const fgi_timers_config* cfg, bool part, const char* what) {
     if (!g || !cfg || cfg->struct_size < sizeof(fgi_timers_config)) return FGI_EINVAL;
-    if (g->failed) return set_err(g, FGI_ESTATE, "fgi_timers_open: the graph is poisoned; fgi_restore or fgi_destroy");
-    if (g->part || g->world > 1)
-        return set_err(g, FGI_ENOTSUP, "fgi_timers_open: the delay timers serve a single device, not a partition");
-    if (g->tim) return set_err(g, FGI_ESTATE, "fgi_timers_open: the graph's timers are open");
+    if (g->failed) return set_err(g, FGI_ESTATE, "%s: the graph is poisoned; fgi_restore or fgi_destroy", what);
+    if (!part && (g->part || g->world > 1))
+        return set_err(g, FGI_ENOTSUP, "fgi_timers_open: the delay timers serve a single device, not a partition "
+                                       "(fgi_part_timers_open)");
+    if (part && !g->part)
+        return set_err(g, FGI_ENOTSUP, "fgi_part_timers_open: not a partitioned graph (fgi_timers_open)");
+    if (g->tim) return set_err(g, FGI_ESTATE, "%s: the graph's timers are open", what);
     hipSetDevice(g->device);
     if (g->aw[0].busy || g->aw[1].busy) FGI_TRY(drain_async(g));
     Timers* t = new Timers();
     g->tim = t;
+    t->part = part;
     t->now = cfg->now;
     t->default_delay = cfg->default_delay;
     hipStream_t s = g->stream;
@@ -494,13 +639,14 @@ fgi_status fgi_timers_open(fgi_graph* g, const fgi_timers_config* cfg) {
     if (st == FGI_OK) st = flush_vis(g);
     // a populated graph: every node already Consistent with DelayStarted, in one pass over the handles
     if (st == FGI_OK && g->nodes_written) {
-        hipLaunchKernelGGL(k_tm_arm, dim3(tgrid(g->ext_handles)), dim3(kTBlock), 0, s, tm_tab(g), (const unsigned long long*)nullptr,
-                           (uint64_t)g->ext_handles, (const unsigned long long*)nullptr);
-        st = tm_sync(g, "fgi_timers_open");
+        tm_arm_all(g);
+        st = tm_sync(g, what);
     }
     if (st != FGI_OK) timers_destroy(g);
     return st;
 }
+
+fgi_status fgi_timers_open(fgi_graph* g, const fgi_timers_config* cfg) { return tm_open(g, cfg, false, "fgi_timers_open"); }
 
 fgi_status fgi_timers_close(fgi_graph* g) {
     if (!g) return FGI_EINVAL;
@@ -510,20 +656,9 @@ fgi_status fgi_timers_close(fgi_graph* g) {
     return FGI_OK;
 }
 
-fgi_status fgi_timers_set_delay(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint64_t* delay) {
-    if (!g || (n && (!handle || !delay))) return FGI_EINVAL;
-    FGI_TRY(tm_usable(g, "fgi_timers_set_delay"));
+// handle[i] (distinct, in range) takes delay[i]: what fgi_timers_set_delay and fgi_part_timers_set_delay share
+static fgi_status tm_set_delay(fgi_graph* g, const char* what, uint32_t n, const uint32_t* handle, const uint64_t* delay) {
     Timers* t = g->tim;
-    for (uint32_t i = 0; i < n; ++i)
-        if (handle[i] >= g->ext_handles)
-            return set_err(g, FGI_EINVAL, "fgi_timers_set_delay: handle %u out of range at %u", handle[i], i);
-    if (!n) return FGI_OK;
-    {
-        std::vector<uint32_t> sorted(handle, handle + n);
-        std::sort(sorted.begin(), sorted.end());
-        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
-        if (dup != sorted.end()) return set_err(g, FGI_EINVAL, "fgi_timers_set_delay: handle %u listed twice", *dup);
-    }
     std::vector<uint32_t> code(n);
     const size_t known = t->dtab_h.size();
     for (uint32_t i = 0; i < n; ++i) {
@@ -534,7 +669,7 @@ fgi_status fgi_timers_set_delay(fgi_graph* g, uint32_t n, const uint32_t* handle
         }
         auto it = t->dcode.find(d);
         if (it == t->dcode.end()) {
-            if (t->dtab_h.size() + 2 >= kClaim) return set_err(g, FGI_ENOMEM, "fgi_timers_set_delay: too many distinct delays");
+            if (t->dtab_h.size() + 2 >= kClaim) return set_err(g, FGI_ENOMEM, "%s: too many distinct delays", what);
             t->dtab_h.push_back(d);
             it = t->dcode.emplace(d, (uint32_t)t->dtab_h.size()).first;
         }
@@ -551,10 +686,28 @@ fgi_status fgi_timers_set_delay(fgi_graph* g, uint32_t n, const uint32_t* handle
     FGI_HIP(g, hipMemcpyAsync(t->up + n, code.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_tm_set_delay, dim3((n + kTBlock - 1) / kTBlock), dim3(kTBlock), 0, s, t->dly, n, (const uint32_t*)t->up,
                        (const uint32_t*)(t->up + n), g->ext_slots, t->ctr);
-    FGI_TRY(tm_sync(g, "fgi_timers_set_delay"));
+    FGI_TRY(tm_sync(g, what));
     // the entries stored now (a slot that lost its code may hold one), the coded slots, the detached handles
     t->holders = std::max<uint64_t>(t->holders, tm_stored(t) + t->ctr_h[kTCoded] + g->n_detached);
     return tm_reserve(g);
+}
+
+fgi_status fgi_timers_set_delay(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint64_t* delay) {
+    if (!g || (n && (!handle || !delay))) return FGI_EINVAL;
+    if (g->part)
+        return set_err(g, FGI_ENOTSUP, "fgi_timers_set_delay: a partition's slots are global ids (fgi_part_timers_set_delay)");
+    FGI_TRY(tm_usable(g, "fgi_timers_set_delay"));
+    for (uint32_t i = 0; i < n; ++i)
+        if (handle[i] >= g->ext_handles)
+            return set_err(g, FGI_EINVAL, "fgi_timers_set_delay: handle %u out of range at %u", handle[i], i);
+    if (!n) return FGI_OK;
+    {
+        std::vector<uint32_t> sorted(handle, handle + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) return set_err(g, FGI_EINVAL, "fgi_timers_set_delay: handle %u listed twice", *dup);
+    }
+    return tm_set_delay(g, "fgi_timers_set_delay", n, handle, delay);
 }
 
 fgi_status fgi_timers_set_now(fgi_graph* g, uint64_t now) {
@@ -567,18 +720,13 @@ fgi_status fgi_timers_set_now(fgi_graph* g, uint64_t now) {
     return FGI_OK;
 }
 
-fgi_status fgi_timers_run_due(fgi_graph* g, uint64_t now, uint32_t* out_ids, uint64_t cap, uint64_t* out_n, uint64_t* out_fired,
-                              fgi_wave_stats* stats) {
-    if (!g) return FGI_EINVAL;
-    if (out_n) *out_n = 0;
-    if (out_fired) *out_fired = 0;
-    FGI_TRY(tm_usable(g, "fgi_timers_run_due"));
+// The due pass at the clock t->now and its wait; the fired list sorted ascending at t->fired + t->fired_cap
+// (*n_fired entries: handles, or on a rank the host's global slot ids). On a rank the fired detached handles,
+// ascending, are left in t->fdet. A pool without entries launches nothing.
+static fgi_status tm_due_pass(fgi_graph* g, const char* what, uint64_t* n_fired) {
     Timers* t = g->tim;
-    if (now < t->now)
-        return set_err(g, FGI_EINVAL, "fgi_timers_run_due: %llu is before the clock (%llu)", (unsigned long long)now,
-                       (unsigned long long)t->now);
-    FGI_TRY(tm_sync(g, "fgi_timers_run_due"));
-    t->now = now;
+    *n_fired = 0;
+    t->fdet.clear();
     const uint64_t top = tm_top(t);
     if (!top) return FGI_OK;
     hipStream_t s = g->stream;
@@ -586,37 +734,79 @@ fgi_status fgi_timers_run_due(fgi_graph* g, uint64_t now, uint32_t* out_ids, uin
     if (t->fired_cap < top) {
         dfree(t->fired);
         t->fired_cap = 0;
-        FGI_TRY(dmalloc(g, &t->fired, 2 * t->cap));
+        FGI_TRY(dmalloc(g, &t->fired, (t->part ? 3 : 2) * t->cap));
         t->fired_cap = t->cap;
     }
     FGI_HIP(g, hipMemsetAsync(t->ctr + kTNewTop, 0, 2 * 8, s));   // kTNewTop, kTFiredN
+    if (t->part) FGI_HIP(g, hipMemsetAsync(t->ctr + kTFiredD, 0, 8, s));
     FGI_HIP(g, hipEventRecord(t->ev[0], s));
-    hipLaunchKernelGGL(k_tm_due, dim3(tgrid(top)), dim3(kTBlock), 0, s, tm_tab(g), t->rec[1], t->fired, t->fired_cap);
+    if (t->part)
+        hipLaunchKernelGGL(k_tm_due_part, dim3(tgrid(top)), dim3(kTBlock), 0, s, tm_tab(g), tm_part(g), t->rec[1], t->fired,
+                           t->fired + 2 * t->fired_cap, t->fired_cap);
+    else
+        hipLaunchKernelGGL(k_tm_due, dim3(tgrid(top)), dim3(kTBlock), 0, s, tm_tab(g), t->rec[1], t->fired, t->fired_cap);
     hipLaunchKernelGGL(k_tm_commit, dim3(1), dim3(64), 0, s, t->ctr);
     FGI_HIP(g, hipEventRecord(t->ev[1], s));
     std::swap(t->rec[0], t->rec[1]);
     t->tomb_ub = 0;
-    FGI_TRY(tm_sync(g, "fgi_timers_run_due"));
+    FGI_TRY(tm_sync(g, what));
     float ms = 0;
     t->last_ms = hipEventElapsedTime(&ms, t->ev[0], t->ev[1]) == hipSuccess ? ms : 0.0;
-    const uint64_t n_fired = std::min<uint64_t>(t->ctr_h[kTFiredN], t->fired_cap);
-    if (out_fired) *out_fired = n_fired;
-    if (!n_fired) return FGI_OK;
-    if (n_fired > 0xFFFFFFFFull) return set_err(g, FGI_ECAPACITY, "fgi_timers_run_due: %llu roots", (unsigned long long)n_fired);
-    // the fired handles ascending: the roots of one wave, every one `immediately`
-    uint32_t* roots = t->fired + t->fired_cap;
-    {
+    const uint64_t n = std::min<uint64_t>(t->ctr_h[kTFiredN], t->fired_cap);
+    if (n > 0xFFFFFFFFull) return set_err(g, FGI_ECAPACITY, "%s: %llu roots", what, (unsigned long long)n);
+    if (n) {   // ascending: the roots of one wave
         Tmp tt;
         size_t tb = 0;
-        FGI_HIP(g, rocprim::radix_sort_keys(nullptr, tb, t->fired, roots, (size_t)n_fired, 0, 32, s));
+        uint32_t* roots = t->fired + t->fired_cap;
+        FGI_HIP(g, rocprim::radix_sort_keys(nullptr, tb, t->fired, roots, (size_t)n, 0, 32, s));
         void* tmp;
         FGI_TRY(tmalloc(g, tt, reinterpret_cast<char**>(&tmp), tb));
-        FGI_HIP(g, rocprim::radix_sort_keys(tmp, tb, t->fired, roots, (size_t)n_fired, 0, 32, s));
+        FGI_HIP(g, rocprim::radix_sort_keys(tmp, tb, t->fired, roots, (size_t)n, 0, 32, s));
     }
-    if (t->imm_cap < n_fired) {
-        FGI_TRY(grow(g, &t->imm, &t->imm_cap, std::max<uint64_t>(n_fired, 4096), "the fired roots' flags"));
-        FGI_HIP(g, hipMemsetAsync(t->imm, 1, t->imm_cap, s));
+    if (t->part) {   // few: a displaced node whose timer ran out before its host released it
+        const uint64_t nd = std::min<uint64_t>(t->ctr_h[kTFiredD], t->fired_cap);
+        t->fdet.resize(nd);
+        if (nd) {
+            FGI_HIP(g, hipMemcpyAsync(t->fdet.data(), t->fired + 2 * t->fired_cap, nd * 4, hipMemcpyDeviceToHost, s));
+            FGI_HIP(g, hipStreamSynchronize(s));
+            std::sort(t->fdet.begin(), t->fdet.end());
+        }
     }
+    *n_fired = n;
+    return FGI_OK;
+}
+
+// the fired roots' `immediately` flags: n ones
+static fgi_status tm_ones(fgi_graph* g, uint64_t n) {
+    Timers* t = g->tim;
+    if (t->imm_cap >= n) return FGI_OK;
+    FGI_TRY(grow(g, &t->imm, &t->imm_cap, std::max<uint64_t>(n, 4096), "the fired roots' flags"));
+    FGI_HIP(g, hipMemsetAsync(t->imm, 1, t->imm_cap, g->stream));
+    return FGI_OK;
+}
+
+fgi_status fgi_timers_run_due(fgi_graph* g, uint64_t now, uint32_t* out_ids, uint64_t cap, uint64_t* out_n, uint64_t* out_fired,
+                              fgi_wave_stats* stats) {
+    if (!g) return FGI_EINVAL;
+    if (out_n) *out_n = 0;
+    if (out_fired) *out_fired = 0;
+    if (g->part)   // never the single-device wave on a rank
+        return set_err(g, FGI_ENOTSUP, "fgi_timers_run_due: a partition's tick is a collective (fgi_part_timers_run_due)");
+    FGI_TRY(tm_usable(g, "fgi_timers_run_due"));
+    Timers* t = g->tim;
+    if (now < t->now)
+        return set_err(g, FGI_EINVAL, "fgi_timers_run_due: %llu is before the clock (%llu)", (unsigned long long)now,
+                       (unsigned long long)t->now);
+    FGI_TRY(tm_sync(g, "fgi_timers_run_due"));
+    t->now = now;
+    uint64_t n_fired = 0;
+    FGI_TRY(tm_due_pass(g, "fgi_timers_run_due", &n_fired));
+    if (out_fired) *out_fired = n_fired;
+    if (!n_fired) return FGI_OK;
+    hipStream_t s = g->stream;
+    // the fired handles ascending: the roots of one wave, every one `immediately`
+    uint32_t* roots = t->fired + t->fired_cap;
+    FGI_TRY(tm_ones(g, n_fired));
     ++t->runs;
     FGI_TRY(run_wave(g, (uint32_t)n_fired, roots, t->imm, stats, true, out_ids ? WaveOut::kIds : WaveOut::kCount));
     const uint64_t n = g->last_wave_n;
@@ -688,6 +878,126 @@ fgi_status fgi_timers_list(fgi_graph* g, uint32_t* handle, uint64_t* version, ui
         if (due) due[i] = recs[i].due;
     }
     return FGI_OK;
+}
+
+// ---- per rank of a partition (C-ABI 0.12) ------------------------------------------------------------------
+
+fgi_status fgi_part_timers_open(fgi_graph* g, const fgi_timers_config* cfg) { return tm_open(g, cfg, true, "fgi_part_timers_open"); }
+
+fgi_status fgi_part_timers_set_delay(fgi_graph* g, uint32_t n, const uint32_t* slot, const uint64_t* delay) {
+    if (!g || (n && (!slot || !delay))) return FGI_EINVAL;
+    PartView pv{};
+    if (!g->part || !part_view(g, &pv))
+        return set_err(g, FGI_ENOTSUP, "fgi_part_timers_set_delay: not a partitioned graph (fgi_timers_set_delay)");
+    FGI_TRY(tm_usable(g, "fgi_part_timers_set_delay"));
+    for (uint32_t i = 0; i < n; ++i)
+        if (slot[i] >= pv.n_global)
+            return set_err(g, FGI_EINVAL, "fgi_part_timers_set_delay: slot %u of %u at %u", slot[i], pv.n_global, i);
+    if (!n) return FGI_OK;
+    {
+        std::vector<uint32_t> sorted(slot, slot + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) return set_err(g, FGI_EINVAL, "fgi_part_timers_set_delay: slot %u listed twice", *dup);
+    }
+    // the rank's share, as its local handles (a slot below base wraps past n_local)
+    std::vector<uint32_t> h;
+    std::vector<uint64_t> d;
+    for (uint32_t i = 0; i < n; ++i)
+        if (slot[i] - pv.base < pv.n_local) {
+            h.push_back(slot[i] - pv.base);
+            d.push_back(delay[i]);
+        }
+    if (h.empty()) return FGI_OK;
+    return tm_set_delay(g, "fgi_part_timers_set_delay", (uint32_t)h.size(), h.data(), d.data());
+}
+
+fgi_status fgi_part_timers_run_due(fgi_graph* g, uint64_t now, uint32_t* out_ids, uint64_t cap, uint64_t* out_n,
+                                   uint64_t* out_fired, uint64_t* out_fired_detached, fgi_wave_stats* stats) {
+    const char* const what = "fgi_part_timers_run_due";
+    if (!g) return FGI_EINVAL;
+    if (out_n) *out_n = 0;
+    if (out_fired) *out_fired = 0;
+    if (out_fired_detached) *out_fired_detached = 0;
+    PartView pv{};
+    if (!g->part || !part_view(g, &pv)) return set_err(g, FGI_ENOTSUP, "%s: not a partitioned graph (fgi_timers_run_due)", what);
+    hipSetDevice(g->device);
+    Timers* t = g->tim;
+    // Agreement first: every rank's verdict and its `now` travel with the call's first collective, so a tick
+    // that any rank refuses removes no entry anywhere and every rank returns the same status.
+    enum : uint64_t { kOk = 0, kClosed, kPoisoned, kClock };
+    const uint64_t mine[2] = {g->failed ? kPoisoned : !t ? kClosed : now < t->now ? kClock : kOk, now};
+    uint64_t all[8 * 2];
+    FGI_TRY(part_allgather_words(g, mine, 2, all));
+    for (uint32_t q = 0; q < pv.world; ++q)
+        if (all[2 * q] == kClosed || all[2 * q] == kPoisoned)
+            return set_err(g, FGI_ESTATE, "%s: rank %u %s", what, q,
+                           all[2 * q] == kClosed ? "has not opened its timers (fgi_part_timers_open)"
+                                                 : "is poisoned; fgi_restore or fgi_destroy");
+    for (uint32_t q = 0; q < pv.world; ++q) {
+        if (all[2 * q] == kClock)
+            return set_err(g, FGI_EINVAL, "%s: %llu is before the clock of rank %u", what, (unsigned long long)now, q);
+        if (all[2 * q + 1] != all[1])
+            return set_err(g, FGI_EINVAL, "%s: rank %u ticks at %llu, rank 0 at %llu", what, q, (unsigned long long)all[2 * q + 1],
+                           (unsigned long long)all[1]);
+    }
+    // the due pass on the rank's own pool; its outcome and the count of its roots travel together, so a rank
+    // whose pass failed takes every rank out of the call before the lists move
+    uint64_t n_mine = 0;
+    auto pass = [&]() -> fgi_status {
+        if (g->aw[0].busy || g->aw[1].busy) FGI_TRY(drain_async(g));
+        FGI_TRY(tm_sync(g, what));
+        t->now = now;
+        return tm_due_pass(g, what, &n_mine);
+    };
+    const fgi_status ps = pass();
+    const uint64_t cnt[2] = {(uint64_t)ps, n_mine};
+    FGI_TRY(part_allgather_words(g, cnt, 2, all));
+    if (ps != FGI_OK) return ps;
+    uint64_t bytes[8], total = 0;
+    for (uint32_t q = 0; q < pv.world; ++q) {
+        if (all[2 * q] != FGI_OK) return set_err(g, FGI_ESTATE, "%s: the due pass of rank %u failed", what, q);
+        bytes[q] = all[2 * q + 1] * 4;
+        total += all[2 * q + 1];
+    }
+    const uint64_t n_det = t->fdet.size();
+    if (out_fired) *out_fired = n_mine + n_det;
+    if (out_fired_detached) *out_fired_detached = n_det;
+    if (!total) return FGI_OK;   // no wave: every rank's last-wave results stay
+    if (total > pv.n_global) return set_err(g, FGI_EDEVICE, "%s: %llu roots of %u slots", what, (unsigned long long)total, pv.n_global);
+    // Ranks own contiguous ranges of the host's numbering, so the ranks' ascending lists in rank order are the
+    // ascending global root list, the same on every rank
+    FGI_TRY(grow(g, &t->groots, &t->groots_cap, std::max<uint64_t>(total, 4096), "the gathered timer roots"));
+    FGI_TRY(tm_ones(g, total));
+    FGI_TRY(part_allgatherv(g, t->fired + t->fired_cap, bytes, t->groots));
+    ++t->runs;
+    // one partitioned wave, every root `immediately`: mapped to codes, marked, driven and armed (at `now`) as
+    // fgi_part_invalidate's
+    FGI_TRY(fgi_part_invalidate(g, (uint32_t)total, t->groots, t->imm, nullptr, stats));
+    return fgi_part_last_wave_ids(g, out_ids, cap, out_n);   // a short cap: FGI_ECAPACITY, the wave has run
+}
+
+fgi_status fgi_part_timers_fired_detached(fgi_graph* g, uint32_t* out_handles, uint64_t cap, uint64_t* out_n) {
+    if (!g) return FGI_EINVAL;
+    if (out_n) *out_n = 0;
+    if (!g->part) return set_err(g, FGI_ENOTSUP, "fgi_part_timers_fired_detached: not a partitioned graph");
+    FGI_TRY(tm_usable(g, "fgi_part_timers_fired_detached"));
+    const std::vector<uint32_t>& f = g->tim->fdet;
+    if (out_n) *out_n = f.size();
+    if (!out_handles) return FGI_OK;
+    if (f.size() > cap)
+        return set_err(g, FGI_ECAPACITY, "fgi_part_timers_fired_detached: %llu handles, the buffer holds %llu",
+                       (unsigned long long)f.size(), (unsigned long long)cap);
+    if (!f.empty()) memcpy(out_handles, f.data(), f.size() * 4);
+    return FGI_OK;
+}
+
+fgi_status fgi_part_local_timers_run_due(fgi_graph* const* gs, uint32_t p, uint64_t now, uint64_t* out_fired,
+                                         uint64_t* out_fired_detached, fgi_wave_stats* stats) {
+    return part_local_run(gs, p, [&](uint32_t r) {
+        return fgi_part_timers_run_due(gs[r], now, nullptr, 0, nullptr, out_fired ? out_fired + r : nullptr,
+                                       out_fired_detached ? out_fired_detached + r : nullptr, stats ? stats + r : nullptr);
+    });
 }
 
 }  // extern "C"

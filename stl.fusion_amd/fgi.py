@@ -284,6 +284,11 @@ SIGNATURES = {
     "fgi_timers_next_due": [_G, _u64p, _u64p],
     "fgi_timers_stats_get": [_G, C.POINTER(TimerStats)],
     "fgi_timers_list": [_G, _u32p, _u64p, _u64p, C.c_uint64, _u64p],
+    "fgi_part_timers_open": [_G, C.POINTER(TimersConfig)],
+    "fgi_part_timers_set_delay": [_G, C.c_uint32, _u32p, _u64p],
+    "fgi_part_timers_run_due": [_G, C.c_uint64, _u32p, C.c_uint64, _u64p, _u64p, _u64p, C.POINTER(WaveStats)],
+    "fgi_part_timers_fired_detached": [_G, _u32p, C.c_uint64, _u64p],
+    "fgi_part_local_timers_run_due": [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint64, _u64p, _u64p, C.POINTER(WaveStats)],
 }
 
 _lib = None
@@ -762,6 +767,39 @@ class Graph:
                                              len(h), C.byref(n)), "timers_list")
         return h, v, d
 
+    # ---- the same per rank of a partition (C-ABI 0.12); close, set_now, next_due, stats and list above serve a rank ----
+    def part_timers_open(self, default_delay: int = 0, now: int = 0):
+        """fgi_part_timers_open (rank-local): this rank keeps the timers of its own local handles from here on."""
+        cfg = TimersConfig(C.sizeof(TimersConfig), 0, default_delay, now)
+        self._check(self.lib.fgi_part_timers_open(self.h, C.byref(cfg)), "part_timers_open")
+
+    def part_timers_set_delay(self, slots, delays):
+        """fgi_part_timers_set_delay (rank-local): global slots; those this rank does not own are skipped."""
+        s, d = _u32(slots), _u64(delays)
+        if len(s) != len(d):
+            raise ValueError("part_timers_set_delay: slots and delays differ in length")
+        self._check(self.lib.fgi_part_timers_set_delay(self.h, len(s), _ptr(s, C.c_uint32), _ptr(d, C.c_uint64)),
+                    "part_timers_set_delay")
+
+    def part_timers_run_due(self, now: int, stats: Optional[WaveStats] = None) -> Tuple[np.ndarray, int, int]:
+        """fgi_part_timers_run_due (collective: every rank, the same `now`): (this rank's ids of the fired timers'
+        wave, ascending global slots; this rank's entries fired; those of them on detached handles)."""
+        ids = np.zeros(self.n_handles, np.uint32)
+        n, fired, det = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.fgi_part_timers_run_due(self.h, now, _ptr(ids, C.c_uint32), len(ids), C.byref(n), C.byref(fired),
+                                                     C.byref(det), C.byref(stats) if stats is not None else None),
+                    "part_timers_run_due")
+        return ids[:n.value].copy(), int(fired.value), int(det.value)
+
+    def part_timers_fired_detached(self) -> np.ndarray:
+        """fgi_part_timers_fired_detached: the local detached handles whose timers the rank's last tick fired."""
+        n = C.c_uint64()
+        self._check(self.lib.fgi_part_timers_fired_detached(self.h, None, 0, C.byref(n)), "part_timers_fired_detached")
+        h = np.zeros(n.value, np.uint32)
+        self._check(self.lib.fgi_part_timers_fired_detached(self.h, _ptr(h, C.c_uint32), len(h), C.byref(n)),
+                    "part_timers_fired_detached")
+        return h
+
     def last_wave_flagged(self) -> Tuple[np.ndarray, np.ndarray]:
         """fgi_last_wave_flagged: (handles, state_flags) of the nodes the last call's cascade flagged
         (InvalidateOnSetOutput / InvalidationDelayStarted newly set) without invalidating them, ascending."""
@@ -1174,6 +1212,19 @@ def part_local_prune(graphs):
     if st != OK:
         _local_error(lib, graphs, st, "fgi_part_local_prune")
     return list(stats)
+
+
+def part_local_timers_run_due(graphs, now: int):
+    """fgi_part_local_timers_run_due: the tick on every rank of an in-process group. Returns (entries fired per
+    rank, those on detached handles per rank, per-rank WaveStats); ids: part_last_wave_ids of each rank."""
+    lib = load_library()
+    arr_g = (C.c_void_p * len(graphs))(*[g.h.value for g in graphs])
+    fired, det = np.zeros(len(graphs), np.uint64), np.zeros(len(graphs), np.uint64)
+    stats = (WaveStats * len(graphs))()
+    st = lib.fgi_part_local_timers_run_due(arr_g, len(graphs), now, _ptr(fired, C.c_uint64), _ptr(det, C.c_uint64), stats)
+    if st != OK:
+        _local_error(lib, graphs, st, "fgi_part_local_timers_run_due")
+    return [int(x) for x in fired], [int(x) for x in det], list(stats)
 
 
 def _ptr_array(arrays, ct):
