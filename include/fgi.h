@@ -590,6 +590,76 @@ fgi_status fgi_timers_stats_get(fgi_graph* g, fgi_timer_stats* out);
 fgi_status fgi_timers_list(fgi_graph* g, uint32_t* handle, uint64_t* version, uint64_t* due, uint64_t cap,
                            uint64_t* out_n);
 
+/* ---- auto-invalidation timers: armed at TrySetOutput (C-ABI 0.13; timers.hip) ---------- */
+/* The other half of the Timeouts.Invalidate timer set: a node that becomes Consistent schedules Invalidate(true)
+ * after ComputedOptions.AutoInvalidationDelay, or after TransientErrorInvalidationDelay when its output is a
+ * transient error (StartAutoInvalidation, Computed.cs:235-246, called by TrySetOutput, Computed.cs:158). Both go
+ * through ComputedExt.Invalidate(TimeSpan) -> AddOrUpdateToEarlier (ComputedExt.cs:10-25), as the delay timers
+ * of the section above do, so the entries share that section's pool, due pass and fire wave; an entry carries a
+ * kind (bit 0: auto) beside (handle, version, due). Single device only: on a partitioned graph all six calls
+ * return FGI_ENOTSUP.
+ * Opt-in: fgi_timers_auto_open needs open timers (FGI_ESTATE before fgi_timers_open, when already on, or on a
+ * poisoned graph). Until it is called no call here allocates or launches anything: fgi_set_output,
+ * fgi_set_output_ex and fgi_run_batch behave and launch exactly as before 0.13, fgi_timers_set_auto_delay and
+ * fgi_timers_start_auto return FGI_ESTATE, fgi_timers_auto_stats_get returns zeros, fgi_timers_list_ex lists
+ * every kind as 0. fgi_timers_close turns auto off too.
+ * Delays: two per handle (auto, transient error), set by fgi_timers_set_auto_delay (a null array leaves that
+ * delay as it is; a handle out of range or listed twice: FGI_EINVAL, nothing stored), sticky for a slot across
+ * recomputations and copied onto a detached handle by the move, exactly as fgi_timers_set_delay's. 0: the
+ * graph's default of that kind (fgi_timers_auto_config; 0 = none). FGI_TIMER_NEVER: none (TimeSpan.MaxValue,
+ * Computed.cs:244, ComputedExt.cs:12). An effective delay of 0 or NEVER stores nothing. The reference's "delay <= 0 means
+ * invalidate at once" (ComputedExt.cs:15-18) is NOT built: a host that wants it calls fgi_invalidate.
+ * Candidates: an item of fgi_set_output / fgi_set_output_ex, or of a batch's SET_OUTPUT step, whose node went
+ * Computing -> Consistent and did NOT carry InvalidateOnSetOutput (Computed.cs:153-156 returns before
+ * StartAutoInvalidation; a node with an InvalidationDelay survives its own cascade as Consistent with
+ * InvalidationDelayStarted and gets its delay entry only). fgi_set_output is fgi_set_output_ex with
+ * transient == NULL; transient[i] != 0 marks item i's output as a transient error. A SET_OUTPUT step's flags
+ * (nullable) are its items' transient flags, read only on a graph with auto open. fgi_timers_start_auto lists
+ * candidates explicitly (handles in range and distinct, else FGI_EINVAL and nothing stored): for nodes
+ * registered Consistent in bulk, whose TrySetOutput the engine never saw.
+ * Auto arm rule, for candidate h, run by a kernel queued behind the call's cascade: the node now at h, its visit
+ * bit folded in, is Consistent, and d = transient ? transient_delay(h) : auto_delay(h) is finite and non-zero:
+ * store (h, version, due = now + d, saturating as above, kind = auto). An entry of another version at h is
+ * overwritten (dropped + armed, as above). One of the same version takes due = min(stored, new) and the union
+ * of the kinds, counted in `merged`, neither armed nor dropped (AddOrUpdateToEarlier, ComputedExt.cs:22).
+ * Delay arm rule meeting an auto entry of the same version: due = min, the kind bit stays, counted in `merged`;
+ * two delay arms of one version keep the stored due time, as before.
+ * Fire: a due entry fires if its version matches and the node is Consistent and (InvalidationDelayStarted or
+ * the entry is auto): the reference's timer calls Invalidate(true) on any live computed (ComputedExt.cs:35).
+ * Everything after that is the section above's: one wave with immediately = 1, its flagged set arms at `now`,
+ * and armed == fired + dropped + stored holds with auto entries included. fired_auto counts the fired entries
+ * of kind auto, armed_auto the entries the auto arm rule stored (new or overwriting).
+ * Move: a moved entry keeps its kind. Behind a moved auto entry the delay arm rule also runs on the detached
+ * handle (min merge): the displacement's Invalidate() has just set InvalidationDelayStarted on the surviving
+ * node, and the reference adds its delay timer to the auto one and keeps the earlier
+ * (ComputedRegistry.cs:91-96 -> Computed.cs:186-197).
+ * Batches: behind the batch the steps are walked in order: a SET_OUTPUT step auto-arms, a BEGIN_COMPUTE step
+ * applies its moves; then the batch's flagged records arm once, as before. A SET_OUTPUT item's candidate handle
+ * is where that node lives when the batch ends: the item's handle, or the detached handle of the first later
+ * BEGIN_COMPUTE step on its slot, or nothing if that step's out is FGI_NONE; its delays are the item's own
+ * handle's. The arm rule reads end-of-batch states, so a node the batch later invalidated is not Consistent and
+ * gets no entry. A step's `out` stays 0 / 1.
+ * Memory: 8 more bytes per handle. The pool bound counts a handle with an auto or transient code of its own as
+ * a holder, and every handle when a default of either kind is set; still at most one entry per handle.
+ * fgi_restore, fgi_release, lazy removal, fgi_timers_next_due, fgi_timers_list (which omits the kind) and
+ * fgi_timers_stats_get behave as in the section above; fgi_restore keeps the auto delays and counters. */
+typedef struct fgi_timers_auto_config {
+    uint32_t struct_size, reserved;
+    uint64_t default_auto_delay, default_transient_delay; /* 0 = none */
+} fgi_timers_auto_config;
+typedef struct fgi_timer_auto_stats {
+    uint64_t armed_auto, merged, fired_auto;
+} fgi_timer_auto_stats;
+fgi_status fgi_timers_auto_open(fgi_graph* g, const fgi_timers_auto_config* cfg);
+fgi_status fgi_timers_set_auto_delay(fgi_graph* g, uint32_t n, const uint32_t* handle,
+                                     const uint64_t* auto_delay /*nullable*/, const uint64_t* transient_delay /*nullable*/);
+fgi_status fgi_set_output_ex(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint8_t* transient /*nullable*/,
+                             uint8_t* out_set, uint32_t* out_ids, uint64_t cap, uint64_t* out_n, fgi_wave_stats* stats);
+fgi_status fgi_timers_start_auto(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint8_t* transient /*nullable*/);
+fgi_status fgi_timers_auto_stats_get(fgi_graph* g, fgi_timer_auto_stats* out);
+fgi_status fgi_timers_list_ex(fgi_graph* g, uint32_t* handle, uint64_t* version, uint64_t* due,
+                              uint8_t* kind /*bit 0: auto*/, uint64_t cap, uint64_t* out_n);
+
 /* ---- delay timers per rank of a partition (C-ABI 0.12; timers.hip) -------------------- */
 /* The same timers on a partitioned graph: each rank keeps the entries of its own local handles in its own
  * device memory, arms them behind its own share of every cascade, and a clock tick is ONE collective call whose

@@ -1123,6 +1123,19 @@ fgi_status timers_drop_handles(fgi_graph* g, uint32_t n, const uint32_t* handles
 // fgi_restore: every entry is dropped; the clock and the delays stay
 fgi_status timers_restore(fgi_graph* g);
 void timers_destroy(fgi_graph* g);
+// auto-invalidation (C-ABI 0.13): whether fgi_timers_auto_open was called on the graph's open timers
+bool timers_auto_on(const fgi_graph* g);
+// The auto arm rule over n candidates, queued behind whatever the stream holds, then one wait (the host arrays
+// are the caller's: consumed when this returns) unless wait is false: then the host arrays stay as they are until
+// the caller's timers_wait. Candidate i is handle[i] (boundary handle, host; FGI_NONE: none)
+// if its set code is 1 (code_dev, a device array, or code_host; both null: every item is a candidate; 2 = set
+// with InvalidateOnSetOutput, 0 = not set: no candidate). src (host, nullable): the handle whose delay codes
+// item i reads, where that is not handle[i] (a batch's node that a later step moved). transient (host,
+// nullable): item i picks the transient-error delay.
+fgi_status timers_arm_auto(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint32_t* src, const uint8_t* code_dev,
+                           const uint8_t* code_host, const uint8_t* transient, bool wait = true);
+// waits for what the timers' hooks queued and reads their counters
+fgi_status timers_wait(fgi_graph* g);
 // ---- sharded loads (shard.hip) ----
 // Their collectives, over the partition's transport (part.hip, PartComm): host words (at most kShardWords
 // per rank) all-gathered on the host; device byte ranges with per-peer counts, all-gathered (src[0,

@@ -20,6 +20,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <unordered_map>
 
 #include "fgi_internal.h"
 
@@ -514,9 +515,11 @@ __global__ void k_au_pending(uint64_t nc, const Cand* __restrict__ cand, const u
 }
 
 // ---- set_output ------------------------------------------------------------------------------
+// out_set[i]: 0 not set, 1 set, ioso_code (1, or 2 where the auto-invalidation timers need to tell) set on a node
+// that carried InvalidateOnSetOutput
 __device__ __forceinline__ void set_output(uint32_t i, const uint32_t* __restrict__ h, uint32_t n_handles,
                                            unsigned long long* node, uint8_t* out_set, uint32_t* roots,
-                                           unsigned long long* nroots) {
+                                           unsigned long long* nroots, uint8_t ioso_code) {
     uint8_t set = 0;
     const uint32_t x = h[i];
     if (x < n_handles) {
@@ -526,7 +529,10 @@ __device__ __forceinline__ void set_output(uint32_t i, const uint32_t* __restric
             const unsigned long long prev = atomicCAS(node + x, w, nw);
             if (prev == w) {
                 set = 1;
-                if (w & kW_IOSO) roots[atomicAdd(nroots, 1ull)] = x;     // 150-156
+                if (w & kW_IOSO) {                                       // 150-156
+                    roots[atomicAdd(nroots, 1ull)] = x;
+                    set = ioso_code;
+                }
                 break;
             }
             w = prev;
@@ -536,9 +542,9 @@ __device__ __forceinline__ void set_output(uint32_t i, const uint32_t* __restric
 }
 
 __global__ void k_set_output(uint32_t n, const uint32_t* __restrict__ h, uint32_t n_handles, unsigned long long* node,
-                             uint8_t* out_set, uint32_t* roots, unsigned long long* nroots) {
+                             uint8_t* out_set, uint32_t* roots, unsigned long long* nroots, uint8_t ioso_code) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) set_output(i, h, n_handles, node, out_set, roots, nroots);
+    if (i < n) set_output(i, h, n_handles, node, out_set, roots, nroots, ioso_code);
 }
 
 // ---- streaming batches (fgi_run_batch) ------------------------------------------------------------
@@ -640,10 +646,11 @@ __global__ void kb_finish(const unsigned long long* top, unsigned long long* dst
 }
 
 __global__ void kb_set_output(const unsigned long long* ab, uint32_t n, const uint32_t* __restrict__ h, uint32_t n_handles,
-                              unsigned long long* node, uint8_t* out_set, uint32_t* roots, unsigned long long* nroots) {
+                              unsigned long long* node, uint8_t* out_set, uint32_t* roots, unsigned long long* nroots,
+                              uint8_t ioso_code) {
     if (batch_aborted(ab)) return;
     const uint64_t i = grid_tid();
-    if (i < n) set_output((uint32_t)i, h, n_handles, node, out_set, roots, nroots);
+    if (i < n) set_output((uint32_t)i, h, n_handles, node, out_set, roots, nroots, ioso_code);
 }
 
 // ---- prune -----------------------------------------------------------------------------------
@@ -1876,7 +1883,9 @@ fgi_status fgi_version(uint32_t* major, uint32_t* minor) {
     //      _next_due / _stats_get / _list)
     // 0.12: the same per rank of a partition (fgi_part_timers_open / _set_delay / _run_due / _fired_detached,
     //      fgi_part_local_timers_run_due)
-    if (minor) *minor = 12;
+    // 0.13: auto-invalidation timers, armed at TrySetOutput (fgi_timers_auto_open, fgi_timers_set_auto_delay,
+    //      fgi_set_output_ex, fgi_timers_start_auto, fgi_timers_auto_stats_get, fgi_timers_list_ex)
+    if (minor) *minor = 13;
     return FGI_OK;
 }
 
@@ -2984,12 +2993,33 @@ fgi_status fgi_add_used(fgi_graph* g, uint32_t n, const uint32_t* dependant, con
     return FGI_OK;
 }
 
+static fgi_status set_output_impl(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint8_t* transient, uint8_t* out_set,
+                                  uint32_t* out_ids, uint64_t cap, uint64_t* out_n, fgi_wave_stats* stats);
+
 fgi_status fgi_set_output(fgi_graph* g, uint32_t n, const uint32_t* handle, uint8_t* out_set, uint32_t* out_ids,
                           uint64_t cap, uint64_t* out_n, fgi_wave_stats* stats) {
+    return set_output_impl(g, n, handle, nullptr, out_set, out_ids, cap, out_n, stats);
+}
+
+fgi_status fgi_set_output_ex(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint8_t* transient, uint8_t* out_set,
+                             uint32_t* out_ids, uint64_t cap, uint64_t* out_n, fgi_wave_stats* stats) {
+    if (g && (g->part || g->world > 1)) {
+        if (out_n) *out_n = 0;
+        return set_err(g, FGI_ENOTSUP, "fgi_set_output_ex: auto-invalidation timers serve a single device, not a partition");
+    }
+    return set_output_impl(g, n, handle, transient, out_set, out_ids, cap, out_n, stats);
+}
+
+// fgi_set_output and fgi_set_output_ex. With auto-invalidation open (fgi_timers_auto_open) the kernel marks the
+// items set on a node that carried InvalidateOnSetOutput, and the auto arm rule runs behind the cascade over the
+// others that were set.
+static fgi_status set_output_impl(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint8_t* transient, uint8_t* out_set,
+                                  uint32_t* out_ids, uint64_t cap, uint64_t* out_n, fgi_wave_stats* stats) {
     if (!g || (n && !handle)) return FGI_EINVAL;
     if (out_n) *out_n = 0;
     if (n == 0) return FGI_OK;
     FGI_TRY(single_only(g, "fgi_set_output"));
+    const bool autos = timers_auto_on(g);
     g->flg_last = -1;
     g->flg_drop.clear();
     hipSetDevice(g->device);
@@ -3007,10 +3037,12 @@ fgi_status fgi_set_output(fgi_graph* g, uint32_t n, const uint32_t* handle, uint
     note_words(g);
     FGI_HIP(g, hipMemsetAsync(g->misc_dev, 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_set_output, dim3(nblk(n)), dim3(256), 0, st, n, dh, g->n_handles,
-                       reinterpret_cast<unsigned long long*>(g->node), dset, droots, g->misc_dev);
+                       reinterpret_cast<unsigned long long*>(g->node), dset, droots, g->misc_dev, (uint8_t)(autos ? 2 : 1));
     unsigned long long nr = 0;
     FGI_TRY(d2h(g, &nr, g->misc_dev, 1));
     if (out_set) FGI_TRY(d2h(g, out_set, dset, n));
+    if (out_set && autos)
+        for (uint32_t i = 0; i < n; ++i) out_set[i] = out_set[i] != 0;
     g->last_wave_n = 0;
     fanout_note(g, kCascWave);   // a call without roots ran an empty cascade
     if (nr)   // Invalidate() (Computed.cs:153-156)
@@ -3020,6 +3052,7 @@ fgi_status fgi_set_output(fgi_graph* g, uint32_t n, const uint32_t* handle, uint
         FGI_TRY(view_refresh(g, kViewLabels, dh, n));
         FGI_TRY(view_commit(g));
     }
+    if (autos) FGI_TRY(timers_arm_auto(g, n, handle, nullptr, dset, nullptr, transient));   // Computed.cs:158
     return copy_ids(g, out_ids, cap, out_n);
 }
 
@@ -3167,7 +3200,7 @@ fgi_status Batch::launch(bool timed, const RecSink* sink) {
                 FGI_TRY(fold(g));
                 note_words(g);
                 hipLaunchKernelGGL(kb_set_output, dim3(nblk(n)), dim3(256), 0, st, abort, n, b.h, g->n_handles, node,
-                                   b.out8, b.roots, b.cnt);
+                                   b.out8, b.roots, b.cnt, (uint8_t)(timers_auto_on(g) ? 2 : 1));
                 FGI_TRY(wave(n, b.roots, nullptr, b.cnt, b.cnt));   // Invalidate() of InvalidateOnSetOutput nodes (153-156)
                 break;
         }
@@ -3438,8 +3471,57 @@ fgi_status Batch::sub_moves(uint32_t end) {
 // displaced node's timer to its detached handle or arm it there, in step order: a launch takes a slot once,
 // so a slot the batch displaced k times has its moves in k launches. Then the arm rule runs once over the
 // records of the batch's cascades, on the states the batch left.
+//
+// With auto-invalidation open the steps are walked one by one instead: a SET_OUTPUT step runs the auto arm rule
+// over its items that were set without InvalidateOnSetOutput, each at the handle where its node lives when the
+// batch ends (its own, or the detached handle the first later BEGIN_COMPUTE step on its slot handed out, or none
+// if that step's node did not survive) with the delays of the item's own handle; a BEGIN_COMPUTE step applies
+// its moves. flags of a SET_OUTPUT step: the items' transient-error flags (the caller's array, still valid).
+// The arm launches are queued without a wait; a step with moves waits once (timers_move), as a displacement
+// round does without auto, and one more wait ends the walk if arm launches are still queued then.
 fgi_status Batch::timer_moves(uint32_t end) {
     if (!timers_on(g)) return FGI_OK;
+    if (timers_auto_on(g)) {
+        std::vector<std::vector<uint32_t>> cand(end);
+        std::unordered_map<uint32_t, uint32_t> later;   // slot -> the out of the nearest later BEGIN_COMPUTE step on it
+        for (uint32_t k = end; k-- > 0;) {
+            const fgi_step& sp = steps[k];
+            if (sp.kind == FGI_STEP_BEGIN_COMPUTE) {
+                const uint32_t* o = reinterpret_cast<const uint32_t*>(H + res_off + bs[k].out_off);
+                for (uint32_t i = 0; i < sp.n; ++i) later[sp.handles[i]] = o[i] == FGI_NONE ? FGI_NONE : o[i] - g->lbl_K;
+            } else if (sp.kind == FGI_STEP_SET_OUTPUT) {
+                cand[k].assign(sp.handles, sp.handles + sp.n);
+                for (uint32_t& c : cand[k]) {
+                    const auto it = later.find(c);
+                    if (it != later.end()) c = it->second;
+                }
+            }
+        }
+        std::vector<uint32_t> src, dst;
+        bool armed = false;   // an arm launch is queued whose host arrays (cand, the caller's) are not consumed yet
+        for (uint32_t k = 0; k < end; ++k) {
+            const fgi_step& sp = steps[k];
+            if (sp.kind == FGI_STEP_SET_OUTPUT) {
+                FGI_TRY(timers_arm_auto(g, sp.n, cand[k].data(), sp.handles, nullptr,
+                                        reinterpret_cast<const uint8_t*>(H + res_off + bs[k].out_off), sp.flags, false));
+                armed = armed || sp.n != 0;
+            } else if (sp.kind == FGI_STEP_BEGIN_COMPUTE) {
+                const uint32_t* o = reinterpret_cast<const uint32_t*>(H + res_off + bs[k].out_off);
+                src.clear();
+                dst.clear();
+                for (uint32_t i = 0; i < sp.n; ++i)
+                    if (o[i] != FGI_NONE) {
+                        src.push_back(sp.handles[i]);
+                        dst.push_back(o[i] - g->lbl_K);
+                    }
+                FGI_TRY(timers_move(g, (uint32_t)src.size(), src.data(), dst.data()));   // (waits, when it has pairs)
+                armed = armed && src.empty();
+            }
+        }
+        if (armed) FGI_TRY(timers_wait(g));   // one wait for the arm launches since the last move
+        if (rec_on) FGI_TRY(timers_arm_records(g, g->brec, std::min<uint64_t>(scr_h[rcur_word], g->brec_cap), nullptr));
+        return FGI_OK;
+    }
     std::vector<std::vector<uint32_t>> src, dst;
     std::vector<uint8_t>& seen = seen_scratch(g, g->ext_slots);   // a slot's moves so far; cleared again below
     for (uint32_t k = 0; k < end && n_begin; ++k) {
@@ -3536,8 +3618,11 @@ fgi_status Batch::unpack(uint32_t* out_ids, uint64_t cap, uint64_t* out_n) {
         const fgi_step& sp = steps[k];
         if (!sp.out || !sp.n) continue;
         const char* src = H + res_off + bs[k].out_off;
-        if (sp.kind == FGI_STEP_SET_OUTPUT) std::memcpy(sp.out, src, sp.n);
-        else if (sp.kind == FGI_STEP_BEGIN_COMPUTE || sp.kind == FGI_STEP_ADD_USED) std::memcpy(sp.out, src, sp.n * 4);
+        if (sp.kind == FGI_STEP_SET_OUTPUT) {
+            std::memcpy(sp.out, src, sp.n);
+            if (timers_auto_on(g))   // the staging tells "set" (1) from "set with InvalidateOnSetOutput" (2)
+                for (uint32_t i = 0; i < sp.n; ++i) static_cast<uint8_t*>(sp.out)[i] = src[i] != 0;
+        } else if (sp.kind == FGI_STEP_BEGIN_COMPUTE || sp.kind == FGI_STEP_ADD_USED) std::memcpy(sp.out, src, sp.n * 4);
         if (sp.kind == FGI_STEP_BEGIN_COMPUTE && g->lbl_K) {   // detached handles: label K + handle
             uint32_t* o = static_cast<uint32_t*>(sp.out);
             for (uint32_t i = 0; i < sp.n; ++i)
@@ -4195,7 +4280,7 @@ fgi_status part_set_output(fgi_graph* g, uint32_t n, const uint32_t* slot, uint8
         FGI_TRY(tmalloc(g, tr, &droots, m));
         FGI_TRY(h2d(g, dh, lh.data(), m));
         hipLaunchKernelGGL(k_set_output, dim3(nblk(m)), dim3(256), 0, st, m, dh, g->n_handles,
-                           reinterpret_cast<unsigned long long*>(g->node), dset, droots, g->misc_dev);
+                           reinterpret_cast<unsigned long long*>(g->node), dset, droots, g->misc_dev, (uint8_t)1);
         FGI_TRY(d2h(g, set.data(), dset, m));
     }
     unsigned long long nr = 0;

@@ -22,6 +22,15 @@
 // which wait for the device anyway (tm_reserve).
 // Everything is allocated by fgi_timers_open; a graph that never opens timers launches nothing here.
 //
+// Auto-invalidation (C-ABI 0.13: fgi_timers_auto_open, _set_auto_delay, _start_auto, _auto_stats_get, _list_ex, and
+// the hook timers_arm_auto behind fgi_set_output_ex and a batch's SET_OUTPUT steps; single device only): two more
+// delay codes per handle (adl, tdl; the same dtab) and a kind per record (TimerRec.pad bit 0: auto).
+//   k_tm_arm_auto   the auto arm rule over (handle, set code, transient) candidates; it ends in tm_store, as the
+//                   delay arm rule does, where an entry of the same version takes the earlier due time and the
+//                   union of the kinds if either side is auto.
+// The due pass fires an auto entry on any Consistent node of its version; a moved auto entry is followed by the
+// delay arm rule on the detached handle. A rank's kernels never see an auto entry.
+//
 // Per rank of a partition (C-ABI 0.12: fgi_part_timers_open, _set_delay, _run_due, _fired_detached,
 // fgi_part_local_timers_run_due, and the hook timers_arm_part): the table covers the rank's local handles, as
 // fgi_dump_states and the rank's state view address them. Handle h < n_local is the host's slot base + h, whose
@@ -79,6 +88,11 @@ struct Timers {
     uint32_t* groots = nullptr;            // [groots_cap] every rank's fired slots, gathered in rank order
     uint64_t groots_cap = 0;
     std::vector<uint32_t> fdet;            // the last tick's fired detached handles, ascending (fgi_part_timers_fired_detached)
+    // auto-invalidation (fgi_timers_auto_open; single device only): null / false until then
+    bool autos = false;
+    uint64_t def_auto = 0, def_trans = 0;  // the graph's default AutoInvalidationDelay / TransientErrorInvalidationDelay
+    uint32_t* adl = nullptr;               // [ext_handles] auto delay codes, coded as dly (the same dtab)
+    uint32_t* tdl = nullptr;               // [ext_handles] transient-error delay codes
 };
 
 namespace {
@@ -87,7 +101,9 @@ constexpr int kTBlock = 256;
 constexpr uint32_t kCodeNever = 0xFFFFFFFFu;
 constexpr uint32_t kClaim = 0xFFFFFFFEu;   // ent[h] while a lane of the running launch works on h
 // device counters
-enum { kTTop = 0, kTArmed, kTFired, kTDropped, kTMoved, kTTomb, kTFail, kTNewTop, kTFiredN, kTCoded, kTMin, kTFiredD, kTWords = 16 };
+enum { kTTop = 0, kTArmed, kTFired, kTDropped, kTMoved, kTTomb, kTFail, kTNewTop, kTFiredN, kTCoded, kTMin, kTFiredD,
+       kTArmedA, kTMerged, kTFiredA, kTCodedA, kTWords = 16 };
+constexpr uint32_t kKindAuto = 1u;         // TimerRec.pad bit 0: the entry is (also) an auto-invalidation's
 
 // what every kernel reads a node and the table through
 struct TmTab {
@@ -103,6 +119,9 @@ struct TmTab {
     uint32_t n_dtab;
     unsigned long long* ctr;
     unsigned long long now, default_delay;
+    uint32_t* adl;              // null: auto-invalidation is off
+    uint32_t* tdl;
+    unsigned long long def_auto, def_trans;
 };
 
 // How a handle finds its node: on a single device through the table's own K and s2l (TmOne), on a rank of a
@@ -141,42 +160,60 @@ __device__ inline unsigned long long tm_word(const TmTab& a, const TmPart& p, ui
 __device__ inline bool tm_waiting(unsigned long long w) {
     return (w & kVMask) != 0 && word_state(w) == FGI_CONSISTENT && (w & kW_DS) != 0;
 }
-__device__ inline unsigned long long tm_delay(const TmTab& a, uint32_t h) {
-    const uint32_t c = a.dly[h];
-    if (c == 0) return a.default_delay;
+__device__ inline unsigned long long tm_decode(const TmTab& a, uint32_t c, unsigned long long dflt) {
+    if (c == 0) return dflt;
     if (c == kCodeNever || c - 1 >= a.n_dtab) return FGI_TIMER_NEVER;
     return a.dtab[c - 1];
+}
+__device__ inline unsigned long long tm_delay(const TmTab& a, uint32_t h) { return tm_decode(a, a.dly[h], a.default_delay); }
+// now + d, saturating
+__device__ inline unsigned long long tm_due_at(const TmTab& a, unsigned long long d) {
+    const unsigned long long due = a.now + d;
+    return due < a.now || due == FGI_TIMER_NEVER ? FGI_TIMER_NEVER - 1 : due;
 }
 
 // what a fired handle is called in the wave's root list
 __device__ inline uint32_t tm_root(const TmOne&, uint32_t h) { return h; }
 __device__ inline uint32_t tm_root(const TmPart& p, uint32_t h) { return p.base + h; }   // an owned slot: the host's global id
 
-// The arm rule on candidate h of every lane for which cand holds. Called by whole wavefronts.
-template <class M>
-__device__ inline void tm_arm(const TmTab& a, const M& map, bool cand, uint32_t h, uint32_t lane) {
-    bool fresh = false;
-    unsigned long long v = 0, due = 0;
-    if (cand && h < a.n_handles) {
-        const unsigned long long w = tm_word(a, map, h);
-        const unsigned long long d = tm_waiting(w) ? tm_delay(a, h) : 0ull;
-        if (d != 0 && d != FGI_TIMER_NEVER) {
-            v = w & kVMask;
-            due = a.now + d;
-            if (due < a.now || due == FGI_TIMER_NEVER) due = FGI_TIMER_NEVER - 1;
-            const uint32_t e = __hip_atomic_exchange(a.ent + h, kClaim, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-            if (e == FGI_NONE) {
-                fresh = true;
-            } else if (e != kClaim) {   // (kClaim: another lane of this launch has h, and will leave the same entry)
-                if (e < a.cap && a.rec[e].version != v) {   // another version's entry: overwritten
-                    a.rec[e].version = v;
-                    a.rec[e].due = due;
-                    atomicAdd(a.ctr + kTArmed, 1ull);
-                    atomicAdd(a.ctr + kTDropped, 1ull);
+// Stores (h, v, due, kind) for every lane with `want`: the common end of the delay arm rule (kind 0) and the auto
+// arm rule (kind kKindAuto). An entry of another version at h is overwritten; one of the same version keeps its
+// place and, if either it or the new one is an auto-invalidation's, takes the earlier due time and the union
+// of the kinds (ConcurrentTimerSet.AddOrUpdateToEarlier; counted in kTMerged); two delay arms of one version
+// leave the stored due time. Called by whole wavefronts.
+__device__ inline void tm_store(const TmTab& a, bool want, uint32_t h, unsigned long long v, unsigned long long due, uint32_t kind,
+                                uint32_t lane) {
+    bool fresh = false, over = false, merged = false;
+    if (want) {
+        const uint32_t e = __hip_atomic_exchange(a.ent + h, kClaim, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        if (e == FGI_NONE) {
+            fresh = true;
+        } else if (e != kClaim) {   // (kClaim: another lane of this launch has h, and will leave the same entry)
+            if (e < a.cap) {
+                TimerRec& r = a.rec[e];
+                if (r.version != v) {   // another version's entry: overwritten
+                    r.version = v;
+                    r.due = due;
+                    r.pad = kind;
+                    over = true;
+                } else if (kind || (r.pad & kKindAuto)) {
+                    if (due < r.due) r.due = due;
+                    r.pad |= kind;
+                    merged = true;
                 }
-                __hip_atomic_store(a.ent + h, e, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
             }
+            __hip_atomic_store(a.ent + h, e, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         }
+    }
+    // the counters, one atomic per wavefront and counter (a recomputed graph overwrites an entry per item)
+    const unsigned long long mo = __ballot(over), mm = __ballot(merged);
+    if (lane == 0) {
+        if (mo) {
+            atomicAdd(a.ctr + kTArmed, (unsigned long long)__popcll(mo));
+            atomicAdd(a.ctr + kTDropped, (unsigned long long)__popcll(mo));
+            if (kind) atomicAdd(a.ctr + kTArmedA, (unsigned long long)__popcll(mo));
+        }
+        if (mm) atomicAdd(a.ctr + kTMerged, (unsigned long long)__popcll(mm));
     }
     const unsigned long long m = __ballot(fresh);
     if (!m) return;
@@ -188,7 +225,7 @@ __device__ inline void tm_arm(const TmTab& a, const M& map, bool cand, uint32_t 
     if (fresh) {
         const unsigned long long idx = base + __popcll(m & ((1ull << lane) - 1));
         if (idx < a.cap) {
-            a.rec[idx] = TimerRec{due, v, h, 0u};
+            a.rec[idx] = TimerRec{due, v, h, kind};
             __hip_atomic_store(a.ent + h, (uint32_t)idx, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
             stored = true;
         } else {   // never with the host's capacity bound: the call that reads the counters next fails
@@ -197,7 +234,27 @@ __device__ inline void tm_arm(const TmTab& a, const M& map, bool cand, uint32_t 
         }
     }
     const unsigned long long ms = __ballot(stored);
-    if ((int)lane == leader && ms) atomicAdd(a.ctr + kTArmed, (unsigned long long)__popcll(ms));
+    if ((int)lane == leader && ms) {
+        atomicAdd(a.ctr + kTArmed, (unsigned long long)__popcll(ms));
+        if (kind) atomicAdd(a.ctr + kTArmedA, (unsigned long long)__popcll(ms));
+    }
+}
+
+// The arm rule on candidate h of every lane for which cand holds. Called by whole wavefronts.
+template <class M>
+__device__ inline void tm_arm(const TmTab& a, const M& map, bool cand, uint32_t h, uint32_t lane) {
+    bool want = false;
+    unsigned long long v = 0, due = 0;
+    if (cand && h < a.n_handles) {
+        const unsigned long long w = tm_word(a, map, h);
+        const unsigned long long d = tm_waiting(w) ? tm_delay(a, h) : 0ull;
+        if (d != 0 && d != FGI_TIMER_NEVER) {
+            want = true;
+            v = w & kVMask;
+            due = tm_due_at(a, d);
+        }
+    }
+    tm_store(a, want, h, v, due, 0u, lane);
 }
 
 // Candidates: flagged records (rec != null: boundary handle << 32 | flags), else every handle below n_max.
@@ -219,6 +276,40 @@ __global__ __launch_bounds__(kTBlock) void k_tm_arm(TmTab a, const unsigned long
     }
 }
 
+// The auto arm rule (StartAutoInvalidation, Computed.cs:235-246) over n candidates. Item i is a candidate if its
+// set code is 1 (code null: every item; 2: set with InvalidateOnSetOutput, Computed.cs:153-156 returns before
+// StartAutoInvalidation; 0: not set). The node now at hs[i] must be Consistent; its delay is the transient-error
+// one if tr[i] (tr nullable), else the auto one, read at src[i] (src nullable: at hs[i]). Wavefronts stride over
+// runs of 64 candidates, as k_tm_arm's.
+__global__ __launch_bounds__(kTBlock) void k_tm_arm_auto(TmTab a, uint64_t n, const uint32_t* hs, const uint32_t* src,
+                                                         const uint8_t* code, const uint8_t* tr) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t base = (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64; base < n; base += nwaves * 64) {
+        const uint64_t i = base + lane;
+        bool want = false;
+        uint32_t h = 0;
+        unsigned long long v = 0, due = 0;
+        if (i < n && (!code || code[i] == 1)) {
+            h = hs[i];
+            const uint32_t s = src ? src[i] : h;
+            if (h < a.n_handles && s < a.n_handles) {
+                const unsigned long long w = tm_word(a, TmOne{}, h);
+                if ((w & kVMask) != 0 && word_state(w) == FGI_CONSISTENT) {
+                    const bool t = tr && tr[i];
+                    const unsigned long long d = tm_decode(a, t ? a.tdl[s] : a.adl[s], t ? a.def_trans : a.def_auto);
+                    if (d != 0 && d != FGI_TIMER_NEVER) {
+                        want = true;
+                        v = w & kVMask;
+                        due = tm_due_at(a, d);
+                    }
+                }
+            }
+        }
+        tm_store(a, want, h, v, due, kKindAuto, lane);
+    }
+}
+
 // The due pass over the pool [0, top) (top = min(ctr[kTTop], cap)): see the file comment. dst: the other copy.
 // On a rank of a partition (M = TmPart) a fired owned slot goes to `fired` as the host's global slot id and a
 // fired detached handle to fired_det (counted by ctr[kTFiredD]), both of fired_cap entries. top, first,
@@ -237,7 +328,9 @@ __device__ __forceinline__ void tm_due(const TmTab& a, const M& m, TimerRec* dst
         bool fire = false;
         if (is_due) {
             const unsigned long long w = tm_word(a, m, r.handle);
-            fire = tm_waiting(w) && (w & kVMask) == r.version;
+            // an auto-invalidation's timer calls Invalidate(true) on any live computed (ComputedExt.cs:35)
+            fire = (w & kVMask) != 0 && word_state(w) == FGI_CONSISTENT && ((w & kW_DS) != 0 || (r.pad & kKindAuto)) &&
+                   (w & kVMask) == r.version;
             a.ent[r.handle] = FGI_NONE;
         }
         bool fire_det = false;   // a rank's detached handle: no partitioned cascade reaches its node
@@ -246,8 +339,9 @@ __device__ __forceinline__ void tm_due(const TmTab& a, const M& m, TimerRec* dst
             fire = fire && !fire_det;
         }
         const unsigned long long mk = __ballot(keep), mf = __ballot(fire), md = __ballot(is_due && !fire && !fire_det);
-        unsigned long long mt = 0;
+        unsigned long long mt = 0, ma = 0;
         if constexpr (kPart) mt = __ballot(fire_det);
+        else ma = __ballot(fire && (r.pad & kKindAuto));
         unsigned long long bk = 0, bf = 0, bt = 0;
         if (lane == 0) {
             if (mk) bk = atomicAdd(a.ctr + kTNewTop, (unsigned long long)__popcll(mk));
@@ -260,6 +354,7 @@ __device__ __forceinline__ void tm_due(const TmTab& a, const M& m, TimerRec* dst
                 atomicAdd(a.ctr + kTFired, (unsigned long long)__popcll(mt));
             }
             if (md) atomicAdd(a.ctr + kTDropped, (unsigned long long)__popcll(md));
+            if (ma) atomicAdd(a.ctr + kTFiredA, (unsigned long long)__popcll(ma));
         }
         bk = __shfl(bk, 0);
         bf = __shfl(bf, 0);
@@ -299,8 +394,10 @@ __global__ void k_tm_commit(unsigned long long* ctr) {
     }
 }
 
-// pair i: the node that left slot from[i] lives on at to[i]. to[i] takes the slot's delay; the slot's entry
-// moves with it if it is the node's (same version), else the arm rule runs on to[i]. from[] distinct.
+// pair i: the node that left slot from[i] lives on at to[i]. to[i] takes the slot's delays; the slot's entry
+// moves with it, kind and all, if it is the node's (same version), else the arm rule runs on to[i]; it also runs
+// behind a moved auto entry (the displacement has just started the node's delay: the earlier due time stays,
+// ComputedRegistry.cs:91-96 -> Computed.cs:186-197). from[] distinct.
 __global__ __launch_bounds__(kTBlock) void k_tm_move(TmTab a, uint32_t n, const uint32_t* from, const uint32_t* to) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63;
@@ -311,6 +408,10 @@ __global__ __launch_bounds__(kTBlock) void k_tm_move(TmTab a, uint32_t n, const 
         d = to[i];
         if (d != FGI_NONE && f != d && f < a.n_handles && d < a.n_handles) {
             a.dly[d] = a.dly[f];
+            if (a.adl) {
+                a.adl[d] = a.adl[f];
+                a.tdl[d] = a.tdl[f];
+            }
             const unsigned long long w = tm_word(a, TmOne{}, d);
             const uint32_t e = a.ent[f];
             if (e != FGI_NONE && e < a.cap && (w & kVMask) != 0 && a.rec[e].version == (w & kVMask)) {
@@ -324,6 +425,7 @@ __global__ __launch_bounds__(kTBlock) void k_tm_move(TmTab a, uint32_t n, const 
                 a.ent[d] = e;
                 a.ent[f] = FGI_NONE;
                 atomicAdd(a.ctr + kTMoved, 1ull);
+                arm = (a.rec[e].pad & kKindAuto) != 0;
             } else {
                 arm = true;
             }
@@ -356,6 +458,23 @@ __global__ __launch_bounds__(kTBlock) void k_tm_set_delay(uint32_t* dly, uint32_
     if (handle[i] >= ext_slots) return;
     if (!old && c) atomicAdd(ctr + kTCoded, 1ull);
     if (old && !c) atomicAdd(ctr + kTCoded, ~0ull);   // - 1
+}
+
+// handle[i] takes the auto code ac[i] and the transient-error code tc[i] (each nullable: that code stays);
+// ctr[kTCodedA] follows the slots that hold either code, as ctr[kTCoded] follows dly's.
+__global__ __launch_bounds__(kTBlock) void k_tm_set_auto(uint32_t* adl, uint32_t* tdl, uint32_t n, const uint32_t* handle,
+                                                         const uint32_t* ac, const uint32_t* tc, uint32_t ext_slots,
+                                                         unsigned long long* ctr) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t h = handle[i];
+    const bool old = adl[h] || tdl[h];
+    if (ac) adl[h] = ac[i];
+    if (tc) tdl[h] = tc[i];
+    const bool now = adl[h] || tdl[h];
+    if (h >= ext_slots) return;
+    if (!old && now) atomicAdd(ctr + kTCodedA, 1ull);
+    if (old && !now) atomicAdd(ctr + kTCodedA, ~0ull);   // - 1
 }
 
 // ctr[kTMin] (set to FGI_TIMER_NONE first) = the smallest due time of the pool's entries
@@ -428,6 +547,10 @@ TmTab tm_tab(const fgi_graph* g) {
     a.ctr = t->ctr;
     a.now = t->now;
     a.default_delay = t->default_delay;
+    a.adl = t->autos ? t->adl : nullptr;
+    a.tdl = t->autos ? t->tdl : nullptr;
+    a.def_auto = t->def_auto;
+    a.def_trans = t->def_trans;
     return a;
 }
 
@@ -484,7 +607,9 @@ inline uint64_t tm_stored(const Timers* t) { return tm_top(t) - std::min<uint64_
 // Grows by copying; the caller's next kernel arguments are built afterwards.
 fgi_status tm_reserve(fgi_graph* g) {
     Timers* t = g->tim;
-    const bool every = t->default_delay != 0 && t->default_delay != FGI_TIMER_NEVER;
+    auto finite = [](uint64_t d) { return d != 0 && d != FGI_TIMER_NEVER; };
+    // (an auto or transient-error default lets any handle's node gain an entry, as a default delay does)
+    const bool every = finite(t->default_delay) || (t->autos && (finite(t->def_auto) || finite(t->def_trans)));
     const uint64_t holders = every ? g->ext_handles : std::min<uint64_t>(g->ext_handles, t->holders);
     const uint64_t need = holders + t->tomb_ub;
     if (t->cap >= need && t->rec[0]) return FGI_OK;
@@ -557,6 +682,41 @@ fgi_status timers_move(fgi_graph* g, uint32_t n, const uint32_t* from, const uin
     return tm_reserve(g);
 }
 
+bool timers_auto_on(const fgi_graph* g) { return g->tim && g->tim->autos; }
+
+fgi_status timers_arm_auto(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint32_t* src, const uint8_t* code_dev,
+                           const uint8_t* code_host, const uint8_t* transient, bool wait) {
+    if (!timers_auto_on(g) || !n) return FGI_OK;
+    Timers* t = g->tim;
+    hipStream_t s = g->stream;
+    FGI_TRY(flush_vis(g));
+    // the upload: handles | delay sources | set codes (bytes) | transient flags (bytes)
+    const uint64_t bw = ((uint64_t)n + 3) / 4;
+    FGI_TRY(tm_upload(g, 1, 2 * (uint64_t)n + 2 * bw));
+    uint32_t* dh = t->up;
+    uint32_t* ds = t->up + n;
+    uint8_t* dc = reinterpret_cast<uint8_t*>(t->up + 2 * (uint64_t)n);
+    uint8_t* dt = reinterpret_cast<uint8_t*>(t->up + 2 * (uint64_t)n + bw);
+    FGI_HIP(g, hipMemcpyAsync(dh, handle, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (src) FGI_HIP(g, hipMemcpyAsync(ds, src, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (!code_dev && code_host) FGI_HIP(g, hipMemcpyAsync(dc, code_host, n, hipMemcpyHostToDevice, s));
+    if (transient) FGI_HIP(g, hipMemcpyAsync(dt, transient, n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_tm_arm_auto, dim3(tgrid(n)), dim3(kTBlock), 0, s, tm_tab(g), (uint64_t)n, (const uint32_t*)dh,
+                       src ? (const uint32_t*)ds : (const uint32_t*)nullptr,
+                       code_dev ? code_dev : code_host ? (const uint8_t*)dc : (const uint8_t*)nullptr,
+                       transient ? (const uint8_t*)dt : (const uint8_t*)nullptr);
+    if (!wait) {
+        FGI_HIP(g, hipGetLastError());
+        return FGI_OK;
+    }
+    return tm_sync(g, "arming auto-invalidation timers");
+}
+
+fgi_status timers_wait(fgi_graph* g) {
+    if (!timers_on(g)) return FGI_OK;
+    return tm_sync(g, "arming auto-invalidation timers");
+}
+
 fgi_status timers_drop_handles(fgi_graph* g, uint32_t n, const uint32_t* handles) {
     if (!timers_on(g) || !n) return FGI_OK;
     Timers* t = g->tim;
@@ -589,7 +749,7 @@ fgi_status timers_restore(fgi_graph* g) {
 void timers_destroy(fgi_graph* g) {
     Timers* t = g->tim;
     if (!t) return;
-    void* dev[] = {t->dly, t->ent, t->rec[0], t->rec[1], t->dtab, t->ctr, t->fired, t->imm, t->up, t->groots};
+    void* dev[] = {t->dly, t->ent, t->rec[0], t->rec[1], t->dtab, t->ctr, t->fired, t->imm, t->up, t->groots, t->adl, t->tdl};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     if (t->ctr_h) (void)hipHostFree(t->ctr_h);
@@ -656,10 +816,10 @@ fgi_status fgi_timers_close(fgi_graph* g) {
     return FGI_OK;
 }
 
-// handle[i] (distinct, in range) takes delay[i]: what fgi_timers_set_delay and fgi_part_timers_set_delay share
-static fgi_status tm_set_delay(fgi_graph* g, const char* what, uint32_t n, const uint32_t* handle, const uint64_t* delay) {
+// delay[i] as a code of the table of distinct delays, which is uploaded again if it gained a delay
+static fgi_status tm_encode(fgi_graph* g, const char* what, uint32_t n, const uint64_t* delay, std::vector<uint32_t>& code) {
     Timers* t = g->tim;
-    std::vector<uint32_t> code(n);
+    code.resize(n);
     const size_t known = t->dtab_h.size();
     for (uint32_t i = 0; i < n; ++i) {
         const uint64_t d = delay[i];
@@ -681,6 +841,15 @@ static fgi_status tm_set_delay(fgi_graph* g, const char* what, uint32_t n, const
         FGI_TRY(grow(g, &t->dtab, &t->dtab_cap, std::max<uint64_t>(2 * t->dtab_h.size(), 64), "the timers' delay table"));
         FGI_HIP(g, hipMemcpyAsync(t->dtab, t->dtab_h.data(), t->dtab_h.size() * 8, hipMemcpyHostToDevice, s));
     }
+    return FGI_OK;
+}
+
+// handle[i] (distinct, in range) takes delay[i]: what fgi_timers_set_delay and fgi_part_timers_set_delay share
+static fgi_status tm_set_delay(fgi_graph* g, const char* what, uint32_t n, const uint32_t* handle, const uint64_t* delay) {
+    Timers* t = g->tim;
+    std::vector<uint32_t> code;
+    FGI_TRY(tm_encode(g, what, n, delay, code));
+    hipStream_t s = g->stream;
     FGI_TRY(tm_upload(g, 2, n));
     FGI_HIP(g, hipMemcpyAsync(t->up, handle, (size_t)n * 4, hipMemcpyHostToDevice, s));
     FGI_HIP(g, hipMemcpyAsync(t->up + n, code.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
@@ -688,7 +857,8 @@ static fgi_status tm_set_delay(fgi_graph* g, const char* what, uint32_t n, const
                        (const uint32_t*)(t->up + n), g->ext_slots, t->ctr);
     FGI_TRY(tm_sync(g, what));
     // the entries stored now (a slot that lost its code may hold one), the coded slots, the detached handles
-    t->holders = std::max<uint64_t>(t->holders, tm_stored(t) + t->ctr_h[kTCoded] + g->n_detached);
+    // (and the slots with an auto or transient-error code: counted apart, so a slot with both kinds counts twice)
+    t->holders = std::max<uint64_t>(t->holders, tm_stored(t) + t->ctr_h[kTCoded] + t->ctr_h[kTCodedA] + g->n_detached);
     return tm_reserve(g);
 }
 
@@ -853,11 +1023,13 @@ fgi_status fgi_timers_stats_get(fgi_graph* g, fgi_timer_stats* out) {
     return FGI_OK;
 }
 
-fgi_status fgi_timers_list(fgi_graph* g, uint32_t* handle, uint64_t* version, uint64_t* due, uint64_t cap, uint64_t* out_n) {
+// fgi_timers_list and fgi_timers_list_ex (kind nullable)
+static fgi_status tm_list(fgi_graph* g, const char* what, uint32_t* handle, uint64_t* version, uint64_t* due, uint8_t* kind,
+                          uint64_t cap, uint64_t* out_n) {
     if (!g) return FGI_EINVAL;
     if (out_n) *out_n = 0;
-    FGI_TRY(tm_usable(g, "fgi_timers_list"));
-    FGI_TRY(tm_sync(g, "fgi_timers_list"));
+    FGI_TRY(tm_usable(g, what));
+    FGI_TRY(tm_sync(g, what));
     const Timers* t = g->tim;
     const uint64_t top = tm_top(t);
     std::vector<TimerRec> recs(top);
@@ -868,16 +1040,121 @@ fgi_status fgi_timers_list(fgi_graph* g, uint32_t* handle, uint64_t* version, ui
     recs.erase(std::remove_if(recs.begin(), recs.end(), [&](const TimerRec& r) { return r.handle >= g->ext_handles; }), recs.end());
     std::sort(recs.begin(), recs.end(), [](const TimerRec& a, const TimerRec& b) { return a.handle < b.handle; });
     if (out_n) *out_n = recs.size();
-    if (!handle && !version && !due) return FGI_OK;
+    if (!handle && !version && !due && !kind) return FGI_OK;
     if (recs.size() > cap)
-        return set_err(g, FGI_ECAPACITY, "fgi_timers_list: %llu entries, the buffers hold %llu", (unsigned long long)recs.size(),
+        return set_err(g, FGI_ECAPACITY, "%s: %llu entries, the buffers hold %llu", what, (unsigned long long)recs.size(),
                        (unsigned long long)cap);
     for (size_t i = 0; i < recs.size(); ++i) {
         if (handle) handle[i] = recs[i].handle;
         if (version) version[i] = recs[i].version;
         if (due) due[i] = recs[i].due;
+        if (kind) kind[i] = (uint8_t)(recs[i].pad & kKindAuto);
     }
     return FGI_OK;
+}
+
+fgi_status fgi_timers_list(fgi_graph* g, uint32_t* handle, uint64_t* version, uint64_t* due, uint64_t cap, uint64_t* out_n) {
+    return tm_list(g, "fgi_timers_list", handle, version, due, nullptr, cap, out_n);
+}
+
+// ---- auto-invalidation (C-ABI 0.13) -------------------------------------------------------------------------
+
+// what the calls of the section check first: never on a partition, then open timers on a usable graph
+static fgi_status tm_auto_usable(fgi_graph* g, const char* what, bool need_auto) {
+    if (g->part || g->world > 1)
+        return set_err(g, FGI_ENOTSUP, "%s: auto-invalidation timers serve a single device, not a partition", what);
+    FGI_TRY(tm_usable(g, what));
+    if (need_auto && !g->tim->autos)
+        return set_err(g, FGI_ESTATE, "%s: auto-invalidation is not open (fgi_timers_auto_open)", what);
+    return FGI_OK;
+}
+
+// handles in range and distinct
+static fgi_status tm_check_handles(fgi_graph* g, const char* what, uint32_t n, const uint32_t* handle) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (handle[i] >= g->ext_handles) return set_err(g, FGI_EINVAL, "%s: handle %u out of range at %u", what, handle[i], i);
+    std::vector<uint32_t> sorted(handle, handle + n);
+    std::sort(sorted.begin(), sorted.end());
+    const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+    if (dup != sorted.end()) return set_err(g, FGI_EINVAL, "%s: handle %u listed twice", what, *dup);
+    return FGI_OK;
+}
+
+fgi_status fgi_timers_auto_open(fgi_graph* g, const fgi_timers_auto_config* cfg) {
+    if (!g || !cfg || cfg->struct_size < sizeof(fgi_timers_auto_config)) return FGI_EINVAL;
+    FGI_TRY(tm_auto_usable(g, "fgi_timers_auto_open", false));
+    Timers* t = g->tim;
+    if (t->autos) return set_err(g, FGI_ESTATE, "fgi_timers_auto_open: auto-invalidation is open");
+    hipStream_t s = g->stream;
+    DevOwn<uint32_t> a, b;   // until they are installed
+    if (hipMalloc(reinterpret_cast<void**>(&a.p), (size_t)g->ext_handles * 4) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&b.p), (size_t)g->ext_handles * 4) != hipSuccess)
+        return set_err(g, FGI_ENOMEM, "the auto-invalidation delays of %u handles", g->ext_handles);
+    FGI_HIP(g, hipMemsetAsync(a.p, 0, (size_t)g->ext_handles * 4, s));
+    FGI_HIP(g, hipMemsetAsync(b.p, 0, (size_t)g->ext_handles * 4, s));
+    FGI_HIP(g, hipStreamSynchronize(s));
+    t->adl = a.release();
+    t->tdl = b.release();
+    t->def_auto = cfg->default_auto_delay;
+    t->def_trans = cfg->default_transient_delay;
+    t->autos = true;
+    return tm_reserve(g);
+}
+
+fgi_status fgi_timers_set_auto_delay(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint64_t* auto_delay,
+                                     const uint64_t* transient_delay) {
+    const char* const what = "fgi_timers_set_auto_delay";
+    if (!g || (n && !handle)) return FGI_EINVAL;
+    FGI_TRY(tm_auto_usable(g, what, true));
+    FGI_TRY(tm_check_handles(g, what, n, handle));
+    if (!n || (!auto_delay && !transient_delay)) return FGI_OK;
+    Timers* t = g->tim;
+    std::vector<uint32_t> ac, tc;
+    if (auto_delay) FGI_TRY(tm_encode(g, what, n, auto_delay, ac));
+    if (transient_delay) FGI_TRY(tm_encode(g, what, n, transient_delay, tc));
+    hipStream_t s = g->stream;
+    FGI_TRY(tm_upload(g, 3, n));
+    FGI_HIP(g, hipMemcpyAsync(t->up, handle, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (auto_delay) FGI_HIP(g, hipMemcpyAsync(t->up + n, ac.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (transient_delay) FGI_HIP(g, hipMemcpyAsync(t->up + 2 * (size_t)n, tc.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_tm_set_auto, dim3((n + kTBlock - 1) / kTBlock), dim3(kTBlock), 0, s, t->adl, t->tdl, n,
+                       (const uint32_t*)t->up, auto_delay ? (const uint32_t*)(t->up + n) : (const uint32_t*)nullptr,
+                       transient_delay ? (const uint32_t*)(t->up + 2 * (size_t)n) : (const uint32_t*)nullptr, g->ext_slots, t->ctr);
+    FGI_TRY(tm_sync(g, what));
+    t->holders = std::max<uint64_t>(t->holders, tm_stored(t) + t->ctr_h[kTCoded] + t->ctr_h[kTCodedA] + g->n_detached);
+    return tm_reserve(g);
+}
+
+fgi_status fgi_timers_start_auto(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint8_t* transient) {
+    const char* const what = "fgi_timers_start_auto";
+    if (!g || (n && !handle)) return FGI_EINVAL;
+    FGI_TRY(tm_auto_usable(g, what, true));
+    FGI_TRY(tm_check_handles(g, what, n, handle));
+    return timers_arm_auto(g, n, handle, nullptr, nullptr, nullptr, transient);
+}
+
+fgi_status fgi_timers_auto_stats_get(fgi_graph* g, fgi_timer_auto_stats* out) {
+    if (!g || !out) return FGI_EINVAL;
+    memset(out, 0, sizeof(*out));
+    if (g->part || g->world > 1)
+        return set_err(g, FGI_ENOTSUP, "fgi_timers_auto_stats_get: auto-invalidation timers serve a single device, not a partition");
+    if (!g->tim || !g->tim->autos) return FGI_OK;
+    FGI_TRY(tm_usable(g, "fgi_timers_auto_stats_get"));
+    FGI_TRY(tm_sync(g, "fgi_timers_auto_stats_get"));
+    const Timers* t = g->tim;
+    out->armed_auto = t->ctr_h[kTArmedA];
+    out->merged = t->ctr_h[kTMerged];
+    out->fired_auto = t->ctr_h[kTFiredA];
+    return FGI_OK;
+}
+
+fgi_status fgi_timers_list_ex(fgi_graph* g, uint32_t* handle, uint64_t* version, uint64_t* due, uint8_t* kind, uint64_t cap,
+                              uint64_t* out_n) {
+    if (!g) return FGI_EINVAL;
+    if (out_n) *out_n = 0;
+    if (g->part || g->world > 1)
+        return set_err(g, FGI_ENOTSUP, "fgi_timers_list_ex: auto-invalidation timers serve a single device, not a partition");
+    return tm_list(g, "fgi_timers_list_ex", handle, version, due, kind, cap, out_n);
 }
 
 // ---- per rank of a partition (C-ABI 0.12) ------------------------------------------------------------------

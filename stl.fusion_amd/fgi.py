@@ -139,6 +139,19 @@ class TimerStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TimersAutoConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("default_auto_delay", C.c_uint64),
+                ("default_transient_delay", C.c_uint64)]
+
+
+class TimerAutoStats(C.Structure):
+    """fgi_timer_auto_stats: the auto-invalidation share of the timers' counters."""
+    _fields_ = [("armed_auto", C.c_uint64), ("merged", C.c_uint64), ("fired_auto", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 TIMER_NEVER = TIMER_NONE = 0xFFFFFFFFFFFFFFFF
 VIEW_PLANES = ("registered", "consistent", "computing", "ioso", "delay_started", "has_delay")
 
@@ -284,6 +297,12 @@ SIGNATURES = {
     "fgi_timers_next_due": [_G, _u64p, _u64p],
     "fgi_timers_stats_get": [_G, C.POINTER(TimerStats)],
     "fgi_timers_list": [_G, _u32p, _u64p, _u64p, C.c_uint64, _u64p],
+    "fgi_timers_auto_open": [_G, C.POINTER(TimersAutoConfig)],
+    "fgi_timers_set_auto_delay": [_G, C.c_uint32, _u32p, _u64p, _u64p],
+    "fgi_set_output_ex": [_G, C.c_uint32, _u32p, _u8p, _u8p, _u32p, C.c_uint64, _u64p, C.POINTER(WaveStats)],
+    "fgi_timers_start_auto": [_G, C.c_uint32, _u32p, _u8p],
+    "fgi_timers_auto_stats_get": [_G, C.POINTER(TimerAutoStats)],
+    "fgi_timers_list_ex": [_G, _u32p, _u64p, _u64p, _u8p, C.c_uint64, _u64p],
     "fgi_part_timers_open": [_G, C.POINTER(TimersConfig)],
     "fgi_part_timers_set_delay": [_G, C.c_uint32, _u32p, _u64p],
     "fgi_part_timers_run_due": [_G, C.c_uint64, _u32p, C.c_uint64, _u64p, _u64p, _u64p, C.POINTER(WaveStats)],
@@ -369,6 +388,12 @@ def build_steps(steps):
             out = np.empty(len(h), np.uint32)   # every element is written
         elif kind == "set_output":
             st.kind = STEP_SET_OUTPUT
+            if len(sp) > 2 and sp[2] is not None:   # transient-error flags (read with auto-invalidation open)
+                f = _u8(sp[2])
+                if len(f) != len(h):
+                    raise ValueError("set_output step: handles and transient flags differ in length")
+                keep.append(f)
+                st.flags = f.ctypes.data
             out = np.empty(len(h), np.uint8)
         else:
             raise ValueError(kind)
@@ -501,11 +526,20 @@ class Graph:
                                           _ptr(out, C.c_uint32)), "add_used")
         return out
 
-    def set_output(self, handles, stats: Optional[WaveStats] = None):
+    def set_output(self, handles, stats: Optional[WaveStats] = None, transient=None):
+        """fgi_set_output; with `transient` (a flag per handle: the output is a transient error) fgi_set_output_ex."""
         h = _u32(handles)
         out_set = np.zeros(len(h), np.uint8)
         ids = np.zeros(self.n_handles, np.uint32)
         n = C.c_uint64()
+        if transient is not None:
+            t = _u8(transient)
+            if len(t) != len(h):
+                raise ValueError("set_output: handles and transient flags differ in length")
+            self._check(self.lib.fgi_set_output_ex(self.h, len(h), _ptr(h, C.c_uint32), _ptr(t, C.c_uint8),
+                                                   _ptr(out_set, C.c_uint8), _ptr(ids, C.c_uint32), len(ids), C.byref(n),
+                                                   C.byref(stats) if stats is not None else None), "set_output")
+            return out_set, ids[:n.value].copy()
         self._check(self.lib.fgi_set_output(self.h, len(h), _ptr(h, C.c_uint32), _ptr(out_set, C.c_uint8),
                                             _ptr(ids, C.c_uint32), len(ids), C.byref(n),
                                             C.byref(stats) if stats is not None else None), "set_output")
@@ -524,7 +558,7 @@ class Graph:
     def run_batch(self, steps, stats: Optional[BatchStats] = None, want_ids: bool = True):
         """fgi_run_batch. `steps`: a list of ("invalidate", handles[, immediately]),
         ("begin_compute", slots, versions[, has_delay]), ("add_used", dependants, used),
-        ("set_output", handles). Returns (ids of every cascade of the batch, per-step outputs: detached
+        ("set_output", handles[, transient]). Returns (ids of every cascade of the batch, per-step outputs: detached
         handles / add_used results / set flags, None for invalidate)."""
         return self._batch(self.lib.fgi_run_batch, "run_batch", steps, stats, want_ids)
 
@@ -766,6 +800,48 @@ class Graph:
         self._check(self.lib.fgi_timers_list(self.h, _ptr(h, C.c_uint32), _ptr(v, C.c_uint64), _ptr(d, C.c_uint64),
                                              len(h), C.byref(n)), "timers_list")
         return h, v, d
+
+    # ---- auto-invalidation timers, armed at TrySetOutput (C-ABI 0.13) ----
+    def timers_auto_open(self, default_auto: int = 0, default_transient: int = 0):
+        """fgi_timers_auto_open: nodes that become Consistent arm their auto-invalidation on the device from here on."""
+        cfg = TimersAutoConfig(C.sizeof(TimersAutoConfig), 0, default_auto, default_transient)
+        self._check(self.lib.fgi_timers_auto_open(self.h, C.byref(cfg)), "timers_auto_open")
+
+    def timers_set_auto_delay(self, handles, auto_delays=None, transient_delays=None):
+        """fgi_timers_set_auto_delay: per handle, 0 = the default of that kind, TIMER_NEVER = none; None leaves
+        that kind's delays as they are."""
+        h = _u32(handles)
+        a = None if auto_delays is None else _u64(auto_delays)
+        t = None if transient_delays is None else _u64(transient_delays)
+        for d in (a, t):
+            if d is not None and len(d) != len(h):
+                raise ValueError("timers_set_auto_delay: handles and delays differ in length")
+        self._check(self.lib.fgi_timers_set_auto_delay(self.h, len(h), _ptr(h, C.c_uint32), _ptr(a, C.c_uint64),
+                                                       _ptr(t, C.c_uint64)), "timers_set_auto_delay")
+
+    def timers_start_auto(self, handles, transient=None):
+        """fgi_timers_start_auto: the auto arm rule over the listed handles (nodes registered Consistent in bulk)."""
+        h = _u32(handles)
+        t = None if transient is None else _u8(transient)
+        if t is not None and len(t) != len(h):
+            raise ValueError("timers_start_auto: handles and transient flags differ in length")
+        self._check(self.lib.fgi_timers_start_auto(self.h, len(h), _ptr(h, C.c_uint32), _ptr(t, C.c_uint8)),
+                    "timers_start_auto")
+
+    def timers_auto_stats(self) -> dict:
+        st = TimerAutoStats()
+        self._check(self.lib.fgi_timers_auto_stats_get(self.h, C.byref(st)), "timers_auto_stats")
+        return st.as_dict()
+
+    def timers_list_ex(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """fgi_timers_list_ex: (handles, versions, due times, kinds) of the stored entries, ascending by handle."""
+        n = C.c_uint64()
+        self._check(self.lib.fgi_timers_list_ex(self.h, None, None, None, None, 0, C.byref(n)), "timers_list_ex")
+        h, v, d = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint64)
+        k = np.zeros(n.value, np.uint8)
+        self._check(self.lib.fgi_timers_list_ex(self.h, _ptr(h, C.c_uint32), _ptr(v, C.c_uint64), _ptr(d, C.c_uint64),
+                                                _ptr(k, C.c_uint8), len(h), C.byref(n)), "timers_list_ex")
+        return h, v, d, k
 
     # ---- the same per rank of a partition (C-ABI 0.12); close, set_now, next_due, stats and list above serve a rank ----
     def part_timers_open(self, default_delay: int = 0, now: int = 0):

@@ -132,12 +132,32 @@ void ComputedRegistry::MoveSubs(uint32_t from, uint32_t to) {
     sub_head_[from] = kNone;
 }
 
+// the options of a node begun without ComputedOptions: the registry's auto-invalidation defaults
+ComputedOptions ComputedRegistry::DefaultOptions(std::chrono::nanoseconds delay) const {
+    ComputedOptions o;
+    o.InvalidationDelay = delay;
+    o.AutoInvalidationDelay = DefaultAutoInvalidationDelay;
+    o.TransientErrorInvalidationDelay = DefaultTransientErrorInvalidationDelay;
+    return o;
+}
+
 std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& input, bool has_delay) {
-    return BeginComputeImpl(input, has_delay, std::chrono::nanoseconds::zero());
+    return BeginComputeImpl(input, has_delay, DefaultOptions(std::chrono::nanoseconds::zero()));
+}
+
+std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& input, const ComputedOptions& options) {
+    return BeginComputeImpl(input, options.InvalidationDelay != std::chrono::nanoseconds::zero(), options);
+}
+
+// an auto-invalidation delay in the engine's ticks; 0: off (max(), or <= 0: "at once" is not built)
+static uint64_t AutoTicks(std::chrono::nanoseconds d) {
+    using ns = std::chrono::nanoseconds;
+    return d == ns::max() || d <= ns::zero() ? 0ull : (uint64_t)d.count();
 }
 
 std::shared_ptr<Computed> ComputedRegistry::BeginComputeImpl(const std::string& input, bool has_delay,
-                                                             std::chrono::nanoseconds delay) {
+                                                             const ComputedOptions& options) {
+    const std::chrono::nanoseconds delay = options.InvalidationDelay;
     Sync();
     const uint32_t s = SlotOf(input, true);
     auto c = std::make_shared<Computed>();
@@ -147,6 +167,8 @@ std::shared_ptr<Computed> ComputedRegistry::BeginComputeImpl(const std::string& 
     c->handle_ = s;
     c->version_ = NextVersion(current_[s] ? current_[s]->version_ : 0);
     c->delay_ = delay;
+    c->auto_delay_ = options.AutoInvalidationDelay;
+    c->transient_delay_ = options.TransientErrorInvalidationDelay;
     const uint8_t hd = has_delay ? 1 : 0;
     uint32_t detached = FGI_NONE;
     fgi_wave_stats ws{};
@@ -160,6 +182,14 @@ std::shared_ptr<Computed> ComputedRegistry::BeginComputeImpl(const std::string& 
         if (slot_delay_[s] != d) {
             Check(FGI_CALL(fgi_timers_set_delay, g_, 1, &s, &d), "fgi_timers_set_delay");
             slot_delay_[s] = d;
+        }
+        // ... and so are its auto-invalidation delays, once any node has had one
+        const uint64_t a = AutoTicks(c->auto_delay_), t = AutoTicks(c->transient_delay_);
+        if (a || t) EnsureAuto();
+        if (dev_auto_ && (slot_auto_[s] != a || slot_transient_[s] != t)) {
+            Check(FGI_CALL(fgi_timers_set_auto_delay, g_, 1, &s, &a, &t), "fgi_timers_set_auto_delay");
+            slot_auto_[s] = a;
+            slot_transient_[s] = t;
         }
         if (detached != FGI_NONE) maybe_armed_ = true;
     }
@@ -176,8 +206,14 @@ std::shared_ptr<Computed> ComputedRegistry::BeginComputeImpl(const std::string& 
             if (dev_timers_) {
                 // (the engine's move kernel did the same on its table)
             } else if (it != timers_.end() && it->second.version == old->version_) {
+                const bool was_auto = it->second.is_auto;
                 timers_[detached] = it->second;
                 timers_.erase(s);
+                // an auto entry of a node whose delay the displacement has just started: the delay timer joins
+                // it and the earlier due time stays (ComputedRegistry.cs:91-96 -> Computed.cs:186-197)
+                const uint32_t f = was_auto ? fgi_view_flags(&view_, detached) : 0u;
+                if ((f & FGI_STATE_MASK) == FGI_CONSISTENT && (f & FGI_F_INVALIDATION_DELAY_STARTED))
+                    StartTimer(detached, old->version_, old->delay_);
             } else {
                 const uint32_t f = fgi_view_flags(&view_, detached);   // the handle names the old node alone
                 if ((f & FGI_STATE_MASK) == FGI_CONSISTENT && (f & FGI_F_INVALIDATION_DELAY_STARTED))
@@ -203,7 +239,7 @@ std::shared_ptr<Computed> ComputedRegistry::BeginComputeImpl(const std::string& 
 }
 
 std::shared_ptr<Computed> ComputedRegistry::BeginCompute(const std::string& input, std::chrono::nanoseconds delay) {
-    return BeginComputeImpl(input, delay != std::chrono::nanoseconds::zero(), delay);
+    return BeginComputeImpl(input, delay != std::chrono::nanoseconds::zero(), DefaultOptions(delay));
 }
 
 uint32_t ComputedRegistry::AddUsed(Computed& dependant, Computed& used) {
@@ -214,19 +250,29 @@ uint32_t ComputedRegistry::AddUsed(Computed& dependant, Computed& used) {
     return out;
 }
 
-bool ComputedRegistry::SetOutput(Computed& c) {
+bool ComputedRegistry::SetOutput(Computed& c, bool transient_error) {
     Sync();
     uint8_t set = 0;
     const uint32_t h = c.handle_;
     uint64_t n = 0;
     uint32_t* ids = IdsBuffer(1024);
-    fgi_status s = FGI_CALL(fgi_set_output, g_, 1, &h, &set, ids, ids_cap_, &n, &last_);
+    const std::chrono::nanoseconds auto_delay = transient_error ? c.transient_delay_ : c.auto_delay_;
+    // the host path decides what the engine's kernel decides: a node that carries InvalidateOnSetOutput is
+    // invalidated by the call and never starts its auto-invalidation (Computed.cs:153-156)
+    const bool host_auto = !dev_timers_ && AutoTicks(auto_delay) != 0 && Owns(c);
+    const bool ioso = host_auto && (fgi_view_flags(&view_, h) & FGI_F_INVALIDATE_ON_SET_OUTPUT) != 0;
+    const uint8_t tr = transient_error ? 1 : 0;
+    fgi_status s = dev_auto_ ? FGI_CALL(fgi_set_output_ex, g_, 1, &h, &tr, &set, ids, ids_cap_, &n, &last_)
+                             : FGI_CALL(fgi_set_output, g_, 1, &h, &set, ids, ids_cap_, &n, &last_);
     if (s == FGI_ECAPACITY) {   // the cascade completed; fetch its ids with the right size
         ids = IdsBuffer(n);
         s = FGI_CALL(fgi_last_wave_ids, g_, ids, n, &n);
     }
     Check(s, "fgi_set_output");
     StartTimers(0);
+    if (dev_auto_) maybe_armed_ = true;   // the engine armed the node behind the call
+    if (host_auto && set && !ioso && (fgi_view_flags(&view_, h) & FGI_STATE_MASK) == FGI_CONSISTENT)
+        StartAutoTimer(h, c.version_, auto_delay);   // StartAutoInvalidation (Computed.cs:235-246)
     Dispatch(ids, n);
     return set != 0;
 }
@@ -645,6 +691,16 @@ void ComputedRegistry::EnsureTimers() {
     dev_timers_ = true;
 }
 
+void ComputedRegistry::EnsureAuto() {
+    if (dev_auto_ || !dev_timers_) return;
+    fgi_timers_auto_config cfg{};   // no graph defaults: every slot carries its node's own delays
+    cfg.struct_size = sizeof(cfg);
+    Check(FGI_CALL(fgi_timers_auto_open, g_, &cfg), "fgi_timers_auto_open");
+    slot_auto_.assign(n_slots_, 0);
+    slot_transient_.assign(n_slots_, 0);
+    dev_auto_ = true;
+}
+
 // Clock in the engine's ticks: nanoseconds since the timers opened, never running backwards
 uint64_t ComputedRegistry::NowTicks() {
     const auto d = std::chrono::duration_cast<std::chrono::nanoseconds>(Clock() - epoch_).count();
@@ -701,10 +757,28 @@ void ComputedRegistry::StartTimer(uint32_t handle, LTag version, std::chrono::na
     if (delay == ns::zero()) delay = DefaultInvalidationDelay;
     if (delay <= ns::zero() || delay == ns::max()) return;   // none, or never (TimeSpan.MaxValue, ComputedExt.cs:12)
     auto it = timers_.find(handle);
-    if (it != timers_.end() && it->second.version == version) return;   // already running
     const TimePoint now = Clock();
     const TimePoint due = delay > TimePoint::max() - now ? TimePoint::max() : now + delay;
-    timers_[handle] = Timer{due, version};
+    if (it != timers_.end() && it->second.version == version) {
+        // already running; an auto-invalidation's entry keeps the earlier due time (AddOrUpdateToEarlier)
+        if (it->second.is_auto && due < it->second.due) it->second.due = due;
+        return;
+    }
+    timers_[handle] = Timer{due, version, false};
+}
+
+void ComputedRegistry::StartAutoTimer(uint32_t handle, LTag version, std::chrono::nanoseconds delay) {
+    using ns = std::chrono::nanoseconds;
+    if (delay <= ns::zero() || delay == ns::max()) return;   // off (Computed.cs:244); "at once" is not built
+    const TimePoint now = Clock();
+    const TimePoint due = delay > TimePoint::max() - now ? TimePoint::max() : now + delay;
+    auto it = timers_.find(handle);
+    if (it != timers_.end() && it->second.version == version) {
+        if (due < it->second.due) it->second.due = due;
+        it->second.is_auto = true;
+        return;
+    }
+    timers_[handle] = Timer{due, version, true};
 }
 
 void ComputedRegistry::StartTimers(uint64_t ticket) {
@@ -758,10 +832,10 @@ size_t ComputedRegistry::RunDueTimers() {
     if (in_timers_ || timers_.empty()) return 0;
     CompletePending();   // a wave in flight may have invalidated a due node: its fan-out removes the entry
     const TimePoint now = Clock();
-    std::vector<std::pair<uint32_t, LTag>> entries;   // (handle, version)
+    std::vector<std::pair<uint32_t, LTag>> entries;   // (handle, version << 1 | auto)
     for (auto it = timers_.begin(); it != timers_.end();) {
         if (it->second.due <= now) {
-            entries.emplace_back(it->first, it->second.version);
+            entries.emplace_back(it->first, it->second.version << 1 | (it->second.is_auto ? 1u : 0u));
             it = timers_.erase(it);
         } else {
             ++it;
@@ -771,14 +845,15 @@ size_t ComputedRegistry::RunDueTimers() {
     std::sort(entries.begin(), entries.end());
     std::vector<uint32_t> due;
     for (const auto& e : entries) due.push_back(e.first);
-    // the entry fires only for the node it was started for, still waiting (Consistent, DelayStarted)
+    // the entry fires only for the node it was started for, still Consistent, and waiting (DelayStarted) unless
+    // the entry is an auto-invalidation's, whose timer invalidates any live node (ComputedExt.cs:35)
     std::vector<uint64_t> ver(due.size());
     std::vector<uint32_t> fl(due.size());
     Check(FGI_CALL(fgi_get_state, g_, (uint32_t)due.size(), due.data(), ver.data(), fl.data()), "fgi_get_state");
     std::vector<uint32_t> roots;
     for (size_t i = 0; i < due.size(); ++i)
-        if (ver[i] == entries[i].second && (fl[i] & FGI_STATE_MASK) == FGI_CONSISTENT &&
-            (fl[i] & FGI_F_INVALIDATION_DELAY_STARTED))
+        if (ver[i] == entries[i].second >> 1 && (fl[i] & FGI_STATE_MASK) == FGI_CONSISTENT &&
+            ((fl[i] & FGI_F_INVALIDATION_DELAY_STARTED) || (entries[i].second & 1)))
             roots.push_back(due[i]);
     if (roots.empty()) return 0;
     const std::vector<uint8_t> imm(roots.size(), 1);

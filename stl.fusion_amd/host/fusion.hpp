@@ -21,6 +21,10 @@
 //   a timer entry per node the engine reports as flagged (fgi_last_wave_flagged /
 //   fgi_wave_wait_flagged), on a registry clock tests can drive: no threads, no sleeping; RunDueTimers
 //   invalidates what is due.
+//   Auto-invalidation: TrySetOutput -> StartAutoInvalidation (Computed.cs:158, 235-246) schedules Invalidate(true)
+//   after ComputedOptions.AutoInvalidationDelay, or TransientErrorInvalidationDelay when the output is a
+//   transient error, on the same timer set with AddOrUpdateToEarlier (ComputedExt.cs:10-25) — here a second
+//   kind of entry on the same registry clock, or in the engine (fgi_timers_auto_open) with DeviceTimers.
 //   RPC replica invalidation: an inbound compute call waits for its computed's invalidation and
 //   then sends `$sys-c.Invalidate(callId)` to its peer (Client/Internal/RpcInboundComputeCall.cs:
 //   53-62, 102-106) — here a subscription (handle -> peer, call id), delivered per peer in batches
@@ -60,6 +64,17 @@ enum class ConsistencyState : uint32_t { Computing = 0, Consistent = 1, Invalida
 
 class Computed;
 class ComputedRegistry;
+
+// ComputedOptions' three delays (ComputedOptions.cs). InvalidationDelay: 0 = none, max() = never. The other two:
+// max() = off (TimeSpan.MaxValue, Computed.cs:244); a value <= 0, the reference's "invalidate at once"
+// (ComputedExt.cs:15-18), is not built and reads as off. The reference's default
+// TransientErrorInvalidationDelay is 1 s; here it is off unless set, so a registry that never sets it behaves
+// as it did before auto-invalidation existed.
+struct ComputedOptions {
+    std::chrono::nanoseconds InvalidationDelay{0};
+    std::chrono::nanoseconds AutoInvalidationDelay = std::chrono::nanoseconds::max();
+    std::chrono::nanoseconds TransientErrorInvalidationDelay = std::chrono::nanoseconds::max();
+};
 
 class FgiError : public std::runtime_error {
    public:
@@ -132,6 +147,9 @@ class Computed {
     bool gone_ = false;   // displaced without a detached handle: the slot names the newer node
     InvalidatedHandlerSet handlers_;
     std::chrono::nanoseconds delay_{0};          // ComputedOptions.InvalidationDelay (0: none, max(): never)
+    // AutoInvalidationDelay / TransientErrorInvalidationDelay as they hold for this node (max(): off)
+    std::chrono::nanoseconds auto_delay_ = std::chrono::nanoseconds::max();
+    std::chrono::nanoseconds transient_delay_ = std::chrono::nanoseconds::max();
     std::shared_ptr<std::promise<void>> when_;   // WhenInvalidated's promise, once asked for
     std::shared_future<void> when_f_;
 };
@@ -169,10 +187,15 @@ class ComputedRegistry {
     // ComputedOptions.InvalidationDelay: 0 = none, nanoseconds::max() = never (TimeSpan.MaxValue,
     // ComputedExt.cs:12: the node is flagged, no timer starts)
     std::shared_ptr<Computed> BeginCompute(const std::string& input, std::chrono::nanoseconds delay);
+    // every delay of the node given explicitly; the overloads above take the registry's
+    // DefaultAutoInvalidationDelay / DefaultTransientErrorInvalidationDelay
+    std::shared_ptr<Computed> BeginCompute(const std::string& input, const ComputedOptions& options);
     // dependant.AddUsed(used); returns the FGI_USED_* outcome (FGI_USED_ESTATE = the reference throws)
     uint32_t AddUsed(Computed& dependant, Computed& used);
     // TrySetOutput: true if the node was Computing; an InvalidateOnSetOutput node cascades at once
-    bool SetOutput(Computed& c);
+    // (Computed.cs:153-156), any other starts its auto-invalidation (Computed.cs:158): after its
+    // TransientErrorInvalidationDelay if transient_error, else after its AutoInvalidationDelay
+    bool SetOutput(Computed& c, bool transient_error = false);
     void InvalidateEverything();
     // one ComputedGraphPruner pass; returns (old, new) `_usedBy` totals of the pruned nodes
     std::pair<uint64_t, uint64_t> Prune();
@@ -230,6 +253,10 @@ class ComputedRegistry {
     using TimePoint = std::chrono::steady_clock::time_point;
     std::function<TimePoint()> Clock = [] { return std::chrono::steady_clock::now(); };
     std::chrono::nanoseconds DefaultInvalidationDelay{0};
+    // auto-invalidation of the nodes begun without ComputedOptions; max(): off (the reference's transient
+    // default is 1 s, see ComputedOptions above)
+    std::chrono::nanoseconds DefaultAutoInvalidationDelay = std::chrono::nanoseconds::max();
+    std::chrono::nanoseconds DefaultTransientErrorInvalidationDelay = std::chrono::nanoseconds::max();
     size_t RunDueTimers();
     size_t PendingTimers() const;
     // The timers live in the engine (fgi_timers_*, fgi.h): its kernels arm them behind every wave from the
@@ -300,6 +327,8 @@ class ComputedRegistry {
     // the flagged set of the last synchronous call (ticket 0) or of an asynchronous ticket -> timer entries
     void StartTimers(uint64_t ticket);
     void StartTimer(uint32_t handle, LTag version, std::chrono::nanoseconds delay);
+    // an auto-invalidation's entry; one of the same version keeps the earlier due time (AddOrUpdateToEarlier)
+    void StartAutoTimer(uint32_t handle, LTag version, std::chrono::nanoseconds delay);
     // the timers of the nodes a wave invalidated are removed before its handlers run
     void DropTimers(const uint32_t* ids, const uint64_t* bits, uint64_t words, uint64_t n);
     void ReportAccess(Computed& c, bool is_new);
@@ -323,14 +352,20 @@ class ComputedRegistry {
     struct Timer {
         TimePoint due;
         LTag version;
+        bool is_auto = false;   // fires on a Consistent node whether or not its delay has started
     };
     std::unordered_map<uint32_t, Timer> timers_;   // handle -> its pending delayed invalidation
     bool in_timers_ = false;                 // RunDueTimers is running (its own wave does not re-enter it)
     // DeviceTimers: opened by the first registry call; the engine's clock as last set; a lower bound of its next
     // due time, void (maybe_armed_) once a wave or a displacement may have armed an entry; each slot's delay
     // as the engine holds it
-    std::shared_ptr<Computed> BeginComputeImpl(const std::string& input, bool has_delay, std::chrono::nanoseconds delay);
+    std::shared_ptr<Computed> BeginComputeImpl(const std::string& input, bool has_delay, const ComputedOptions& options);
+    ComputedOptions DefaultOptions(std::chrono::nanoseconds delay) const;
     void EnsureTimers();
+    // DeviceTimers: the engine's auto-invalidation opens with the first node that has such a delay
+    void EnsureAuto();
+    bool dev_auto_ = false;
+    std::vector<uint64_t> slot_auto_, slot_transient_;   // each slot's auto delays as the engine holds them (0: none)
     uint64_t NowTicks();
     size_t RunDueTimersDevice();
     bool dev_timers_ = false, maybe_armed_ = false;
