@@ -289,7 +289,10 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
                              fgi_wave_stats* stats /*nullable*/);
 /* dependant.AddUsed(used) for each pair (IComputedImpl.AddUsed/AddUsedBy, Computed.cs:347-385,
  * reached from ComputedExt.UseNew / TryUseExisting, Internal/ComputedExt.cs:13-22, 70-76).
- * out_result[i] gets an FGI_USED_* code. Pairs in one call are applied as one batch.
+ * out_result[i] gets an FGI_USED_* code. Pairs in one call are applied as one batch. A `used` handle that
+ * names no node (an empty slot, a released detached handle) counts as Invalidated: FGI_USED_INVALIDATED, and
+ * the dependant gets InvalidateOnSetOutput (the reference passes node objects, so it has no such case; a
+ * computed that is gone can only be treated as one that must not be relied on).
  * Deviation from SURVEY.md §8(b)'s sketch `(src_slot, dst_slot, dst_version)`: the pairs are node
  * handles, as the reference's AddUsed takes node objects (Computed.cs:347, `AddUsed(IComputedImpl
  * used)`), not (input, version) keys. The dependant's version is its node's own (a handle names one
@@ -542,7 +545,9 @@ fgi_status fgi_part_unsubscribe_peer(fgi_graph* g, uint32_t peer, uint64_t* out_
  * detached handle handed out.
  * Move: when a displaced node survives to detached handle d, an entry (slot, its version) moves to d with its
  * due time unchanged; without one the arm rule runs on d. A batch applies its moves behind itself, in step
- * order, before it arms its records.
+ * order, before it arms its records. fgi_begin_compute arms its displacement cascade's records behind its install:
+ * a displaced node that the cascade also reached along an edge is armed under d like any other displaced node
+ * (not under its slot and then moved), so `moved` counts only entries that stood before the call.
  * Fire: fgi_timers_run_due(now) sets the clock, removes every entry with due <= now, and fires those whose
  * node still has the entry's version and is Consistent with InvalidationDelayStarted (the others are stale:
  * counted in dropped). The fired handles, ascending, are the roots of ONE wave with immediately = 1, run as
@@ -854,7 +859,12 @@ fgi_status fgi_stream(fgi_graph* g, void** stream);
 /* Traversal options (defaults in brackets). Results never depend on them; they exist so tests can
  * pin each code path and benches can compare them.
  *   FGI_OPT_DEAD_FILTER [1]  skip edges whose dependant was invalidated in an earlier level using
- *                            a per-wave bitmap (E_match then counts examined edges only)
+ *                            a per-wave bitmap (E_match then counts examined edges only). The bitmap is
+ *                            read without synchronisation, so an edge whose dependant another lane
+ *                            visits in the same level is examined or skipped as the lanes happen to
+ *                            run: with the filter on, e_match of a wave whose levels reach a node along
+ *                            several edges may differ between two runs of the same wave (every other
+ *                            count and every result is the same). 0 makes e_match exact and repeatable
  *   FGI_OPT_DIRECTION   [0]  0 auto (push/pull per level), 1 push only, 2 pull only
  *   FGI_OPT_PULL_ALPHA  [28] auto: pull when frontier edges > total edges / alpha
  *   FGI_OPT_PULL_BETA   [32] auto: after a pull level, pull again while the frontier holds more

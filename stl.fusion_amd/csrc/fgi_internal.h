@@ -635,6 +635,7 @@ struct fgi_graph {
     unsigned long long* flg_cnt = nullptr;   // [2] entries in flg_out[k]
     int flg_last = -1;                 // the last call's set: -1 empty, 0 / 1 flg_out[k], -2 a batch's (bflg_runs)
     std::vector<uint32_t> flg_drop;    // boundary slots the last call replaced (fgi_begin_compute): not in its set
+    bool flg_arm_later = false;        // fgi_begin_compute: the cascade's records arm behind the install, not the post-pass
     // Invalidated bitmap: bit h set = node h was invalidated by this wave. It is the frontier of a
     // pull level: every node invalidated before the previous level already had all its dependants
     // visited, so "an invalidated parent" and "a parent in the previous level's frontier" select

@@ -2921,7 +2921,13 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
     // displacement cascade first (ComputedRegistry.cs:91-94), then detach + install
     g->last_wave_n = 0;
     fanout_note(g, kCascWave);   // a call that displaces nothing ran an empty cascade
-    if (cnt[0]) FGI_TRY(run_wave(g, (uint32_t)cnt[0], droots, nullptr, stats, false, WaveOut::kCount));
+    // The cascade's flagged records arm behind the install (as a batch arms behind its moves): a displaced node that
+    // the cascade also reached along an edge has a record under its slot, which names the new node by then, so it
+    // is armed under its detached handle by the move below like a displaced node no edge reached.
+    g->flg_arm_later = true;
+    const fgi_status wst = cnt[0] ? run_wave(g, (uint32_t)cnt[0], droots, nullptr, stats, false, WaveOut::kCount) : FGI_OK;
+    g->flg_arm_later = false;
+    FGI_TRY(wst);
     view_begin(g);   // the cascade's share of the state view is in; the install's follows below
     // the call's slots hold new nodes when it returns: a displaced node the cascade flagged is not in the
     // call's flagged set under its slot (it lives on as out_detached[i])
@@ -2943,7 +2949,10 @@ fgi_status fgi_begin_compute(fgi_graph* g, uint32_t n, const uint32_t* slot, con
     // subscriptions follow the node: a displaced node that lives on takes its entries to its detached handle
     if (fanout_live(g)) FGI_TRY(fanout_move(g, n, slot, od.data()));
     // and so does its delay timer; a displaced node without one is armed under its detached handle
-    if (timers_on(g)) FGI_TRY(timers_move(g, n, slot, od.data()));
+    if (timers_on(g)) {
+        if (g->flg_last == 0) FGI_TRY(timers_arm_records(g, g->flg_out[0], g->n_handles, g->flg_cnt));
+        FGI_TRY(timers_move(g, n, slot, od.data()));
+    }
     return FGI_OK;
 }
 

@@ -3916,7 +3916,8 @@ static fgi_status launch_flagged(fgi_graph* g, int k) {
     hipLaunchKernelGGL(k_flag_list, dim3(grid), dim3(kBlock), 0, s, a);
     FGI_HIP(g, hipGetLastError());
     // the delay timers of what the wave flagged, armed on the device from the records (timers.hip)
-    if (timers_on(g)) FGI_TRY(timers_arm_records(g, g->flg_out[k], g->n_handles, g->flg_cnt + k));
+    // (fgi_begin_compute arms them itself, behind its install: a displaced node is armed where it lives on)
+    if (timers_on(g) && !g->flg_arm_later) FGI_TRY(timers_arm_records(g, g->flg_out[k], g->n_handles, g->flg_cnt + k));
     return FGI_OK;
 }
 

@@ -61,6 +61,17 @@ def test_async_pair(pkg, gpu_available):
     M.scn_async(_maker(pkg))
 
 
+def test_begin_reaches_own_slots(pkg, gpu_available):
+    M.scn_begin_reaches_own_slots(_maker(pkg))
+
+
+@pytest.mark.parametrize("labels", [-1, 1])
+def test_displaced_and_reached(pkg, gpu_available, labels):
+    """A displaced delayed node that the same call's cascade reached along an edge is armed under its detached
+    handle, not under its slot and then moved (fgi_timer_stats.moved stays 0)."""
+    M.scn_displaced_and_reached(_maker(pkg, labels))
+
+
 def test_open_on_a_populated_graph(pkg, gpu_available):
     M.scn_open_populated(_maker(pkg))
 

@@ -178,13 +178,14 @@ class Driver:
 
     def _oracle_begin(self, slots, versions, has_delay, handles):
         """begin_compute on the oracle; handles: the engine's detached handles or None. Returns the (slot,
-        detached handle) pairs of the displaced nodes that live on, and the slots whose node it invalidated."""
-        moves, inv = [], []
+        detached handle) pairs of the displaced nodes that live on, and the slots whose node the call invalidated:
+        by the displacement itself, or before it by the cascade of an earlier item of the same call (the oracle
+        takes the items one by one; such a node is no longer registered when its slot's turn comes)."""
+        moves = []
+        bv, bf = self.states()
         for i, (s, v) in enumerate(zip(_u32(slots), np.asarray(versions, np.uint64))):
             _, displaced = self.o.begin_compute(int(s), int(v), bool(has_delay[i]) if has_delay is not None else False)
             lives = displaced != O.NONE and (self.o.node_info(displaced)[2] & 3) != INVALIDATED
-            if displaced != O.NONE and not lives:
-                inv.append(int(s))
             if handles is not None:
                 assert (handles[i] != NONE) == lives, f"slot {s}: detached handle {handles[i]}, the oracle's node lives: {lives}"
             if lives:
@@ -192,6 +193,8 @@ class Driver:
                 assert d not in self.det, f"detached handle {d} handed out while it still names a node"
                 self.det[d] = displaced
                 moves.append((int(s), d))
+        moved = {s for s, _ in moves}
+        inv = [int(s) for s in _u32(slots) if bv[s] != 0 and (bf[s] & 3) != INVALIDATED and int(s) not in moved]
         return moves, inv
 
     def begin_compute(self, slots, versions, has_delay=None):
@@ -675,6 +678,35 @@ def scn_saturation(make):
     return drv
 
 
+def scn_begin_reaches_own_slots(make):
+    """0 -> 1 -> 2, and one BEGIN_COMPUTE step over all three slots: the displacement of 0 invalidates the nodes of
+    1 and 2 before their own turn comes (the oracle finds no registered node to displace there). The step's ids
+    are all three slots, whichever item invalidated them."""
+    drv = make(chain_arrays(4, [(0, 1), (1, 2)], seed=5), 2)
+    drv.open()
+    v = drv.states()[0]
+    ids = drv.batch([("begin_compute", [0, 1, 2], v[[0, 1, 2]] + np.uint64(2))])
+    assert list(ids) == [0, 1, 2] and not drv.det
+    assert list(drv.batch([("begin_compute", [3], v[[3]] + np.uint64(2)), ("invalidate", [0, 3])])) == [3]
+    return drv
+
+
+def scn_displaced_and_reached(make):
+    """0 -> 1 (delayed, delay 5, never flagged), and one fgi_begin_compute over both slots: the displacement of 0
+    reaches 1 along the edge, and 1 is displaced by the same call. Its node has no entry when the call begins, so
+    it is armed under its detached handle (no move), exactly as the delayed node of slot 2, which no edge reaches."""
+    drv = make(chain_arrays(4, [(0, 1)], delayed=[1, 2], seed=7), 3)
+    drv.open()
+    drv.set_delay([1, 2], [5, 5])
+    drv.set_now(2)
+    v = drv.states()[0]
+    d1, d2 = drv.begin_compute([0, 1, 2], v[[0, 1, 2]] + np.uint64(2))
+    assert drv.entries == {d1: (int(v[1]), 7), d2: (int(v[2]), 7)}
+    assert drv.c == dict(armed=2, fired=0, dropped=0, moved=0, runs=0) and drv.seen["displaced_armed"] == 2
+    assert drv.tick(7)[1] == 2
+    return drv
+
+
 def _alone(arrays, n_det, **kw):
     return Driver(arrays, n_det, **kw)
 
@@ -705,6 +737,15 @@ def test_small_scenarios_model():
     d = scn_displacement(_alone)
     assert d.c["moved"] == 1 and d.seen["displaced_armed"] == 1
     assert scn_cascading(_alone).c == dict(armed=2, fired=2, dropped=0, moved=0, runs=2)
+
+
+def test_displaced_and_reached_model():
+    assert scn_displaced_and_reached(_alone).c == dict(armed=2, fired=2, dropped=0, moved=0, runs=1)
+
+
+def test_begin_reaches_own_slots_model():
+    drv = scn_begin_reaches_own_slots(_alone)
+    assert (drv.states()[1][:4] & 3).tolist() == [COMPUTING] * 4
 
 
 def test_batch_model():
