@@ -601,8 +601,9 @@ fgi_status fgi_timers_list(fgi_graph* g, uint32_t* handle, uint64_t* version, ui
  * transient error (StartAutoInvalidation, Computed.cs:235-246, called by TrySetOutput, Computed.cs:158). Both go
  * through ComputedExt.Invalidate(TimeSpan) -> AddOrUpdateToEarlier (ComputedExt.cs:10-25), as the delay timers
  * of the section above do, so the entries share that section's pool, due pass and fire wave; an entry carries a
- * kind (bit 0: auto) beside (handle, version, due). Single device only: on a partitioned graph all six calls
- * return FGI_ENOTSUP.
+ * kind (bit 0: auto) beside (handle, version, due). These six calls serve a single device: on a partitioned
+ * graph all of them return FGI_ENOTSUP, and a rank uses the fgi_part_* calls of the section "auto-invalidation
+ * timers per rank of a partition" (C-ABI 0.14) below.
  * Opt-in: fgi_timers_auto_open needs open timers (FGI_ESTATE before fgi_timers_open, when already on, or on a
  * poisoned graph). Until it is called no call here allocates or launches anything: fgi_set_output,
  * fgi_set_output_ex and fgi_run_batch behave and launch exactly as before 0.13, fgi_timers_set_auto_delay and
@@ -733,6 +734,59 @@ fgi_status fgi_part_timers_fired_detached(fgi_graph* g, uint32_t* out_handles /*
 fgi_status fgi_part_local_timers_run_due(fgi_graph* const* gs, uint32_t p, uint64_t now,
                                          uint64_t* out_fired /*p, nullable*/, uint64_t* out_fired_detached /*p, nullable*/,
                                          fgi_wave_stats* stats /*p, nullable*/);
+
+/* ---- auto-invalidation timers per rank of a partition (C-ABI 0.14; timers.hip) ---------- */
+/* The auto-invalidation timers of the 0.13 section on a partitioned graph: each call is the 0.13 call per rank,
+ * on the rank's own table (the 0.12 section: local handles, h < n_slots is global slot rank * block + h), with
+ * slot arguments as global ids in the host's numbering; partition codes are never visible. The 0.13 names keep
+ * returning FGI_ENOTSUP on a partitioned graph, and the calls of this section return FGI_ENOTSUP on a graph that
+ * is not partitioned. The 0.13 section's rules (delays, candidates, the auto arm rule, the min merge, the fire
+ * rule, the move, the counters) apply per rank, with these differences.
+ * Opt-in, per rank: fgi_part_timers_auto_open needs the rank's timers open (FGI_ESTATE before
+ * fgi_part_timers_open, when auto is already on, or on a poisoned graph). Until it is called the rank allocates
+ * and launches nothing for this: fgi_part_set_output, fgi_part_set_output_ex and fgi_part_run_batch behave and
+ * launch exactly as before 0.14 whatever transient flags they are given, fgi_part_timers_set_auto_delay and
+ * fgi_part_timers_start_auto return FGI_ESTATE, fgi_part_timers_auto_stats_get returns zeros and
+ * fgi_part_timers_list_ex lists every kind as 0. fgi_timers_close turns a rank's auto off too.
+ * Rank-local calls: fgi_part_timers_auto_open, _set_auto_delay, _start_auto, _auto_stats_get and _list_ex use no
+ * collective. A slot >= n_global or a slot listed twice is FGI_EINVAL and nothing is stored. A slot the rank does
+ * not own is skipped, and the transient flag of a skipped item with it, so a host may hand every rank the same
+ * list, as with fgi_part_timers_set_delay. fgi_part_timers_list_ex returns local handles, as fgi_timers_list does
+ * on a rank.
+ * fgi_part_set_output_ex is collective, as fgi_part_set_output is, which is fgi_part_set_output_ex with
+ * transient == NULL. Candidates: the owned items whose node went Computing -> Consistent without
+ * InvalidateOnSetOutput. The auto arm rule runs in a kernel queued on the rank's stream behind the call's cascade
+ * and before the call's delay arm (the 0.12 section). It adds no wait and no copy back:
+ * fgi_wave_stats.host_syncs is what it is with auto closed. The transient flags are read only on a rank with
+ * auto open.
+ * Batches (fgi_part_run_batch, fgi_part_local_run_batch): a SET_OUTPUT step's flags (nullable) are its items'
+ * transient flags, read only on a rank with auto open. A partition applies a batch step by step, and the step
+ * auto-arms behind its own cascade, on the states that step left, at the item's own slot. If a later
+ * BEGIN_COMPUTE step of the same batch displaces the node, that step's move carries the entry to the detached
+ * handle, kind included, and the delay arm rule then runs there with the min merge, as for any displacement. The
+ * batch's flagged records still arm once behind the whole batch. THIS DIFFERS from the single-device batch of
+ * 0.13, which resolves every SET_OUTPUT item to the handle where its node lives when the batch ends and reads
+ * end-of-batch states: here a node that a later step of the same batch invalidates keeps a stale entry until the
+ * entry comes due, and is then counted in `dropped`. armed == fired + dropped + stored holds either way.
+ * Firing: fgi_part_timers_run_due is unchanged in shape. A due entry fires if its version matches and its node
+ * is Consistent and (InvalidationDelayStarted or the entry is auto). An auto entry on an owned slot becomes a
+ * root of the tick's wave; one on a detached handle is reported through fgi_part_timers_fired_detached, not
+ * cascaded. fired_auto counts both.
+ * Other calls: fgi_restore drops the rank's entries and keeps its auto delays and counters; fgi_release drops a
+ * detached handle's entry; fgi_timers_next_due, fgi_timers_stats_get and fgi_timers_list serve the rank as in
+ * the 0.12 section.
+ * Memory: 8 more bytes per local handle. The pool bound is the 0.13 section's with every term the rank's own: a
+ * slot with an auto or transient code counts only on the rank that owns it (no other rank stores the code). */
+fgi_status fgi_part_timers_auto_open(fgi_graph* g, const fgi_timers_auto_config* cfg);
+fgi_status fgi_part_timers_set_auto_delay(fgi_graph* g, uint32_t n, const uint32_t* slot /*global*/,
+                                          const uint64_t* auto_delay /*nullable*/, const uint64_t* transient_delay /*nullable*/);
+fgi_status fgi_part_set_output_ex(fgi_graph* g, uint32_t n, const uint32_t* slot, const uint8_t* transient /*nullable*/,
+                                  uint8_t* out_set, uint32_t* out_ids, uint64_t cap, uint64_t* out_n, fgi_wave_stats* stats);
+fgi_status fgi_part_timers_start_auto(fgi_graph* g, uint32_t n, const uint32_t* slot /*global*/,
+                                      const uint8_t* transient /*nullable*/);
+fgi_status fgi_part_timers_auto_stats_get(fgi_graph* g, fgi_timer_auto_stats* out);
+fgi_status fgi_part_timers_list_ex(fgi_graph* g, uint32_t* handle /*local*/, uint64_t* version, uint64_t* due,
+                                   uint8_t* kind /*bit 0: auto*/, uint64_t cap, uint64_t* out_n);
 
 /* ---- streaming batches (BASELINE.json configs[4]) ------------------------------- */
 /* One step of a batch: the arguments of the matching single call. */

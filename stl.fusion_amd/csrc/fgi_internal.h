@@ -1135,6 +1135,12 @@ bool timers_auto_on(const fgi_graph* g);
 // nullable): item i picks the transient-error delay.
 fgi_status timers_arm_auto(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint32_t* src, const uint8_t* code_dev,
                            const uint8_t* code_host, const uint8_t* transient, bool wait = true);
+// The same rule on a rank of a partition with auto open (fgi_part_timers_auto_open; else a no-op), queued on the
+// rank's stream: nothing waits, nothing is copied. Every array is the device's: item i names the host's global
+// slot slot_dev[i] (a slot of another rank is skipped), code_dev[i] is its set code (nullable: every item is a
+// candidate), transient_dev[i] its transient flag (nullable).
+fgi_status timers_arm_auto_part(fgi_graph* g, uint32_t n, const uint32_t* slot_dev, const uint8_t* code_dev,
+                                const uint8_t* transient_dev);
 // waits for what the timers' hooks queued and reads their counters
 fgi_status timers_wait(fgi_graph* g);
 // ---- sharded loads (shard.hip) ----

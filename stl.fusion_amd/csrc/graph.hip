@@ -1885,7 +1885,9 @@ fgi_status fgi_version(uint32_t* major, uint32_t* minor) {
     //      fgi_part_local_timers_run_due)
     // 0.13: auto-invalidation timers, armed at TrySetOutput (fgi_timers_auto_open, fgi_timers_set_auto_delay,
     //      fgi_set_output_ex, fgi_timers_start_auto, fgi_timers_auto_stats_get, fgi_timers_list_ex)
-    if (minor) *minor = 13;
+    // 0.14: the same per rank of a partition (fgi_part_timers_auto_open, fgi_part_timers_set_auto_delay,
+    //      fgi_part_set_output_ex, fgi_part_timers_start_auto, fgi_part_timers_auto_stats_get, fgi_part_timers_list_ex)
+    if (minor) *minor = 14;
     return FGI_OK;
 }
 
@@ -4260,9 +4262,12 @@ fgi_status part_add_used(fgi_graph* g, uint32_t n, const uint32_t* dep, const ui
 }
 
 // Computed.TrySetOutput (Computed.cs:141-160) over a partition; the nodes flagged
-// InvalidateOnSetOutput are the roots of one cascade on every rank. out_set: every item, every rank
-fgi_status part_set_output(fgi_graph* g, uint32_t n, const uint32_t* slot, uint8_t* out_set, fgi_wave_stats* stats,
-                           std::vector<uint32_t>* ids) {
+// InvalidateOnSetOutput are the roots of one cascade on every rank. out_set: every item, every rank.
+// transient (nullable, by item): read only on a rank with auto-invalidation open (fgi_part_timers_auto_open),
+// where the auto arm rule runs behind the cascade over the owned items that were set without
+// InvalidateOnSetOutput (timers.hip)
+fgi_status part_set_output(fgi_graph* g, uint32_t n, const uint32_t* slot, const uint8_t* transient, uint8_t* out_set,
+                           fgi_wave_stats* stats, std::vector<uint32_t>* ids) {
     PartView pv;
     FGI_TRY(part_check(g, &pv, "fgi_part_set_output"));
     if (n && !slot) return FGI_EINVAL;
@@ -4276,7 +4281,8 @@ fgi_status part_set_output(fgi_graph* g, uint32_t n, const uint32_t* slot, uint8
             lh.push_back(slot[i] - pv.base);
         }
     const uint32_t m = (uint32_t)li.size();
-    Tmp th, ts, tr, tfl;
+    const bool autos = timers_auto_on(g);   // the staging then tells "set" (1) from "set with InvalidateOnSetOutput" (2)
+    Tmp th, ts, tr, tfl, tas, tat;
     uint32_t *dh = nullptr, *droots = nullptr, *dfl = nullptr;
     uint8_t* dset = nullptr;
     FGI_TRY(fold(g));
@@ -4289,12 +4295,32 @@ fgi_status part_set_output(fgi_graph* g, uint32_t n, const uint32_t* slot, uint8
         FGI_TRY(tmalloc(g, tr, &droots, m));
         FGI_TRY(h2d(g, dh, lh.data(), m));
         hipLaunchKernelGGL(k_set_output, dim3(nblk(m)), dim3(256), 0, st, m, dh, g->n_handles,
-                           reinterpret_cast<unsigned long long*>(g->node), dset, droots, g->misc_dev, (uint8_t)1);
+                           reinterpret_cast<unsigned long long*>(g->node), dset, droots, g->misc_dev, (uint8_t)(autos ? 2 : 1));
         FGI_TRY(d2h(g, set.data(), dset, m));
     }
     unsigned long long nr = 0;
     FGI_TRY(d2h(g, &nr, g->misc_dev, 1));
     FGI_TRY(part_cascade(g, pv, (uint32_t)nr, droots, stats, ids));   // Invalidate() (Computed.cs:153-156)
+    // StartAutoInvalidation (Computed.cs:158) behind the cascade, on the states it left. The timer table is
+    // addressed in the host's numbering, so the owned items go up as the host's slots, not as codes; their set
+    // codes are dset, still on the device. Queued only; the host arrays live until the call's last wait below.
+    std::vector<uint32_t> as;
+    std::vector<uint8_t> at;
+    if (autos && m) {
+        uint32_t* das = nullptr;
+        uint8_t* dat = nullptr;
+        as.resize(m);
+        for (uint32_t j = 0; j < m; ++j) as[j] = part_slot_of(g, slot[li[j]]);
+        FGI_TRY(tmalloc(g, tas, &das, m));
+        FGI_TRY(h2d(g, das, as.data(), m));
+        if (transient) {
+            at.resize(m);
+            for (uint32_t j = 0; j < m; ++j) at[j] = transient[li[j]];
+            FGI_TRY(tmalloc(g, tat, &dat, m));
+            FGI_TRY(h2d(g, dat, at.data(), m));
+        }
+        FGI_TRY(timers_arm_auto_part(g, m, das, dset, dat));
+    }
     if (view_on(g) && m) {   // the owned items' new states (Consistent, or what the cascade left)
         view_begin(g);
         FGI_TRY(view_refresh(g, kViewLabels, dh, m));
@@ -4364,12 +4390,24 @@ fgi_status fgi_part_add_used(fgi_graph* g, uint32_t n, const uint32_t* dependant
     return part_add_used(g, n, part_codes_in(g, n, dependant, md), part_codes_in(g, n, used, mu), out_result);
 }
 
+fgi_status fgi_part_set_output_ex(fgi_graph* g, uint32_t n, const uint32_t* slot, const uint8_t* transient, uint8_t* out_set,
+                                  uint32_t* out_ids, uint64_t cap, uint64_t* out_n, fgi_wave_stats* stats) {
+    if (!g) return FGI_EINVAL;
+    if (out_n) *out_n = 0;
+    if (!g->part) return set_err(g, FGI_ENOTSUP, "fgi_part_set_output_ex: not a partitioned graph (fgi_set_output_ex)");
+    std::vector<uint32_t> ids, ms;
+    slot = part_codes_in(g, n, slot, ms);
+    FGI_TRY(part_set_output(g, n, slot, transient, out_set, stats, &ids));
+    FGI_TRY(timers_arm_part(g));   // behind the cascade and the auto arm
+    return part_copy_ids(ids, out_ids, cap, out_n);
+}
+
 fgi_status fgi_part_set_output(fgi_graph* g, uint32_t n, const uint32_t* slot, uint8_t* out_set, uint32_t* out_ids,
                                uint64_t cap, uint64_t* out_n, fgi_wave_stats* stats) {
     if (!g) return FGI_EINVAL;
     std::vector<uint32_t> ids, ms;
     slot = part_codes_in(g, n, slot, ms);
-    FGI_TRY(part_set_output(g, n, slot, out_set, stats, &ids));
+    FGI_TRY(part_set_output(g, n, slot, nullptr, out_set, stats, &ids));
     FGI_TRY(timers_arm_part(g));
     return part_copy_ids(ids, out_ids, cap, out_n);
 }
@@ -4495,7 +4533,8 @@ fgi_status fgi_part_run_batch(fgi_graph* g, uint32_t n_steps, const fgi_step* st
                 FGI_TRY(part_add_used(g, sp.n, sp.handles, sp.used, static_cast<uint32_t*>(sp.out)));
                 break;
             case FGI_STEP_SET_OUTPUT:
-                FGI_TRY(part_set_output(g, sp.n, sp.handles, static_cast<uint8_t*>(sp.out), &ws, &ids));
+                // (flags: the items' transient flags, read only on a rank with auto-invalidation open)
+                FGI_TRY(part_set_output(g, sp.n, sp.handles, sp.flags, static_cast<uint8_t*>(sp.out), &ws, &ids));
                 break;
         }
         if (stats && sp.kind != FGI_STEP_ADD_USED) stats->waves += 1;

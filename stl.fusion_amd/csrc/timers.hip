@@ -23,13 +23,13 @@
 // Everything is allocated by fgi_timers_open; a graph that never opens timers launches nothing here.
 //
 // Auto-invalidation (C-ABI 0.13: fgi_timers_auto_open, _set_auto_delay, _start_auto, _auto_stats_get, _list_ex, and
-// the hook timers_arm_auto behind fgi_set_output_ex and a batch's SET_OUTPUT steps; single device only): two more
-// delay codes per handle (adl, tdl; the same dtab) and a kind per record (TimerRec.pad bit 0: auto).
+// the hook timers_arm_auto behind fgi_set_output_ex and a batch's SET_OUTPUT steps; per rank of a partition below):
+// two more delay codes per handle (adl, tdl; the same dtab) and a kind per record (TimerRec.pad bit 0: auto).
 //   k_tm_arm_auto   the auto arm rule over (handle, set code, transient) candidates; it ends in tm_store, as the
 //                   delay arm rule does, where an entry of the same version takes the earlier due time and the
 //                   union of the kinds if either side is auto.
 // The due pass fires an auto entry on any Consistent node of its version; a moved auto entry is followed by the
-// delay arm rule on the detached handle. A rank's kernels never see an auto entry.
+// delay arm rule on the detached handle.
 //
 // Per rank of a partition (C-ABI 0.12: fgi_part_timers_open, _set_delay, _run_due, _fired_detached,
 // fgi_part_local_timers_run_due, and the hook timers_arm_part): the table covers the rank's local handles, as
@@ -44,6 +44,14 @@
 //                   wave, after the ranks' lists are gathered) and detached handles (reported, not cascaded).
 // A tick is a collective (fgi_part_timers_run_due): the verdicts, the counts and the sorted lists of all ranks
 // travel through part_allgather_words and part_allgatherv, then one partitioned wave runs from all the roots.
+//
+// Auto-invalidation per rank (C-ABI 0.14: fgi_part_timers_auto_open, _set_auto_delay, _start_auto, _auto_stats_get,
+// _list_ex, and the hook timers_arm_auto_part behind fgi_part_set_output_ex and a partition batch's SET_OUTPUT
+// steps): the same adl / tdl over the rank's local handles and the same kind bit.
+//   k_tm_arm_auto_part   k_tm_arm_auto over candidates named by the host's global slots: the local handle is
+//                        slot - base, a slot of another rank is skipped, the node is found through the rank's map.
+// A rank's due pass fires an auto entry on an owned slot into the tick's roots and one on a detached handle into
+// the detached list, and counts both in kTFiredA; the move, drop and min kernels serve a rank as they are.
 #include "fgi_internal.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -88,7 +96,7 @@ struct Timers {
     uint32_t* groots = nullptr;            // [groots_cap] every rank's fired slots, gathered in rank order
     uint64_t groots_cap = 0;
     std::vector<uint32_t> fdet;            // the last tick's fired detached handles, ascending (fgi_part_timers_fired_detached)
-    // auto-invalidation (fgi_timers_auto_open; single device only): null / false until then
+    // auto-invalidation (fgi_timers_auto_open, fgi_part_timers_auto_open): null / false until then
     bool autos = false;
     uint64_t def_auto = 0, def_trans = 0;  // the graph's default AutoInvalidationDelay / TransientErrorInvalidationDelay
     uint32_t* adl = nullptr;               // [ext_handles] auto delay codes, coded as dly (the same dtab)
@@ -333,15 +341,16 @@ __device__ __forceinline__ void tm_due(const TmTab& a, const M& m, TimerRec* dst
                    (w & kVMask) == r.version;
             a.ent[r.handle] = FGI_NONE;
         }
+        const bool fire_auto = fire && (r.pad & kKindAuto);   // (on a rank: owned slots and detached handles alike)
         bool fire_det = false;   // a rank's detached handle: no partitioned cascade reaches its node
         if constexpr (kPart) {
             fire_det = fire && r.handle >= a.ext_slots;
             fire = fire && !fire_det;
         }
         const unsigned long long mk = __ballot(keep), mf = __ballot(fire), md = __ballot(is_due && !fire && !fire_det);
-        unsigned long long mt = 0, ma = 0;
+        const unsigned long long ma = __ballot(fire_auto);
+        unsigned long long mt = 0;
         if constexpr (kPart) mt = __ballot(fire_det);
-        else ma = __ballot(fire && (r.pad & kKindAuto));
         unsigned long long bk = 0, bf = 0, bt = 0;
         if (lane == 0) {
             if (mk) bk = atomicAdd(a.ctr + kTNewTop, (unsigned long long)__popcll(mk));
@@ -515,6 +524,40 @@ __global__ __launch_bounds__(kTBlock) void k_tm_arm_part(TmTab a, TmPart p, cons
             if (rec) cand = h < p.n_local;
         }
         tm_arm(a, p, cand, h, lane);
+    }
+}
+
+// k_tm_arm_auto for a rank. Item i names the host's global slot slot[i]; its local handle is slot[i] - base (a slot
+// below base wraps past n_local) and a slot of another rank is no candidate, nor is an item whose set code is
+// not 1 (code nullable: every item). The node is read through the rank's map, the delay codes at the same local
+// handle, the set code and the transient flag (tr nullable) by item. An item that is skipped only clears `want`:
+// every lane of a wavefront reaches tm_store, and the trip count depends on the wavefront alone.
+__global__ __launch_bounds__(kTBlock) void k_tm_arm_auto_part(TmTab a, TmPart p, uint64_t n, const uint32_t* slot,
+                                                              const uint8_t* code, const uint8_t* tr) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t base = (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 64; base < n; base += nwaves * 64) {
+        const uint64_t i = base + lane;
+        bool want = false;
+        uint32_t h = 0;
+        unsigned long long v = 0, due = 0;
+        if (i < n && (!code || code[i] == 1)) {
+            const uint32_t l = slot[i] - p.base;
+            if (l < p.n_local && l < a.n_handles) {
+                const unsigned long long w = tm_word(a, p, l);
+                if ((w & kVMask) != 0 && word_state(w) == FGI_CONSISTENT) {
+                    const bool t = tr && tr[i];
+                    const unsigned long long d = tm_decode(a, t ? a.tdl[l] : a.adl[l], t ? a.def_trans : a.def_auto);
+                    if (d != 0 && d != FGI_TIMER_NEVER) {
+                        want = true;
+                        h = l;
+                        v = w & kVMask;
+                        due = tm_due_at(a, d);
+                    }
+                }
+            }
+        }
+        tm_store(a, want, h, v, due, kKindAuto, lane);
     }
 }
 
@@ -710,6 +753,15 @@ fgi_status timers_arm_auto(fgi_graph* g, uint32_t n, const uint32_t* handle, con
         return FGI_OK;
     }
     return tm_sync(g, "arming auto-invalidation timers");
+}
+
+fgi_status timers_arm_auto_part(fgi_graph* g, uint32_t n, const uint32_t* slot_dev, const uint8_t* code_dev,
+                                const uint8_t* transient_dev) {
+    if (!timers_auto_on(g) || !g->tim->part || !n) return FGI_OK;
+    hipLaunchKernelGGL(k_tm_arm_auto_part, dim3(tgrid(n)), dim3(kTBlock), 0, g->stream, tm_tab(g), tm_part(g), (uint64_t)n,
+                       slot_dev, code_dev, transient_dev);
+    FGI_HIP(g, hipGetLastError());
+    return FGI_OK;
 }
 
 fgi_status timers_wait(fgi_graph* g) {
@@ -1080,11 +1132,10 @@ static fgi_status tm_check_handles(fgi_graph* g, const char* what, uint32_t n, c
     return FGI_OK;
 }
 
-fgi_status fgi_timers_auto_open(fgi_graph* g, const fgi_timers_auto_config* cfg) {
-    if (!g || !cfg || cfg->struct_size < sizeof(fgi_timers_auto_config)) return FGI_EINVAL;
-    FGI_TRY(tm_auto_usable(g, "fgi_timers_auto_open", false));
+// what fgi_timers_auto_open and fgi_part_timers_auto_open share, on open timers
+static fgi_status tm_auto_open(fgi_graph* g, const char* what, const fgi_timers_auto_config* cfg) {
     Timers* t = g->tim;
-    if (t->autos) return set_err(g, FGI_ESTATE, "fgi_timers_auto_open: auto-invalidation is open");
+    if (t->autos) return set_err(g, FGI_ESTATE, "%s: auto-invalidation is open", what);
     hipStream_t s = g->stream;
     DevOwn<uint32_t> a, b;   // until they are installed
     if (hipMalloc(reinterpret_cast<void**>(&a.p), (size_t)g->ext_handles * 4) != hipSuccess ||
@@ -1101,12 +1152,16 @@ fgi_status fgi_timers_auto_open(fgi_graph* g, const fgi_timers_auto_config* cfg)
     return tm_reserve(g);
 }
 
-fgi_status fgi_timers_set_auto_delay(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint64_t* auto_delay,
-                                     const uint64_t* transient_delay) {
-    const char* const what = "fgi_timers_set_auto_delay";
-    if (!g || (n && !handle)) return FGI_EINVAL;
-    FGI_TRY(tm_auto_usable(g, what, true));
-    FGI_TRY(tm_check_handles(g, what, n, handle));
+fgi_status fgi_timers_auto_open(fgi_graph* g, const fgi_timers_auto_config* cfg) {
+    if (!g || !cfg || cfg->struct_size < sizeof(fgi_timers_auto_config)) return FGI_EINVAL;
+    FGI_TRY(tm_auto_usable(g, "fgi_timers_auto_open", false));
+    return tm_auto_open(g, "fgi_timers_auto_open", cfg);
+}
+
+// handle[i] (distinct, in range) takes auto_delay[i] and transient_delay[i] (each nullable): what
+// fgi_timers_set_auto_delay and fgi_part_timers_set_auto_delay share
+static fgi_status tm_set_auto_delay(fgi_graph* g, const char* what, uint32_t n, const uint32_t* handle, const uint64_t* auto_delay,
+                                    const uint64_t* transient_delay) {
     if (!n || (!auto_delay && !transient_delay)) return FGI_OK;
     Timers* t = g->tim;
     std::vector<uint32_t> ac, tc;
@@ -1123,6 +1178,15 @@ fgi_status fgi_timers_set_auto_delay(fgi_graph* g, uint32_t n, const uint32_t* h
     FGI_TRY(tm_sync(g, what));
     t->holders = std::max<uint64_t>(t->holders, tm_stored(t) + t->ctr_h[kTCoded] + t->ctr_h[kTCodedA] + g->n_detached);
     return tm_reserve(g);
+}
+
+fgi_status fgi_timers_set_auto_delay(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint64_t* auto_delay,
+                                     const uint64_t* transient_delay) {
+    const char* const what = "fgi_timers_set_auto_delay";
+    if (!g || (n && !handle)) return FGI_EINVAL;
+    FGI_TRY(tm_auto_usable(g, what, true));
+    FGI_TRY(tm_check_handles(g, what, n, handle));
+    return tm_set_auto_delay(g, what, n, handle, auto_delay, transient_delay);
 }
 
 fgi_status fgi_timers_start_auto(fgi_graph* g, uint32_t n, const uint32_t* handle, const uint8_t* transient) {
@@ -1275,6 +1339,97 @@ fgi_status fgi_part_local_timers_run_due(fgi_graph* const* gs, uint32_t p, uint6
         return fgi_part_timers_run_due(gs[r], now, nullptr, 0, nullptr, out_fired ? out_fired + r : nullptr,
                                        out_fired_detached ? out_fired_detached + r : nullptr, stats ? stats + r : nullptr);
     });
+}
+
+// ---- auto-invalidation per rank of a partition (C-ABI 0.14) -------------------------------------------------
+
+// what the calls of the section check first: a rank of a partition, then open timers on a usable graph
+static fgi_status tm_part_auto_usable(fgi_graph* g, const char* what, bool need_auto, PartView* pv) {
+    if (!g->part || !part_view(g, pv))
+        return set_err(g, FGI_ENOTSUP, "%s: not a partitioned graph (a single device has the fgi_timers_* call)", what);
+    FGI_TRY(tm_usable(g, what));
+    if (need_auto && !g->tim->autos)
+        return set_err(g, FGI_ESTATE, "%s: auto-invalidation is not open (fgi_part_timers_auto_open)", what);
+    return FGI_OK;
+}
+
+// global slots in range and distinct
+static fgi_status tm_check_slots(fgi_graph* g, const char* what, const PartView& pv, uint32_t n, const uint32_t* slot) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (slot[i] >= pv.n_global) return set_err(g, FGI_EINVAL, "%s: slot %u of %u at %u", what, slot[i], pv.n_global, i);
+    std::vector<uint32_t> sorted(slot, slot + n);
+    std::sort(sorted.begin(), sorted.end());
+    const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+    if (dup != sorted.end()) return set_err(g, FGI_EINVAL, "%s: slot %u listed twice", what, *dup);
+    return FGI_OK;
+}
+
+fgi_status fgi_part_timers_auto_open(fgi_graph* g, const fgi_timers_auto_config* cfg) {
+    if (!g || !cfg || cfg->struct_size < sizeof(fgi_timers_auto_config)) return FGI_EINVAL;
+    PartView pv{};
+    FGI_TRY(tm_part_auto_usable(g, "fgi_part_timers_auto_open", false, &pv));
+    return tm_auto_open(g, "fgi_part_timers_auto_open", cfg);
+}
+
+fgi_status fgi_part_timers_set_auto_delay(fgi_graph* g, uint32_t n, const uint32_t* slot, const uint64_t* auto_delay,
+                                          const uint64_t* transient_delay) {
+    const char* const what = "fgi_part_timers_set_auto_delay";
+    if (!g || (n && !slot)) return FGI_EINVAL;
+    PartView pv{};
+    FGI_TRY(tm_part_auto_usable(g, what, true, &pv));
+    FGI_TRY(tm_check_slots(g, what, pv, n, slot));
+    // the rank's share, as its local handles (a slot below base wraps past n_local)
+    std::vector<uint32_t> h;
+    std::vector<uint64_t> ad, td;
+    for (uint32_t i = 0; i < n; ++i)
+        if (slot[i] - pv.base < pv.n_local) {
+            h.push_back(slot[i] - pv.base);
+            if (auto_delay) ad.push_back(auto_delay[i]);
+            if (transient_delay) td.push_back(transient_delay[i]);
+        }
+    return tm_set_auto_delay(g, what, (uint32_t)h.size(), h.data(), auto_delay ? ad.data() : nullptr,
+                             transient_delay ? td.data() : nullptr);
+}
+
+fgi_status fgi_part_timers_start_auto(fgi_graph* g, uint32_t n, const uint32_t* slot, const uint8_t* transient) {
+    const char* const what = "fgi_part_timers_start_auto";
+    if (!g || (n && !slot)) return FGI_EINVAL;
+    PartView pv{};
+    FGI_TRY(tm_part_auto_usable(g, what, true, &pv));
+    FGI_TRY(tm_check_slots(g, what, pv, n, slot));
+    if (!n) return FGI_OK;
+    // the whole list goes up: the kernel skips the slots of other ranks, and their transient flags with them
+    Timers* t = g->tim;
+    hipStream_t s = g->stream;
+    const uint64_t bw = ((uint64_t)n + 3) / 4;
+    FGI_TRY(tm_upload(g, 1, (uint64_t)n + bw));
+    uint8_t* dt = reinterpret_cast<uint8_t*>(t->up + n);
+    FGI_HIP(g, hipMemcpyAsync(t->up, slot, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (transient) FGI_HIP(g, hipMemcpyAsync(dt, transient, n, hipMemcpyHostToDevice, s));
+    FGI_TRY(timers_arm_auto_part(g, n, t->up, nullptr, transient ? dt : nullptr));
+    return tm_sync(g, what);
+}
+
+fgi_status fgi_part_timers_auto_stats_get(fgi_graph* g, fgi_timer_auto_stats* out) {
+    if (!g || !out) return FGI_EINVAL;
+    memset(out, 0, sizeof(*out));
+    if (!g->part) return set_err(g, FGI_ENOTSUP, "fgi_part_timers_auto_stats_get: not a partitioned graph (fgi_timers_auto_stats_get)");
+    if (!g->tim || !g->tim->autos) return FGI_OK;
+    FGI_TRY(tm_usable(g, "fgi_part_timers_auto_stats_get"));
+    FGI_TRY(tm_sync(g, "fgi_part_timers_auto_stats_get"));
+    const Timers* t = g->tim;
+    out->armed_auto = t->ctr_h[kTArmedA];
+    out->merged = t->ctr_h[kTMerged];
+    out->fired_auto = t->ctr_h[kTFiredA];
+    return FGI_OK;
+}
+
+fgi_status fgi_part_timers_list_ex(fgi_graph* g, uint32_t* handle, uint64_t* version, uint64_t* due, uint8_t* kind, uint64_t cap,
+                                   uint64_t* out_n) {
+    if (!g) return FGI_EINVAL;
+    if (out_n) *out_n = 0;
+    if (!g->part) return set_err(g, FGI_ENOTSUP, "fgi_part_timers_list_ex: not a partitioned graph (fgi_timers_list_ex)");
+    return tm_list(g, "fgi_part_timers_list_ex", handle, version, due, kind, cap, out_n);
 }
 
 }  // extern "C"

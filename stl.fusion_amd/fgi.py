@@ -308,6 +308,12 @@ SIGNATURES = {
     "fgi_part_timers_run_due": [_G, C.c_uint64, _u32p, C.c_uint64, _u64p, _u64p, _u64p, C.POINTER(WaveStats)],
     "fgi_part_timers_fired_detached": [_G, _u32p, C.c_uint64, _u64p],
     "fgi_part_local_timers_run_due": [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint64, _u64p, _u64p, C.POINTER(WaveStats)],
+    "fgi_part_timers_auto_open": [_G, C.POINTER(TimersAutoConfig)],
+    "fgi_part_timers_set_auto_delay": [_G, C.c_uint32, _u32p, _u64p, _u64p],
+    "fgi_part_set_output_ex": [_G, C.c_uint32, _u32p, _u8p, _u8p, _u32p, C.c_uint64, _u64p, C.POINTER(WaveStats)],
+    "fgi_part_timers_start_auto": [_G, C.c_uint32, _u32p, _u8p],
+    "fgi_part_timers_auto_stats_get": [_G, C.POINTER(TimerAutoStats)],
+    "fgi_part_timers_list_ex": [_G, _u32p, _u64p, _u64p, _u8p, C.c_uint64, _u64p],
 }
 
 _lib = None
@@ -876,6 +882,49 @@ class Graph:
                     "part_timers_fired_detached")
         return h
 
+    # ---- auto-invalidation timers per rank of a partition (C-ABI 0.14); slots are global ids ----
+    def part_timers_auto_open(self, default_auto: int = 0, default_transient: int = 0):
+        """fgi_part_timers_auto_open (rank-local): this rank's nodes that become Consistent arm their
+        auto-invalidation on the device from here on."""
+        cfg = TimersAutoConfig(C.sizeof(TimersAutoConfig), 0, default_auto, default_transient)
+        self._check(self.lib.fgi_part_timers_auto_open(self.h, C.byref(cfg)), "part_timers_auto_open")
+
+    def part_timers_set_auto_delay(self, slots, auto_delays=None, transient_delays=None):
+        """fgi_part_timers_set_auto_delay (rank-local): global slots; those this rank does not own are skipped."""
+        h = _u32(slots)
+        a = None if auto_delays is None else _u64(auto_delays)
+        t = None if transient_delays is None else _u64(transient_delays)
+        for d in (a, t):
+            if d is not None and len(d) != len(h):
+                raise ValueError("part_timers_set_auto_delay: slots and delays differ in length")
+        self._check(self.lib.fgi_part_timers_set_auto_delay(self.h, len(h), _ptr(h, C.c_uint32), _ptr(a, C.c_uint64),
+                                                            _ptr(t, C.c_uint64)), "part_timers_set_auto_delay")
+
+    def part_timers_start_auto(self, slots, transient=None):
+        """fgi_part_timers_start_auto (rank-local): the auto arm rule over the listed global slots this rank owns."""
+        h = _u32(slots)
+        t = None if transient is None else _u8(transient)
+        if t is not None and len(t) != len(h):
+            raise ValueError("part_timers_start_auto: slots and transient flags differ in length")
+        self._check(self.lib.fgi_part_timers_start_auto(self.h, len(h), _ptr(h, C.c_uint32), _ptr(t, C.c_uint8)),
+                    "part_timers_start_auto")
+
+    def part_timers_auto_stats(self) -> dict:
+        st = TimerAutoStats()
+        self._check(self.lib.fgi_part_timers_auto_stats_get(self.h, C.byref(st)), "part_timers_auto_stats")
+        return st.as_dict()
+
+    def part_timers_list_ex(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """fgi_part_timers_list_ex: (local handles, versions, due times, kinds) of the rank's stored entries,
+        ascending by handle."""
+        n = C.c_uint64()
+        self._check(self.lib.fgi_part_timers_list_ex(self.h, None, None, None, None, 0, C.byref(n)), "part_timers_list_ex")
+        h, v, d = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint64)
+        k = np.zeros(n.value, np.uint8)
+        self._check(self.lib.fgi_part_timers_list_ex(self.h, _ptr(h, C.c_uint32), _ptr(v, C.c_uint64), _ptr(d, C.c_uint64),
+                                                     _ptr(k, C.c_uint8), len(h), C.byref(n)), "part_timers_list_ex")
+        return h, v, d, k
+
     def last_wave_flagged(self) -> Tuple[np.ndarray, np.ndarray]:
         """fgi_last_wave_flagged: (handles, state_flags) of the nodes the last call's cascade flagged
         (InvalidateOnSetOutput / InvalidationDelayStarted newly set) without invalidating them, ascending."""
@@ -1078,14 +1127,24 @@ class Graph:
                                                _ptr(out, C.c_uint32)), "part_add_used")
         return out
 
-    def part_set_output(self, slots, stats: Optional[WaveStats] = None):
+    def part_set_output(self, slots, stats: Optional[WaveStats] = None, transient=None):
+        """fgi_part_set_output, or fgi_part_set_output_ex when transient (the items' transient-error flags, read
+        on a rank with auto-invalidation open) is given."""
         h = _u32(slots)
         out_set = np.zeros(len(h), np.uint8)
         ids = np.zeros(self.n_handles, np.uint32)
         n = C.c_uint64()
-        self._check(self.lib.fgi_part_set_output(self.h, len(h), _ptr(h, C.c_uint32), _ptr(out_set, C.c_uint8),
-                                                 _ptr(ids, C.c_uint32), len(ids), C.byref(n),
-                                                 C.byref(stats) if stats is not None else None), "part_set_output")
+        st = C.byref(stats) if stats is not None else None
+        if transient is None:
+            self._check(self.lib.fgi_part_set_output(self.h, len(h), _ptr(h, C.c_uint32), _ptr(out_set, C.c_uint8),
+                                                     _ptr(ids, C.c_uint32), len(ids), C.byref(n), st), "part_set_output")
+        else:
+            t = _u8(transient)
+            if len(t) != len(h):
+                raise ValueError("part_set_output: slots and transient flags differ in length")
+            self._check(self.lib.fgi_part_set_output_ex(self.h, len(h), _ptr(h, C.c_uint32), _ptr(t, C.c_uint8),
+                                                        _ptr(out_set, C.c_uint8), _ptr(ids, C.c_uint32), len(ids), C.byref(n),
+                                                        st), "part_set_output_ex")
         return out_set, ids[:n.value].copy()
 
     def part_invalidate_all(self, stats: Optional[WaveStats] = None) -> np.ndarray:
